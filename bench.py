@@ -8,10 +8,22 @@ head, pose update, reprojection, resampling) — fp32 throughout, inputs already
 Weak scaling: every rank runs its own 16 pairs (the batch shards with no collective,
 SURVEY.md §8(e)); ``value`` = all pairs·iterations of all ranks ÷ the slowest rank's time.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
-Extra JSON fields:
+A plain run sets up, warms up, times the K steps and prints the headline line (``metric``,
+``value``, ``unit``, ``ms_per_step``, ``dtype``, ``config`` ...): nothing else touches the GPU,
+and no kernel timer sits inside the timed steps.  ``--dump-outputs DIR`` also writes what the
+last timed step returned (rank 0), one ``DIR/<name>.npy`` per output list, float32, stacked
+over the refinement iterations: ``flow_pose``, ``flow_pred``, ``rotation``, ``translation``,
+``mask``, ``delta_rotation``, ``delta_translation``.  An array above its share of the 60 MB
+budget is stored as a fixed, seeded sample of its flattened elements (``dump_outputs``).  Inputs
+and weights are seeded, so two builds run with the same arguments compare output for output.
+
+``--full`` adds every other measurement to the line: the live kernel timers and rooflines, the
+end-to-end, renderer and training-step legs and the CPU baseline.
+
+Extra JSON fields (``--full``):
 * ``roofline``: the kernel with the most GPU time in the step, ``conv_wino5_kernel`` — the
   SepConvGRU's F(4,5) Winograd convolution on fp32 MFMA — over ALL four of its launches per
   refinement iteration (z|r and q of the 1×5 and the 5×1 stage), bracketed live with HIP events
@@ -122,6 +134,56 @@ def time_steps(step, steps, warmup, world, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     return elapsed
+
+
+OUTPUT_NAMES = ("flow_pose", "flow_pred", "rotation", "translation", "mask", "delta_rotation",
+                "delta_translation")  # SCFlowDecoder.forward's 7 lists, one entry per iteration
+DUMP_BUDGET_BYTES = 60_000_000
+
+
+def dump_outputs(outs, path):
+    """Write the decoder's 7 output lists as ``path/<name>.npy`` (float32, the list stacked over
+    the iterations).  Each array gets an equal share of DUMP_BUDGET_BYTES; a larger one is stored
+    as a sample of its flattened elements at sorted indices drawn from a generator seeded with
+    the array's size alone, so equal arguments sample equal positions in every run and build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // (4 * len(OUTPUT_NAMES))
+    for name, seq in zip(OUTPUT_NAMES, outs):
+        t = torch.stack([x.detach().float() for x in seq])
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(t.numel()).integers(0, t.numel(), size=cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
+def result_line(args, world, elapsed, hb):
+    """The result line of a plain run; ``--full`` adds its other measurements to it."""
+    cfg_name = ("configs[4]" if (args.batch, args.size, args.iters) == (32, 512, 12)
+                else "configs[1]" if (args.batch, args.size, args.iters) == (16, 256, 8)
+                else "custom size")
+    return {
+        "metric": METRIC,
+        "value": round(world * args.batch * args.iters * args.steps / elapsed, 2),
+        "unit": "iters/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (seeded features, YCB-V-like poses/intrinsics, analytic ellipsoid depth; "
+                "deterministic random-init weights)",
+        "config": {"workload": f"SCFlowDecoder forward, {args.batch} pairs/GPU, "
+                               f"{args.size}x{args.size}, {args.iters} GRU iters (BASELINE {cfg_name})",
+                   "global_batch": args.batch * world, "image": args.size, "iters": args.iters,
+                   "launch": "hipGraph replay" if args.graph else "eager",
+                   "schedule": (f"two interleaved halves of {args.batch - hb} + {hb} pairs "
+                                f"(ping-pong)" if hb != args.batch else "whole batch"),
+                   "parallelism": f"dp{world}"},
+    }
 
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s
@@ -461,6 +523,11 @@ def main():
     ap.add_argument("--batch", type=int, default=16, help="pairs per GPU")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--iters", type=int, default=8)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: kernel timers and "
+                         "rooflines, end-to-end / renderer / training-step legs, CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--e2e-batch", type=int, default=32,
@@ -483,6 +550,8 @@ def main():
                     help="memory-side bytes per launch from rocprofv3 PMC passes "
                          "(default profiles/traffic_b{batch}_s{size}.json)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -528,7 +597,8 @@ def main():
               for name, n in per_step.items()}
     for t in timers.values():
         t.enabled = False
-    if not args.no_kernel_timer:
+    timed_kernels = args.full and not args.no_kernel_timer
+    if timed_kernels:
         dec.kernel_hooks.update(timers)
     if not args.graph:
         def step():
@@ -547,10 +617,25 @@ def main():
         g = GraphedForward(dec, inp, warmup=args.warmup, before_capture=arm, invalid_flow_num=0.0)
         step = g.replay
 
+    last = {}
+    if args.dump_outputs:  # keep what each step returns: the last timed step's is written out
+        run = step
+
+        def step():
+            last["out"] = run()
     elapsed = time_steps(step, args.steps, 0, world, dev)
     for t in timers.values():
         t.enabled = False
-    if not args.graph and not args.no_kernel_timer:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last.pop("out"), args.dump_outputs)
+    hb = dec.hook_batch or args.batch  # pairs per launch (a ping-pong half: batch / 2)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result_line(args, world, elapsed, hb)), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    if not args.graph and timed_kernels:
         step()  # the queue refilled past the timed region's final synchronize
         for name, t in timers.items():
             t.enabled = name not in live
@@ -607,11 +692,8 @@ def main():
         except Exception as e:  # the extra leg must not take the headline line down with it
             train = {"error": f"{type(e).__name__}: {e}"[:400]}
 
-    units = world * args.batch * args.iters * args.steps
-    value = units / elapsed
     h8 = args.size // 8
-    hb = dec.hook_batch or args.batch  # pairs per bracketed launch (a ping-pong half: batch / 2)
-    m_px = hb * h8 * h8
+    m_px = hb * h8 * h8  # pixels per bracketed launch
     hc, xc = dec.h_channels, dec.cxt_channels
     tpath = args.traffic_json or os.path.join(ROOT, "profiles", f"traffic_b{hb}_s{args.size}.json")
     tj, traffic = load_traffic(tpath)
@@ -670,34 +752,10 @@ def main():
                                      fullres_alone)
 
     if rank == 0:
-        cfg_name = ("configs[4]" if (args.batch, args.size, args.iters) == (32, 512, 12)
-                    else "configs[1]" if (args.batch, args.size, args.iters) == (16, 256, 8)
-                    else "custom size")
-        res = {
-            "metric": METRIC,
-            "value": round(value, 2),
-            "unit": "iters/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic (seeded features, YCB-V-like poses/intrinsics, analytic ellipsoid depth; "
-                    "deterministic random-init weights)",
-            "config": {"workload": f"SCFlowDecoder forward, {args.batch} pairs/GPU, "
-                                   f"{args.size}x{args.size}, {args.iters} GRU iters (BASELINE {cfg_name})",
-                       "global_batch": args.batch * world, "image": args.size, "iters": args.iters,
-                       "launch": "hipGraph replay" if args.graph else "eager",
-                       "schedule": (f"two interleaved halves of {args.batch - hb} + {hb} pairs "
-                                    f"(ping-pong)" if hb != args.batch else "whole batch"),
-                       "parallelism": f"dp{world}"},
-            "roofline": headline,
-            "rooflines_secondary": secondary,
-            "traffic_source": os.path.relpath(tpath, ROOT) if tj else None,
-        }
+        res = result_line(args, world, elapsed, hb)
+        res["roofline"] = headline
+        res["rooflines_secondary"] = secondary
+        res["traffic_source"] = os.path.relpath(tpath, ROOT) if tj else None
         if e2e is not None:
             res["end_to_end"] = e2e
         if train is not None:

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="--steps 10 --warmup 3 --no-cpu-baseline --e2e-batch 0 --train-batch 0"
+B="--full --steps 10 --warmup 3 --no-cpu-baseline --e2e-batch 0 --train-batch 0"
 C4="--batch 32 --size 512 --iters 12"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/kt -o run -- python3 $R/bench.py $B > $OUT/bench_kt_c1.json 2> $OUT/kt.err || exit 1
 DB=$(find $OUT/kt -name "*.db" | head -1)

@@ -7,7 +7,7 @@
 #   test                 whole GPU suite, no -x (every collected test reached)
 #   test=EXPR            GPU tests matching -k EXPR, -x
 #   smoke                __graft_entry__.smoke()
-#   bench[=ARGS]         bench.py [ARGS]                      → bench.json
+#   bench[=ARGS]         bench.py --full [ARGS]               → bench.json
 #   c4                   configs[4] bench line (B=32, 512², 12 iterations) → bench_c4.json
 #   dec[=ARGS]           decoder-only bench leg, 20 steps     → dec.json (one line printed)
 #   conv=B:S:ONLY[:stamps]   tools/conv_bench.py at batch B, feature size S, shapes ONLY
@@ -29,7 +29,7 @@
 TAG=${1:?tag}; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/s_$TAG; mkdir -p $OUT; cd $R; export TMPDIR=/tmp
-DEC="--no-cpu-baseline --e2e-batch 0 --train-batch 0"
+DEC="--full --no-cpu-baseline --e2e-batch 0 --train-batch 0"
 C4="--batch 32 --size 512 --iters 12"
 line() { python3 -c "import json,sys;d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]);print(sys.argv[2], d['value'], d['ms_per_step'], d.get('roofline',{}).get('frac'))" "$@"; }
 cfg() { [ "$2" = 64 ] && echo "$C4" || echo "--batch $1"; }  # conv_bench size → bench config
@@ -49,10 +49,10 @@ for STEP in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1 || exit 5
       tail -2 $OUT/smoke.txt ;;
     bench)
-      timeout -k 10 500 python bench.py $V > $OUT/bench.json 2> $OUT/bench.err || exit 6
+      timeout -k 10 500 python bench.py --full $V > $OUT/bench.json 2> $OUT/bench.err || exit 6
       line $OUT/bench.json bench ;;
     c4)
-      timeout -k 10 300 python bench.py $C4 --no-cpu-baseline --e2e-batch 0 --train-batch 0 > $OUT/bench_c4.json 2> $OUT/bench_c4.err || exit 7
+      timeout -k 10 300 python bench.py $C4 $DEC > $OUT/bench_c4.json 2> $OUT/bench_c4.err || exit 7
       line $OUT/bench_c4.json c4 ;;
     dec)
       timeout -k 10 300 python bench.py --steps 20 --warmup 3 $DEC $V > $OUT/dec.json 2> $OUT/dec.err || exit 8
