@@ -110,13 +110,34 @@ int scflow_corr_lookup_conv1x1(const float* pyr, const float* flow, const float*
                                int num_levels, int radius, int cout, int act, int align_corners,
                                void* stream);
 long long scflow_corr_lookup_conv1x1_lds_bytes(void);
+/* Occlusion-masked lookup (the reference's mask_corr, scflow_decoder.py:189-207: corr · mask
+ * before the motion encoder): out[m][k] = mask[m] · lookup(pyr, flow)[m][k], mask [n·h·w], for
+ * every layout and kernel of scflow_corr_lookup_ex (tiled = 0) / scflow_corr_lookup_tiled (tiled
+ * != 0).  The multiply happens where the sample is stored: no extra pass over the L·(2r+1)²
+ * features, no extra launch; the result equals (unmasked lookup) · mask bit for bit.  mask NULL:
+ * exactly the unmasked call. */
+int scflow_corr_lookup_masked(const float* pyr, const float* flow, int flow_layout,
+                              const float* mask, float* out, int out_layout, int out_stride, int n,
+                              int h, int w, int num_levels, int radius, int align_corners, int tiled,
+                              void* stream);
+/* scflow_corr_lookup_conv1x1 on the masked lookup: out[m][·] = act(W·(mask[m]·lookup[m]) + bias).
+ * The sample is scaled as it enters the LDS A row (the reference's order, conv(corr · mask)), not
+ * the accumulator, so the result is bit-identical to scflow_corr_lookup_masked (tiled) followed
+ * by the SCFLOW_CONV_1X1W conv.  mask NULL: exactly scflow_corr_lookup_conv1x1. */
+int scflow_corr_lookup_conv1x1_masked(const float* pyr, const float* flow, const float* mask,
+                                      const float* weight, const float* bias, float* out,
+                                      int out_stride, int n, int h, int w, int num_levels,
+                                      int radius, int cout, int act, int align_corners,
+                                      void* stream);
 /* ABI markers: scflow_abi_version() returns SCFLOW_ABI_VERSION of the header the library was
  * built from (2: scflow_conv_args ends with the F(4×4,3×3) workspace fields ws / ws_bytes, and
  * scflow_conv_pick_bk may return SCFLOW_CONV_WINO4; 3: + scflow_xhead_pred and its workspace
- * query); scflow_conv_args_size() its
+ * query; 4: + the occlusion-masked entries scflow_corr_lookup_masked,
+ * scflow_corr_lookup_conv1x1_masked, scflow_flow_downsample_masked, scflow_pose_step_masked and
+ * scflow_corr_lookup_backward_masked — new exports only); scflow_conv_args_size() its
  * sizeof(scflow_conv_args).  A binding checks both before its first call (scflow_amd/_lib.py
  * does, at load). */
-#define SCFLOW_ABI_VERSION 3
+#define SCFLOW_ABI_VERSION 4
 int scflow_abi_version(void);
 long long scflow_conv_args_size(void);
 /* Tuning only: launch-time environment switches (SCFLOW_WINO4_DEPTH, SCFLOW_WINO4_XCD,
@@ -254,6 +275,12 @@ int scflow_pose_update_flow(const float* drot6, const float* dt, const float* R_
  * channels-last to out0 (pixel stride s0) and, if out1 != NULL, also to out1 (stride s1). */
 int scflow_flow_downsample(const float* flow, float* out0, int s0, float* out1, int s1, int n,
                            int H, int W, int h, int w, float value_scale, void* stream);
+/* ... under the reference's mask_flow (scflow_decoder.py:189-207: the flow entering the motion
+ * encoder is flow · mask): out0 keeps the unmasked ↓8 flow (the lookup's centroids), out1 and
+ * outm (stride sm; either may be NULL) receive it times mask[n·h·w].  mask NULL: × 1. */
+int scflow_flow_downsample_masked(const float* flow, float* out0, int s0, float* out1, int s1,
+                                  const float* mask, float* outm, int sm, int n, int H, int W,
+                                  int h, int w, float value_scale, void* stream);
 
 /* a11 up: flow_out[n][2][H][W] = value_scale·bilinear(lr + delta) and mask_out[n][1][H][W] =
  * bilinear(mask); lr/delta are channels-last [n·h·w][2] (delta may be NULL), mask [n·h·w][1]
@@ -377,6 +404,26 @@ int scflow_pose_step_heads(const float* x, int xsplit, const float* xbias, int k
                            float* mask_up, float* lr_next, int s_next, float* hx_next, int s_hx,
                            int h, int w, float up_scale, float down_scale, int parts,
                            void* stream);
+
+/* scflow_pose_step_masked: the superset of scflow_pose_step / _part / _heads with the masked
+ *   iteration tail (mask_flow).  x NULL: scflow_pose_step_part's arguments (drot / dt are read);
+ *   x != NULL: scflow_pose_step_heads' (drot / dt are written).  mask_next [n·h·w] is the mask
+ *   this iteration just predicted: lr_next still receives the unmasked ↓8 flow (the next
+ *   lookup's centroids), lrm_next (pixel stride s_lrm; may be NULL; must alias neither lr nor
+ *   lr_next) and hx_next receive lr_next · mask_next — the flow branch's input and the motion
+ *   features' flow channels of the next iteration.  mask_next NULL: hx_next and lrm_next receive
+ *   lr_next, everything as the unmasked entries bit for bit.  The full-resolution outputs never
+ *   depend on mask_next. */
+int scflow_pose_step_masked(const float* x, int xsplit, const float* xbias, int k, const float* Wr,
+                            const float* br, int rch, const float* Wt, const float* bt,
+                            const long long* label, int num_class, float* drot, float* dt,
+                            const float* R_src, const float* t_src, const float* K,
+                            const float* points, float* R_dst, float* t_dst, float* flow, int n,
+                            int H, int W, float weight, int depth_transform, float invalid_num,
+                            const float* lr, const float* delta, const float* mask, float* flow_up,
+                            float* mask_up, float* lr_next, int s_next, float* hx_next, int s_hx,
+                            const float* mask_next, float* lrm_next, int s_lrm, int h, int w,
+                            float up_scale, float down_scale, int parts, void* stream);
 
 /* §8(f)-1: RAFTEncoder (Basic) — feature encoder (InstanceNorm) and context encoder (BatchNorm,
  * eval statistics), models/encoder/raft_encoder.py:286-314, BasicBlock models/backbone/resnet.py:
@@ -631,6 +678,13 @@ int scflow_conv_wgrad_batched(const scflow_wgrad_args* args, int segs, const flo
 int scflow_corr_lookup_backward(const float* dout, int out_layout, int out_stride, const float* flow,
                                 int flow_layout, float* dpyr, int n, int h, int w, int num_levels,
                                 int radius, void* stream);
+/* The adjoint of scflow_corr_lookup_masked with respect to the pyramid: scatters
+ * mask[m] · dout[m][k] (mask [n·h·w]; the same bits as scflow_corr_lookup_backward fed
+ * dout · mask).  No gradient for the mask or the flow.  mask NULL: scflow_corr_lookup_backward. */
+int scflow_corr_lookup_backward_masked(const float* dout, int out_layout, int out_stride,
+                                       const float* flow, int flow_layout, const float* mask,
+                                       float* dpyr, int n, int h, int w, int num_levels, int radius,
+                                       void* stream);
 
 /* §8(f)-3 mesh renderer (replaces pytorch3d's MeshRasterizer + HardPhongShader behind
  * models/utils/rendering.py:196-248, configured as scflow_ycbv_real.py:261-274).

@@ -23,7 +23,7 @@ CONV_WINO = 2  # scflow_conv_args.bk: Winograd F(2x2,3x3) packing/kernel (SCFLOW
 CONV_1X1W = 3  # scflow_conv_args.bk: wide 1x1 packing/kernel (SCFLOW_CONV_1X1W)
 CONV_WINO4 = 4  # scflow_conv_args.bk: Winograd F(4x4,3x3) packing/kernel (SCFLOW_CONV_WINO4)
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
-ABI_VERSION = 3  # SCFLOW_ABI_VERSION of include/scflow_hip.h this binding mirrors
+ABI_VERSION = 4  # SCFLOW_ABI_VERSION of include/scflow_hip.h this binding mirrors
 
 
 class ConvArgs(ctypes.Structure):
@@ -113,6 +113,11 @@ SIGNATURES = {
     "scflow_corr_lookup_conv1x1_lds_bytes": (c_ll, []),
     "scflow_corr_lookup_tiled": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int,
                                          c_int, c_int, c_int, c_vp]),
+    "scflow_corr_lookup_masked": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int,
+                                          c_int, c_int, c_int, c_int, c_int, c_vp]),
+    "scflow_corr_lookup_conv1x1_masked": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
+                                                  c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                  c_vp]),
     "scflow_in_apply": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
     "scflow_colsum": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp]),
     "scflow_colsum_workspace": (c_int, [c_int, c_int]),
@@ -148,6 +153,8 @@ SIGNATURES = {
                                         c_int, c_int, c_float, c_int, c_float, c_vp]),
     "scflow_flow_downsample": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int,
                                        c_int, c_float, c_vp]),
+    "scflow_flow_downsample_masked": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int,
+                                              c_int, c_int, c_int, c_int, c_float, c_vp]),
     "scflow_flow_upsample": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
                                      c_float, c_vp]),
     "scflow_pose_step": (c_int, [c_vp] * 9 + [c_int, c_int, c_int, c_float, c_int, c_float] +
@@ -159,6 +166,11 @@ SIGNATURES = {
                                        c_int, c_vp, c_vp] + [c_vp] * 7 +
                                [c_int, c_int, c_int, c_float, c_int, c_float] + [c_vp] * 6 +
                                [c_int, c_vp, c_int, c_int, c_int, c_float, c_float, c_int, c_vp]),
+    "scflow_pose_step_masked": (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp,
+                                        c_int, c_vp, c_vp] + [c_vp] * 7 +
+                                [c_int, c_int, c_int, c_float, c_int, c_float] + [c_vp] * 6 +
+                                [c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_float,
+                                 c_float, c_int, c_vp]),
     "scflow_sync_event_create": (c_int, [ctypes.POINTER(c_vp)]),
     "scflow_sync_event_destroy": (c_int, [c_vp]),
     "scflow_sync_event_record": (c_int, [c_vp, c_vp]),
@@ -229,6 +241,8 @@ SIGNATURES = {
                               c_int, c_vp]),
     "scflow_corr_lookup_backward": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int,
                                             c_int, c_int, c_vp]),
+    "scflow_corr_lookup_backward_masked": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_int,
+                                                   c_int, c_int, c_int, c_int, c_vp]),
     "scflow_gemm_f32_splits": (c_int, [c_int, c_int, c_int, c_int]),
     "scflow_gemm_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int] + [c_ll] * 9 +
                         [c_float, c_float, c_int, c_int, c_vp, c_vp]),

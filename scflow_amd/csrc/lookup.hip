@@ -36,6 +36,16 @@ __device__ __forceinline__ float unnorm_coord(float s, int size, int ac) {
   return ac ? ((g + 1.f) / 2.f) * (float)(size - 1) : ((g + 1.f) * (float)size - 1.f) / 2.f;
 }
 
+// floor of a sample coordinate as an int for the generic kernel's taps, clamped to [−2, 2³⁰]: a
+// coordinate at or beyond 2³¹ (a +inf or huge flow) converts to INT_MAX, and the `+ 1` of its
+// east / south tap then overflows — the compiler, entitled to assume it does not, let that tap
+// pass the bounds test and load far outside the map.  Every clamped value is off the map on the
+// same side, so every result that was defined is unchanged (NaN → −2: taps off the map, and the
+// NaN weights still make the sample NaN)
+__device__ __forceinline__ int tap_floor(float f) {
+  return (int)fminf(fmaxf(f, -2.f), 1073741824.f);
+}
+
 __device__ __forceinline__ float tap(const float* __restrict__ m, int x, int y, int Wl, int Hl) {
   return (x >= 0 && x < Wl && y >= 0 && y < Hl) ? m[y * Wl + x] : 0.f;
 }
@@ -44,7 +54,7 @@ template <int R>
 __global__ __launch_bounds__(256) void corr_lookup_kernel(
     const float* __restrict__ pyr, const float* __restrict__ flow, int flow_layout,
     float* __restrict__ out, int out_layout, int out_stride, int N, int H, int W, int L,
-    long long total, int ac) {
+    long long total, int ac, const float* __restrict__ mask) {
 #pragma clang fp contract(off)
   constexpr int r = R;
   constexpr int D = 2 * R + 1;
@@ -75,13 +85,16 @@ __global__ __launch_bounds__(256) void corr_lookup_kernel(
     Wl >>= 1;
   }
   const float* m = pyr + off + ((size_t)n * P + p) * Hl * Wl;
+  // masked lookup (scflow_corr_lookup_masked): the pixel's occlusion mask scales every sample
+  // where it is written; NULL: × 1, the unmasked bits
+  const float mk = mask ? mask[(size_t)n * P + p] : 1.f;
   const float scale = (float)(1 << lvl);
   const float cx = ((float)x + fx) / scale;
   const float cy = ((float)y + fy) / scale;
   const float ix = unnorm_coord(cx + (float)(a - r), Wl, ac);
   const float ix_w = floorf(ix);
   const float ix_e = ix_w + 1.f;
-  const int xw = (int)ix_w, xe = xw + 1;
+  const int xw = tap_floor(ix_w), xe = xw + 1;
   float* o = out_layout == SCFLOW_LAYOUT_NHWC
                  ? out + ((size_t)n * P + p) * out_stride + lvl * D * D + a * D
                  : out + ((size_t)n * L * D * D + lvl * D * D + a * D) * P + p;
@@ -91,7 +104,7 @@ __global__ __launch_bounds__(256) void corr_lookup_kernel(
     const float iy = unnorm_coord(cy + (float)(b - r), Hl, ac);
     const float iy_n = floorf(iy);
     const float iy_s = iy_n + 1.f;
-    const int yn = (int)iy_n, ys = yn + 1;
+    const int yn = tap_floor(iy_n), ys = yn + 1;
     const float nw = (ix_e - ix) * (iy_s - iy);
     const float ne = (ix - ix_w) * (iy_s - iy);
     const float sw = (ix_e - ix) * (iy - iy_n);
@@ -101,7 +114,7 @@ __global__ __launch_bounds__(256) void corr_lookup_kernel(
     v += tap(m, xe, yn, Wl, Hl) * ne;
     v += tap(m, xw, ys, Wl, Hl) * sw;
     v += tap(m, xe, ys, Wl, Hl) * se;
-    o[(size_t)b * ostep] = v;
+    o[(size_t)b * ostep] = v * mk;
   }
 }
 
@@ -222,7 +235,7 @@ template <int R, bool TILED, bool TR = false, bool TB = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TB ? 6 : 3))) void corr_lookup_lds_kernel(
     const float* __restrict__ pyr, const float* __restrict__ flow, int flow_layout,
     float* __restrict__ out, int out_layout, int out_stride, int N, int H, int W, int L,
-    int vec_out, int ac, unsigned long long* stamps) {
+    int vec_out, int ac, unsigned long long* stamps, const float* __restrict__ mask) {
 #pragma clang fp contract(off)
   constexpr int D = 2 * R + 1;
   constexpr int WIN = lk_win(R, TR, TB);  // LDS row length of a level's region
@@ -261,6 +274,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TB ? 6 : 3)
   const int p = active ? (int)(gp % P) : 0;
   const int y = p / W, x = p % W;
   float fx = 0.f, fy = 0.f;
+  // masked lookup: the pixel's mask scales its samples where they are produced (NULL: × 1)
+  const float mk = active && mask ? mask[gp] : 1.f;
   if (active) {
     if (flow_layout == SCFLOW_LAYOUT_NHWC) {
       fx = flow[((size_t)n * P + p) * 2 + 0];
@@ -554,7 +569,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TB ? 6 : 3)
         v += t01 * (wxe * wyn);
         v += t10 * (wxw * wys);
         v += t11 * (wxe * wys);
-        o[(size_t)(l * D * D + sidx) * ostep] = ok ? v : 0.f;
+        o[(size_t)(l * D * D + sidx) * ostep] = (ok ? v : 0.f) * mk;
       }
     }
     if (stamps) {
@@ -606,7 +621,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TB ? 6 : 3)
       v += t01[b] * (wxe * wyn);
       v += t10[b] * (wxw * wys);
       v += t11[b] * (wxe * wys);
-      res[q][b] = ok[b] ? v : 0.f;
+      res[q][b] = (ok[b] ? v : 0.f) * mk;
     }
   }
   if (vec_out) {
@@ -682,7 +697,8 @@ static bool lk_tile_rows() {
 
 static int corr_lookup_launch(const float* pyr, const float* flow, int flow_layout, float* out,
                               int out_layout, int out_stride, int n, int h, int w, int num_levels,
-                              int radius, int align_corners, bool tiled, void* stream) {
+                              int radius, int align_corners, bool tiled, const float* mask,
+                              void* stream) {
   const int ac = align_corners ? 1 : 0;
   if (!pyr || !flow || !out || n <= 0 || h <= 0 || w <= 0 || num_levels < 1 || num_levels > 8 ||
       radius < 0)
@@ -717,11 +733,11 @@ static int corr_lookup_launch(const float* pyr, const float* flow, int flow_layo
 #define SCFLOW_LKL(RR, TT)                                                                          \
   corr_lookup_lds_kernel<RR, TT><<<blk, 256, lds, st>>>(pyr, flow, flow_layout, out, out_layout,      \
                                                         out_stride, n, h, w, num_levels, vec, ac,  \
-                                                        g_lk_stamps)
+                                                        g_lk_stamps, mask)
     if (tiled && radius == 4 && lk_tile_regions(h, w)) {
       const size_t lds_tr = sizeof(float) * LK_SLOTS * lk_tr_slot_floats(num_levels);
       corr_lookup_lds_kernel<4, true, true><<<blk, 256, lds_tr, st>>>(
-          pyr, flow, flow_layout, out, out_layout, out_stride, n, h, w, num_levels, vec, ac, g_lk_stamps);
+          pyr, flow, flow_layout, out, out_layout, out_stride, n, h, w, num_levels, vec, ac, g_lk_stamps, mask);
       return scflow_launch_status();
     }
     if (tiled && lk_tile_rows()) {
@@ -731,10 +747,10 @@ static int corr_lookup_launch(const float* pyr, const float* flow, int flow_layo
                                  ((uintptr_t)out & 15) == 0 && sf_tb >= num_levels * D * D);
       const int vtb = vec_tb && sf_tb >= num_levels * D * D;
       switch (radius) {
-        case 1: corr_lookup_lds_kernel<1, true, false, true><<<blk, 256, lds_tb, st>>>(pyr, flow, flow_layout, out, out_layout, out_stride, n, h, w, num_levels, vtb, ac, g_lk_stamps); break;
-        case 2: corr_lookup_lds_kernel<2, true, false, true><<<blk, 256, lds_tb, st>>>(pyr, flow, flow_layout, out, out_layout, out_stride, n, h, w, num_levels, vtb, ac, g_lk_stamps); break;
-        case 3: corr_lookup_lds_kernel<3, true, false, true><<<blk, 256, lds_tb, st>>>(pyr, flow, flow_layout, out, out_layout, out_stride, n, h, w, num_levels, vtb, ac, g_lk_stamps); break;
-        default: corr_lookup_lds_kernel<4, true, false, true><<<blk, 256, lds_tb, st>>>(pyr, flow, flow_layout, out, out_layout, out_stride, n, h, w, num_levels, vtb, ac, g_lk_stamps); break;
+        case 1: corr_lookup_lds_kernel<1, true, false, true><<<blk, 256, lds_tb, st>>>(pyr, flow, flow_layout, out, out_layout, out_stride, n, h, w, num_levels, vtb, ac, g_lk_stamps, mask); break;
+        case 2: corr_lookup_lds_kernel<2, true, false, true><<<blk, 256, lds_tb, st>>>(pyr, flow, flow_layout, out, out_layout, out_stride, n, h, w, num_levels, vtb, ac, g_lk_stamps, mask); break;
+        case 3: corr_lookup_lds_kernel<3, true, false, true><<<blk, 256, lds_tb, st>>>(pyr, flow, flow_layout, out, out_layout, out_stride, n, h, w, num_levels, vtb, ac, g_lk_stamps, mask); break;
+        default: corr_lookup_lds_kernel<4, true, false, true><<<blk, 256, lds_tb, st>>>(pyr, flow, flow_layout, out, out_layout, out_stride, n, h, w, num_levels, vtb, ac, g_lk_stamps, mask); break;
       }
       return scflow_launch_status();
     }
@@ -756,7 +772,8 @@ static int corr_lookup_launch(const float* pyr, const float* flow, int flow_layo
 #define SCFLOW_LK(RR)                                                                            \
   case RR:                                                                                       \
     corr_lookup_kernel<RR><<<blocks, 256, 0, st>>>(pyr, flow, flow_layout, out, out_layout,      \
-                                                   out_stride, n, h, w, num_levels, total, ac); \
+                                                   out_stride, n, h, w, num_levels, total, ac, \
+                                                   mask);                                      \
     break;
   switch (radius) {
     SCFLOW_LK(0) SCFLOW_LK(1) SCFLOW_LK(2) SCFLOW_LK(3) SCFLOW_LK(4) SCFLOW_LK(5) SCFLOW_LK(6)
@@ -770,7 +787,7 @@ SCFLOW_API int scflow_corr_lookup_ex(const float* pyr, const float* flow, int fl
                                      int out_layout, int out_stride, int n, int h, int w,
                                      int num_levels, int radius, int align_corners, void* stream) {
   return corr_lookup_launch(pyr, flow, flow_layout, out, out_layout, out_stride, n, h, w, num_levels,
-                            radius, align_corners, false, stream);
+                            radius, align_corners, false, nullptr, stream);
 }
 
 SCFLOW_API int scflow_corr_lookup_tiled(const float* pyr, const float* flow, int flow_layout,
@@ -778,7 +795,18 @@ SCFLOW_API int scflow_corr_lookup_tiled(const float* pyr, const float* flow, int
                                         int w, int num_levels, int radius, int align_corners,
                                         void* stream) {
   return corr_lookup_launch(pyr, flow, flow_layout, out, out_layout, out_stride, n, h, w, num_levels,
-                            radius, align_corners, true, stream);
+                            radius, align_corners, true, nullptr, stream);
+}
+
+// out[m][k] = mask[m] · lookup[m][k] (mask: [n·h·w], NULL: the unmasked call); `tiled`: the
+// pyramid of scflow_corr_pyramid_tiled.  Every kernel the two entries above dispatch to, the
+// multiply at the sample's store: no extra pass, no extra launch.
+SCFLOW_API int scflow_corr_lookup_masked(const float* pyr, const float* flow, int flow_layout,
+                                         const float* mask, float* out, int out_layout,
+                                         int out_stride, int n, int h, int w, int num_levels,
+                                         int radius, int align_corners, int tiled, void* stream) {
+  return corr_lookup_launch(pyr, flow, flow_layout, out, out_layout, out_stride, n, h, w, num_levels,
+                            radius, align_corners, tiled != 0, mask, stream);
 }
 
 SCFLOW_API int scflow_corr_lookup(const float* pyr, const float* flow, int flow_layout, float* out,

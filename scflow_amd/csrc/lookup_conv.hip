@@ -63,6 +63,7 @@ struct LcArgs {
   const float* flow;    // [n·h·w][2] (NHWC)
   const float* weight;  // 1×1 packing (SCFLOW_CONV_1X1W) of the [cout][324] conv weight
   const float* bias;    // [cout] or NULL
+  const float* mask;    // [n·h·w] or NULL: scales a pixel's samples (scflow_corr_lookup_conv1x1_masked)
   float* out;           // [n·h·w][so]
   int so, n, h, w, cout, act, ac;
 };
@@ -101,9 +102,13 @@ __global__ __launch_bounds__(512, 1) void corr_lookup_conv1x1_kernel(LcArgs a) {
   const int p = active ? (int)(gp % P) : 0;
   const int y = p / W, x = p % W;
   float fx = 0.f, fy = 0.f;
+  // the masked lookup's multiply, on the sample as it enters the A row (conv(corr · mask), the
+  // reference's order — not on the accumulator); NULL: × 1, the unmasked bits
+  float mk = 1.f;
   if (active) {
     fx = a.flow[gp * 2];
     fy = a.flow[gp * 2 + 1];
+    if (a.mask) mk = a.mask[gp];
   }
   const long long left = M - m0;
   const int npx = left < LC_PX ? (int)left : LC_PX;
@@ -210,7 +215,7 @@ __global__ __launch_bounds__(512, 1) void corr_lookup_conv1x1_kernel(LcArgs a) {
           v += t01[b] * (wxe * wyn);
           v += t10[b] * (wxw * wys);
           v += t11[b] * (wxe * wys);
-          arow[aa * LC_D + b] = ok[b] ? v : 0.f;
+          arow[aa * LC_D + b] = (ok[b] ? v : 0.f) * mk;
         }
       }
     }
@@ -336,10 +341,10 @@ SCFLOW_API long long scflow_corr_lookup_conv1x1_lds_bytes(void) {
   return (long long)sizeof(float) * LC_PX * (LC_KP + LC_WP);
 }
 
-SCFLOW_API int scflow_corr_lookup_conv1x1(const float* pyr, const float* flow, const float* weight,
-                                          const float* bias, float* out, int out_stride, int n,
-                                          int h, int w, int num_levels, int radius, int cout,
-                                          int act, int align_corners, void* stream) {
+static int lookup_conv1x1_launch(const float* pyr, const float* flow, const float* mask,
+                                 const float* weight, const float* bias, float* out, int out_stride,
+                                 int n, int h, int w, int num_levels, int radius, int cout, int act,
+                                 int align_corners, void* stream) {
   if (!pyr || !flow || !weight || !out || n <= 0 || h <= 0 || w <= 0 || cout <= 0 ||
       out_stride < cout)
     return SCFLOW_EINVAL;
@@ -354,6 +359,7 @@ SCFLOW_API int scflow_corr_lookup_conv1x1(const float* pyr, const float* flow, c
   a.flow = flow;
   a.weight = weight;
   a.bias = bias;
+  a.mask = mask;
   a.out = out;
   a.so = out_stride;
   a.n = n;
@@ -372,4 +378,23 @@ SCFLOW_API int scflow_corr_lookup_conv1x1(const float* pyr, const float* flow, c
   const long long M = (long long)n * h * w;
   corr_lookup_conv1x1_kernel<<<(unsigned)((M + LC_PX - 1) / LC_PX), 512, lds, (hipStream_t)stream>>>(a);
   return scflow_launch_status();
+}
+
+SCFLOW_API int scflow_corr_lookup_conv1x1(const float* pyr, const float* flow, const float* weight,
+                                          const float* bias, float* out, int out_stride, int n,
+                                          int h, int w, int num_levels, int radius, int cout,
+                                          int act, int align_corners, void* stream) {
+  return lookup_conv1x1_launch(pyr, flow, nullptr, weight, bias, out, out_stride, n, h, w,
+                               num_levels, radius, cout, act, align_corners, stream);
+}
+
+// conv(mask · lookup): bit-identical to scflow_corr_lookup_masked (tiled) + the wide 1×1 conv
+SCFLOW_API int scflow_corr_lookup_conv1x1_masked(const float* pyr, const float* flow,
+                                                 const float* mask, const float* weight,
+                                                 const float* bias, float* out, int out_stride,
+                                                 int n, int h, int w, int num_levels, int radius,
+                                                 int cout, int act, int align_corners,
+                                                 void* stream) {
+  return lookup_conv1x1_launch(pyr, flow, mask, weight, bias, out, out_stride, n, h, w, num_levels,
+                               radius, cout, act, align_corners, stream);
 }

@@ -87,7 +87,9 @@ __global__ __launch_bounds__(256) void pose_flow_kernel(
 
 __global__ __launch_bounds__(256) void downsample_kernel(const float* __restrict__ flow,
                                                          float* __restrict__ o0, int s0,
-                                                         float* __restrict__ o1, int s1, int N,
+                                                         float* __restrict__ o1, int s1,
+                                                         const float* __restrict__ mask,
+                                                         float* __restrict__ om, int sm, int N,
                                                          int H, int W, int h, int w, float vs) {
 #pragma clang fp contract(off)
   const long long total = (long long)N * h * w;
@@ -107,9 +109,15 @@ __global__ __launch_bounds__(256) void downsample_kernel(const float* __restrict
   }
   o0[idx * s0 + 0] = r[0];
   o0[idx * s0 + 1] = r[1];
+  // masked (scflow_flow_downsample_masked): o0 unmasked, o1 and om times the pixel's mask
+  const float mk = mask ? mask[idx] : 1.f;
   if (o1) {
-    o1[idx * s1 + 0] = r[0];
-    o1[idx * s1 + 1] = r[1];
+    o1[idx * s1 + 0] = r[0] * mk;
+    o1[idx * s1 + 1] = r[1] * mk;
+  }
+  if (om) {
+    om[idx * sm + 0] = r[0] * mk;
+    om[idx * sm + 1] = r[1] * mk;
   }
 }
 
@@ -230,7 +238,22 @@ SCFLOW_API int scflow_flow_downsample(const float* flow, float* out0, int s0, fl
     return SCFLOW_EINVAL;
   const long long total = (long long)n * h * w;
   downsample_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-      flow, out0, s0, out1, s1, n, H, W, h, w, value_scale);
+      flow, out0, s0, out1, s1, nullptr, nullptr, 0, n, H, W, h, w, value_scale);
+  return scflow_launch_status();
+}
+
+// the unfused tail's ↓8 flow under mask_flow: out0 ← the unmasked flow (the lookup's), out1 and
+// outm ← flow · mask (mask: [n·h·w]); mask NULL: scflow_flow_downsample (+ a copy in outm)
+SCFLOW_API int scflow_flow_downsample_masked(const float* flow, float* out0, int s0, float* out1,
+                                             int s1, const float* mask, float* outm, int sm, int n,
+                                             int H, int W, int h, int w, float value_scale,
+                                             void* stream) {
+  if (!flow || !out0 || s0 < 2 || (out1 && s1 < 2) || (outm && sm < 2) || n <= 0 || H <= 0 ||
+      W <= 0 || h <= 0 || w <= 0)
+    return SCFLOW_EINVAL;
+  const long long total = (long long)n * h * w;
+  downsample_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+      flow, out0, s0, out1, s1, mask, outm, sm, n, H, W, h, w, value_scale);
   return scflow_launch_status();
 }
 
@@ -313,6 +336,48 @@ SCFLOW_API int scflow_pose_step_heads(const float* x, int xsplit, const float* x
   a.hx = x; a.hxs = (long long)n * k; a.hk = k; a.hsplit = xsplit; a.hxb = xbias;
   a.Wr = Wr; a.br = br; a.Wt = Wt; a.bt = bt; a.hlabel = label; a.hrch = rch; a.hncls = num_class;
   a.drot_out = drot; a.dt_out = dt;
+  pose_step_kernel<<<dim3(a.bf + a.bl, n), 256, 0, (hipStream_t)stream>>>(a);
+  return scflow_launch_status();
+}
+
+// The superset of the three entries above with the masked tail: x NULL → scflow_pose_step_part
+// (drot / dt read), else scflow_pose_step_heads (drot / dt written).  mask_next ([n·h·w], the mask
+// this iteration just predicted) non-NULL: lr_next still receives the unmasked ↓8 flow; lrm_next
+// (stride s_lrm, may be NULL) and hx_next receive lr_next · mask_next.  mask_next NULL: lrm_next,
+// when given, is a copy of lr_next and everything else is the unmasked entry's, bit for bit.
+SCFLOW_API int scflow_pose_step_masked(const float* x, int xsplit, const float* xbias, int k,
+                                       const float* Wr, const float* br, int rch, const float* Wt,
+                                       const float* bt, const long long* label, int num_class,
+                                       float* drot, float* dt, const float* R_src,
+                                       const float* t_src, const float* K, const float* points,
+                                       float* R_dst, float* t_dst, float* flow, int n, int H, int W,
+                                       float weight, int depth_transform, float invalid_num,
+                                       const float* lr, const float* delta, const float* mask,
+                                       float* flow_up, float* mask_up, float* lr_next, int s_next,
+                                       float* hx_next, int s_hx, const float* mask_next,
+                                       float* lrm_next, int s_lrm, int h, int w, float up_scale,
+                                       float down_scale, int parts, void* stream) {
+  if (parts < 1 || parts > 3 || !drot) return SCFLOW_EINVAL;
+  if (x && (xsplit < 1 || !xbias || k <= 0 || !Wr || !br || !Wt || !bt || !label ||
+            num_class <= 0 || !dt || rch != pose_rot_dim(depth_transform)))
+    return SCFLOW_EINVAL;
+  if ((mask_next || lrm_next) && !lr_next) return SCFLOW_EINVAL;
+  if (lrm_next && (s_lrm < 2 || lrm_next == lr || lrm_next == lr_next)) return SCFLOW_EINVAL;
+  PoseStepArgs a;
+  const int st = pose_step_args(&a, drot, dt, R_src, t_src, K, points, R_dst, t_dst, flow, n, H, W,
+                                weight, depth_transform, invalid_num, lr, delta, mask, flow_up,
+                                mask_up, lr_next, s_next, hx_next, s_hx, h, w, up_scale, down_scale,
+                                256);
+  if (st != SCFLOW_OK) return st;
+  if (!(parts & 1)) a.bf = 0;
+  if (!(parts & 2)) a.bl = 0;
+  if (a.bf + a.bl == 0) return SCFLOW_EINVAL;  // parts = 2 needs lr_next
+  a.mnext = mask_next; a.o2 = lrm_next; a.s2 = s_lrm;
+  if (x) {
+    a.hx = x; a.hxs = (long long)n * k; a.hk = k; a.hsplit = xsplit; a.hxb = xbias;
+    a.Wr = Wr; a.br = br; a.Wt = Wt; a.bt = bt; a.hlabel = label; a.hrch = rch; a.hncls = num_class;
+    a.drot_out = drot; a.dt_out = dt;
+  }
   pose_step_kernel<<<dim3(a.bf + a.bl, n), 256, 0, (hipStream_t)stream>>>(a);
   return scflow_launch_status();
 }

@@ -177,6 +177,10 @@ struct PoseStepArgs {
   const float* lr; const float* delta; const float* mask; float* fo; float* mo;
   float* o0; int s0; float* o1; int s1; int h, w; float up_scale, down_scale;
   int bf, bl;
+  // masked tail (scflow_pose_step_masked; mnext NULL: off): the mask just predicted, [n·h·w].
+  // o0 keeps the unmasked ↓8 flow (the lookup's); o2 (lrm_next, stride s2) and o1 (hx_next)
+  // receive it times the mask (the flow branch's input, the motion features' flow channels)
+  const float* mnext; float* o2; int s2;
   int given;  // 1: Rsrc / tsrc are the updated pose already (no update, Rout / tout unused)
   // heads fused (hx != NULL; scflow_pose_step_heads): the pose delta of image n is computed in
   // the launch from the last FC's K-split partial sums — x = relu(Σ_z hx[z·hxs] + hxb), the
@@ -354,7 +358,9 @@ __device__ __forceinline__ void pose_step_body(const PoseStepArgs& a, float* sh,
     for (int c = 0; c < 2; ++c) {
       const float v = a.down_scale * bilerp(f[0][c], f[1][c], f[2][c], f[3][c], ly, lx);
       a.o0[idx * a.s0 + c] = v;
-      if (a.o1) a.o1[idx * a.s1 + c] = v;
+      const float vm = a.mnext ? v * a.mnext[idx] : v;
+      if (a.o1) a.o1[idx * a.s1 + c] = vm;
+      if (a.o2) a.o2[idx * a.s2 + c] = vm;
     }
   }
 }
@@ -396,6 +402,7 @@ static inline int pose_step_args(PoseStepArgs* a, const float* drot6, const floa
   a->w = w; a->up_scale = up_scale; a->down_scale = down_scale;
   a->given = given ? 1 : 0;
   a->hx = nullptr;
+  a->mnext = nullptr; a->o2 = nullptr; a->s2 = 0;
   const int bf = ceil_div((long long)H * W, nt);
   // from a given pose the part runs beside other work (the decoder's side stream): 4 pixels per
   // thread, a quarter of the workgroups to schedule

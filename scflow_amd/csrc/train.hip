@@ -119,7 +119,8 @@ __device__ __forceinline__ void tap_add(float* m, int x, int y, int Wl, int Hl, 
 template <int R>
 __global__ __launch_bounds__(256) void corr_lookup_bwd_kernel(
     const float* __restrict__ dout, int out_layout, int out_stride, const float* __restrict__ flow,
-    int flow_layout, float* __restrict__ dpyr, int N, int H, int W, int L, long long total) {
+    int flow_layout, float* __restrict__ dpyr, int N, int H, int W, int L, long long total,
+    const float* __restrict__ mask) {
 #pragma clang fp contract(off)
   constexpr int r = R;
   constexpr int D = 2 * R + 1;
@@ -149,6 +150,8 @@ __global__ __launch_bounds__(256) void corr_lookup_bwd_kernel(
     Wl >>= 1;
   }
   float* m = dpyr + off + ((size_t)n * P + p) * Hl * Wl;
+  // masked lookup's adjoint: the pixel's mask scales its output gradients (NULL: × 1)
+  const float mk = mask ? mask[(size_t)n * P + p] : 1.f;
   const float scale = (float)(1 << lvl);
   const float cx = ((float)x + fx) / scale;
   const float cy = ((float)y + fy) / scale;
@@ -161,7 +164,7 @@ __global__ __launch_bounds__(256) void corr_lookup_bwd_kernel(
                        : dout + ((size_t)n * L * D * D + lvl * D * D + a * D) * P + p;
   const int gstep = out_layout == SCFLOW_LAYOUT_NHWC ? 1 : P;
   for (int b = 0; b < D; ++b) {
-    const float gv = g[(size_t)b * gstep];
+    const float gv = g[(size_t)b * gstep] * mk;
     if (gv == 0.f) continue;
     const float iy = unnorm_coord_b(cy + (float)(b - r), Hl);
     const float iy_n = floorf(iy);
@@ -182,7 +185,8 @@ __global__ __launch_bounds__(256) void corr_lookup_bwd_kernel(
 template <int R>
 __global__ __launch_bounds__(256) void corr_lookup_bwd_win_kernel(
     const float* __restrict__ dout, int out_layout, int out_stride, const float* __restrict__ flow,
-    int flow_layout, float* __restrict__ dpyr, int N, int H, int W, int L, long long total) {
+    int flow_layout, float* __restrict__ dpyr, int N, int H, int W, int L, long long total,
+    const float* __restrict__ mask) {
 #pragma clang fp contract(off)
   constexpr int r = R;
   constexpr int D = 2 * R + 1;
@@ -216,6 +220,8 @@ __global__ __launch_bounds__(256) void corr_lookup_bwd_win_kernel(
     Wl >>= 1;
   }
   float* m = dpyr + off + ((size_t)n * P + p) * Hl * Wl;
+  // masked lookup's adjoint: the pixel's mask scales its output gradients (NULL: × 1)
+  const float mk = mask ? mask[(size_t)n * P + p] : 1.f;
   const float scale = (float)(1 << lvl);
   const float cx = ((float)x + fx) / scale;
   const float cy = ((float)y + fy) / scale;
@@ -246,7 +252,7 @@ __global__ __launch_bounds__(256) void corr_lookup_bwd_win_kernel(
     for (int a = 0; a < D; ++a) {
       const int xw = x0 + a + ox[a];
       for (int b = 0; b < D; ++b) {
-        const float gv = g[(size_t)(a * D + b) * gstep];
+        const float gv = g[(size_t)(a * D + b) * gstep] * mk;
         const int yn = y0 + b + oy[b];
         tap_add(m, xw, yn, Wl, Hl, gv * (wxw[a] * wyn[b]));
         tap_add(m, xw + 1, yn, Wl, Hl, gv * (wxe[a] * wyn[b]));
@@ -287,7 +293,7 @@ __global__ __launch_bounds__(256) void corr_lookup_bwd_win_kernel(
     for (int i = 0; i < WN; ++i) v[i] = 0.f;
 #pragma unroll
     for (int a = 0; a < D; ++a) {
-      const float gv = g[(size_t)(a * D + b) * gstep];
+      const float gv = g[(size_t)(a * D + b) * gstep] * mk;
       v[a] += gv * ux0[a];
       v[a + 1] += gv * ux1[a];
       v[a + 2] += gv * ux2[a];
@@ -2032,9 +2038,10 @@ SCFLOW_API int scflow_col2im(const float* cols, float* dx, int sdx, int n, int h
   return scflow_launch_status();
 }
 
-SCFLOW_API int scflow_corr_lookup_backward(const float* dout, int out_layout, int out_stride,
-                                           const float* flow, int flow_layout, float* dpyr, int n,
-                                           int h, int w, int num_levels, int radius, void* stream) {
+static int corr_lookup_backward_launch(const float* dout, int out_layout, int out_stride,
+                                       const float* flow, int flow_layout, const float* mask,
+                                       float* dpyr, int n, int h, int w, int num_levels, int radius,
+                                       void* stream) {
   if (!dout || !flow || !dpyr || n <= 0 || h <= 0 || w <= 0 || num_levels < 1 || num_levels > 8 ||
       radius < 0)
     return SCFLOW_EINVAL;
@@ -2055,7 +2062,8 @@ SCFLOW_API int scflow_corr_lookup_backward(const float* dout, int out_layout, in
 #define SCFLOW_LKW(RR)                                                                             \
   case RR:                                                                                         \
     corr_lookup_bwd_win_kernel<RR><<<bw, 256, 0, st>>>(dout, out_layout, out_stride, flow,         \
-                                                       flow_layout, dpyr, n, h, w, num_levels, tw); \
+                                                       flow_layout, dpyr, n, h, w, num_levels, tw, \
+                                                       mask);                                      \
     break;
       SCFLOW_LKW(1)
       SCFLOW_LKW(2)
@@ -2072,7 +2080,7 @@ SCFLOW_API int scflow_corr_lookup_backward(const float* dout, int out_layout, in
   case RR:                                                                                        \
     corr_lookup_bwd_kernel<RR><<<blocks, 256, 0, st>>>(dout, out_layout, out_stride, flow,        \
                                                        flow_layout, dpyr, n, h, w, num_levels,    \
-                                                       total);                                    \
+                                                       total, mask);                              \
     break;
     SCFLOW_LKB(1)
     SCFLOW_LKB(2)
@@ -2085,6 +2093,23 @@ SCFLOW_API int scflow_corr_lookup_backward(const float* dout, int out_layout, in
       return SCFLOW_EUNSUPPORTED;
   }
   return scflow_launch_status();
+}
+
+SCFLOW_API int scflow_corr_lookup_backward(const float* dout, int out_layout, int out_stride,
+                                           const float* flow, int flow_layout, float* dpyr, int n,
+                                           int h, int w, int num_levels, int radius, void* stream) {
+  return corr_lookup_backward_launch(dout, out_layout, out_stride, flow, flow_layout, nullptr, dpyr,
+                                     n, h, w, num_levels, radius, stream);
+}
+
+// the adjoint of scflow_corr_lookup_masked with respect to the pyramid: scatters
+// mask[m] · dout[m][k] (no gradient for the mask or the flow); mask NULL: the call above
+SCFLOW_API int scflow_corr_lookup_backward_masked(const float* dout, int out_layout, int out_stride,
+                                                  const float* flow, int flow_layout,
+                                                  const float* mask, float* dpyr, int n, int h,
+                                                  int w, int num_levels, int radius, void* stream) {
+  return corr_lookup_backward_launch(dout, out_layout, out_stride, flow, flow_layout, mask, dpyr, n,
+                                     h, w, num_levels, radius, stream);
 }
 
 SCFLOW_API int scflow_colsum(const float* x, int rows, int cols, int ld, float* out, int accumulate,

@@ -119,7 +119,7 @@ class SCFlowDecoder(nn.Module):
         # fork / join with device-scope events (no system-scope cache writeback per record)
         self.device_scope_events = True
         # the iteration's tail (pose update, pose flow, ×8 prediction, next ↓8 flow) as one
-        # launch (scflow_pose_step); only without flow/correlation masking
+        # launch (scflow_pose_step; under mask_flow scflow_pose_step_masked)
         self.fuse_tail = True
         # the lookup and corr_net.0 (1×1 324→256) as ONE launch (scflow_corr_lookup_conv1x1: the
         # correlation features stay in LDS) when the geometry allows (tiled pyramid, L = 4, r = 4)
@@ -195,6 +195,14 @@ class SCFlowDecoder(nn.Module):
         fb = None if fp.bias is None else fp.bias.detach()
         mb = None if mp.bias is None else mp.bias.detach()
         return hargs, self._xpred_w, ws, fb, mb, fh
+
+    @property
+    def last_plan(self) -> Optional[dict]:
+        """The schedule the last forward took (read-only copy; None before the first): the
+        booleans ``fuse_tail``, ``defer``, ``pair_tail``, ``fuse_lc`` (fused lookup + 1×1),
+        ``tiled`` (tiled pyramid) and ``side_stream``.  The mask flags do not change it."""
+        plan = getattr(self, "_last_plan", None)
+        return None if plan is None else dict(plan)
 
     @property
     def hx_channels(self) -> int:
@@ -462,9 +470,7 @@ class SCFlowDecoder(nn.Module):
         flow_pred_r = ConvRunner.of(self.flow_pred.predict_layer, None)
         mask_pred_r = ConvRunner.of(self.mask_pred.predict_layer, "Sigmoid")
         label = (label if head_label is None else head_label).to(dev).long()
-        mask_lr = None
-        if self.mask_corr or self.mask_flow:
-            mask_lr = torch.ones(M, 1, device=dev, dtype=f32)  # interpolate(ones, 1/8) == ones
+        masked = bool(self.mask_corr or self.mask_flow)
         flow_full = init_flow.contiguous().float()
         hx_flow = Chan(HX, hx_c - 2, 2)
         hx_motion = Chan(HX, hc + xc, co)
@@ -530,13 +536,25 @@ class SCFlowDecoder(nn.Module):
             o_drot = torch.empty(iters, N, self.pose_pred.rotation_out_channels, device=dev,
                                  dtype=f32)
             o_dt = torch.empty(iters, N, 3, device=dev, dtype=f32)
-        # Fused iteration tail (no masking): one launch does the pose update, the pose flow, this
+        # Fused iteration tail: one launch does the pose update, the pose flow, this
         # iteration's ×8 prediction (from F2) and the next iteration's ↓8 flow (into the other
         # F2 buffer, computed from the new pose).  F2 alternates between two buffers, so the
         # recorded launches that read it (lookup, flow branch) are recorded once per parity.
-        fuse_tail = self.fuse_tail and not (self.mask_flow or self.mask_corr)
+        # Occlusion masking (mask_corr / mask_flow, scflow_decoder.py:189-207) runs the same plan:
+        # the mask the previous iteration predicted (mask_prev: all ones before the first) scales
+        # the correlation samples inside the lookup kernels (mask_corr) and the ↓8 flow inside the
+        # launch that produces it (mask_flow: the tail, or the downsample) — F2 stays the unmasked
+        # flow (the lookup's centroids), FLM = F2 · mask feeds the flow branch and the motion
+        # features' flow channels, double-buffered per parity like F2.
+        fuse_tail = self.fuse_tail
         F2s = [F2, torch.empty_like(F2)] if fuse_tail else [F2, F2]
-        flow_in = F2 * mask_lr if self.mask_flow else F2
+        if self.mask_flow:
+            FLMs = [torch.empty_like(F2), torch.empty_like(F2)] if fuse_tail else \
+                [torch.empty_like(F2)] * 2
+        else:
+            FLMs = F2s
+        flow_in = FLMs[0]
+        mask_prev = None  # the mask buffer this iteration's masked launches read
 
         def seg_flow_branch():
             run_chain(self.encoder.flow_net, Chan.whole(flow_in), Chan(MF, cc, cf), N, h, w, s_flow,
@@ -545,12 +563,12 @@ class SCFlowDecoder(nn.Module):
         def seg_lookup():
             ops.corr_lookup(pyr, F2, N, h, w, self.num_levels, self.radius, out=Chan.whole(CORR),
                             flow_layout="nhwc", align_corners=self.corr_lookup.align_corners,
-                            tiled=tiled)
+                            tiled=tiled, mask=mask_prev if self.mask_corr else None)
 
         corr_net = self.encoder.corr_net
         c0m = corr_net[0].conv
         fuse_lc = (self.fuse_lookup_conv and h * w <= self.fuse_lookup_conv_max_px and tiled and
-                   not self.mask_corr and len(corr_net) == 2 and
+                   len(corr_net) == 2 and
                    tuple(c0m.kernel_size) == (1, 1) and tuple(c0m.stride) == (1, 1) and
                    tuple(c0m.padding) == (0, 0) and
                    ops.lookup_conv1x1_ok(h, w, self.num_levels, self.radius, c0m.in_channels,
@@ -561,7 +579,8 @@ class SCFlowDecoder(nn.Module):
             packed, bias = r0.packed(c0m.in_channels, 0, w, _lib.CONV_1X1W)
             ops.corr_lookup_conv1x1(pyr, F2, packed, bias, Chan.whole(s_corr[-1]), N, h, w,
                                     self.num_levels, self.radius, c0m.out_channels,
-                                    corr_net[0].act_type, self.corr_lookup.align_corners)
+                                    corr_net[0].act_type, self.corr_lookup.align_corners,
+                                    mask=mask_prev if self.mask_corr else None)
 
         def seg_corr_hidden():  # corr_net.0 (1×1 324→256)
             if len(corr_net) > 1:
@@ -626,8 +645,23 @@ class SCFlowDecoder(nn.Module):
         # the tail is paired)
         MASKs = [MASK, torch.empty_like(MASK)] if defer else [MASK, MASK]
         pt = self.pair_tail if self.pair_tail >= 0 else int(h * w <= 32 * 32)
-        pair_tail = (bool(pt) and len(self.delta_flow_encoder) == len(self.mask_encoder) and
-                     not (self.mask_flow or self.mask_corr))
+        pair_tail = bool(pt) and len(self.delta_flow_encoder) == len(self.mask_encoder)
+        self._last_plan = dict(fuse_tail=bool(fuse_tail), defer=bool(defer),
+                               pair_tail=bool(pair_tail), fuse_lc=bool(fuse_lc), tiled=bool(tiled),
+                               side_stream=bool(two))
+        if masked:
+            MASKs[1].fill_(1.0)  # before the first prediction: interpolate(ones, 1/8) == ones
+        # Masked plan, paired tail + deferred outputs: nothing on the main stream orders the tail
+        # of iteration i (which writes F2s[(i+1)%2]) after the side stream's deferred launch of
+        # iteration i−1 (which reads that buffer as its ↓8 flow) — no join sits between them when
+        # the tail is paired.  The masked plan orders the two with an event of its own.
+        ev_full = None
+        if masked and defer and pair_tail and two:
+            if self.device_scope_events:
+                ev_full = self._sync_events(dev, (slot, "full"))[0]
+                h_main, h_side = main.cuda_stream, side.cuda_stream
+            else:
+                ev_full = torch.cuda.Event()
         cur_par = [0]
         pending = []  # the previous iteration's deferred full-resolution launches
         if defer:  # the deferred launches' pose outputs (duplicates of o_R / o_t: not read)
@@ -640,16 +674,17 @@ class SCFlowDecoder(nn.Module):
         for it in range(iters):
             par = f"{it % 2}" if fuse_tail else ""
             F2 = F2s[it % 2]
-            if not self.mask_flow:
-                flow_in = F2
-            # a11 ↓: flow at feature resolution → F2 (and the motion-feature flow channels); the
-            # fused tail of the previous iteration already wrote it
+            flow_in = FLMs[it % 2]
+            if masked:  # the mask iteration it−1 predicted (ones before the first)
+                mask_prev = MASKs[(it - 1) % 2]
+            # a11 ↓: flow at feature resolution → F2 (and the motion-feature flow channels, times
+            # the mask under mask_flow); the fused tail of the previous iteration already wrote it
             if not fuse_tail or it == 0:
-                ops.flow_downsample(flow_full, Chan.whole(F2), h, w, 1.0 / scale,
-                                    out1=None if self.mask_flow else hx_flow)
-            if self.mask_flow:
-                torch.mul(F2, mask_lr, out=flow_in)
-                HX[:, hx_c - 2:].copy_(flow_in)
+                if self.mask_flow:
+                    ops.flow_downsample(flow_full, Chan.whole(F2), h, w, 1.0 / scale, out1=hx_flow,
+                                        mask=mask_prev, outm=Chan.whole(flow_in))
+                else:
+                    ops.flow_downsample(flow_full, Chan.whole(F2), h, w, 1.0 / scale, out1=hx_flow)
             if pp is not None:
                 pp[0](it)
             # a3 (flow branch) on the side stream
@@ -665,8 +700,6 @@ class SCFlowDecoder(nn.Module):
                 self._hook("corr_lookup", True)
                 segment("lookup" + par, seg_lookup)
                 self._hook("corr_lookup", False)
-                if self.mask_corr:
-                    CORR.mul_(mask_lr)
                 segment("corr_hidden", seg_corr_hidden)
             self._hook("corr_net1", True)
             segment("corr_last", seg_corr_last)
@@ -682,6 +715,11 @@ class SCFlowDecoder(nn.Module):
                     for c in pending:
                         c()
                     self._hook("pose_flow", False)
+                    if ev_full is not None:
+                        if self.device_scope_events:
+                            ev_full.record(h_side)
+                        else:
+                            ev_full.record(side)
                 pending = []
             segment("out", seg_out)
             # a4 GRU (in place on HX[:, :hc])
@@ -708,8 +746,6 @@ class SCFlowDecoder(nn.Module):
                 # flow predictor + Δflow encoder (into this iteration's Δflow buffer)
                 segment("flow_pred" + (par if defer else ""), seg_flow_pred)
                 join()
-            if mask_lr is not None:
-                mask_lr = MASKs[cur_par[0]]
             # a7 pose head on cat[h, Δflow feat, mask feat] (two channel sources, no concat)
             segment("pose_trunk", seg_pose_trunk)
             drot, dtr = o_drot[it], o_dt[it]
@@ -730,6 +766,9 @@ class SCFlowDecoder(nn.Module):
                         nxt = dict(lr_next=None if last else Chan.whole(F2s[(j + 1) % 2]),
                                    hx_next=None if last else hx_flow,
                                    depth_transform=self.depth_transform)
+                        if self.mask_flow and not last:  # the next iteration's masked ↓8 flow
+                            nxt.update(mask_next=MASKs[j % 2],
+                                       lrm_next=Chan.whole(FLMs[(j + 1) % 2]))
                         # the rotation / translation heads inside the pose step's launch
                         # (scflow_pose_step_heads), or as their own launch before it
                         ha = self.pose_pred.heads_args(pose_x[0], label) if self.fuse_heads else None
@@ -746,8 +785,9 @@ class SCFlowDecoder(nn.Module):
                                     ops.pose_step_given(o_R[j], o_t[j], *step[4:6], *step[8:])
                                 else:  # (reads the deltas the ↓8 launch wrote)
                                     fstep = step[:6] + (R_scr, t_scr) + step[8:]
-                                    ops.pose_step(*fstep, **{k: v for k, v in nxt.items() if k != "heads"},
-                                                  parts=1)
+                                    ops.pose_step(*fstep, parts=1,
+                                                  **{k: v for k, v in nxt.items()
+                                                     if k not in ("heads", "mask_next", "lrm_next")})
                         else:
                             with ops.binding(pc, run=False):
                                 ops.pose_step(*step, **nxt)
@@ -756,6 +796,11 @@ class SCFlowDecoder(nn.Module):
                 hc, pc, fc = tail_calls[it]
                 for c in hc:
                     c()
+                if ev_full is not None and it > 0:  # after iteration it−1's deferred launch
+                    if self.device_scope_events:
+                        ev_full.wait(h_main)
+                    else:
+                        main.wait_event(ev_full)
                 # deferred: this is the critical-path ↓8 launch (its own timer); otherwise the
                 # whole pose step
                 hook = "pose_step_crit" if fc else "pose_flow"

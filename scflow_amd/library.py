@@ -159,6 +159,67 @@ def _corr_lookup_backward(ctx, dout):
 corr_lookup.register_autograd(_corr_lookup_backward, setup_context=_corr_lookup_setup)
 
 
+# ------------------------------------------------------------------------------------ a2, masked
+@torch.library.custom_op("scflow::corr_lookup_masked", mutates_args=(), device_types="cuda")
+def corr_lookup_masked(pyramid: Tensor, flow: Tensor, mask: Tensor, num_levels: int, radius: int,
+                       align_corners: bool) -> Tensor:
+    """``corr_lookup`` times the occlusion mask [B, 1, H, W] (the reference's ``mask_corr``,
+    scflow_decoder.py:189-207), multiplied where each sample is stored
+    (scflow_corr_lookup_masked): → [B, L·(2r+1)², H, W]."""
+    B, _, H, W = flow.shape
+    return ops.corr_lookup(pyramid.contiguous(), flow.contiguous(), B, H, W, num_levels, radius,
+                           align_corners=align_corners, mask=mask.contiguous().view(B * H * W))
+
+
+@corr_lookup_masked.register_fake
+def _(pyramid, flow, mask, num_levels, radius, align_corners):
+    B, _, H, W = flow.shape
+    return flow.new_empty(B, num_levels * (2 * radius + 1) ** 2, H, W)
+
+
+def _corr_lookup_masked_setup(ctx, inputs, output):
+    pyramid, flow, mask, num_levels, radius, align_corners = inputs
+    ctx.save_for_backward(flow, mask)
+    ctx.cfg = (pyramid.numel(), num_levels, radius, align_corners)
+
+
+@torch.library.custom_op("scflow::corr_lookup_masked_backward", mutates_args=(),
+                         device_types="cuda")
+def corr_lookup_masked_backward(dout: Tensor, flow: Tensor, mask: Tensor, numel: int,
+                                num_levels: int, radius: int) -> Tensor:
+    """Gradient w.r.t. the pyramid only: the adjoint scatter of mask · dout
+    (scflow_corr_lookup_backward_masked, align_corners=True)."""
+    B, _, H, W = flow.shape
+    dpyr = torch.zeros(numel, device=dout.device, dtype=torch.float32)
+    ops.corr_lookup_backward(dout.permute(0, 2, 3, 1).contiguous().view(B * H * W, -1),
+                             flow.permute(0, 2, 3, 1).contiguous(), dpyr, B, H, W, num_levels,
+                             radius, mask=mask.contiguous().view(B * H * W))
+    return dpyr
+
+
+@corr_lookup_masked_backward.register_fake
+def _(dout, flow, mask, numel, num_levels, radius):
+    return dout.new_empty(numel)
+
+
+def _corr_lookup_masked_backward(ctx, dout):
+    flow, mask = ctx.saved_tensors
+    numel, L, r, ac = ctx.cfg
+    if not ac:
+        raise NotImplementedError("scflow::corr_lookup_masked backward: align_corners=True only "
+                                  "(SCFlow's configuration)")
+    if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+        # the same policy as scflow::corr_lookup's flow gradient: every SCFlow configuration
+        # detaches both (detach_flow, detach_mask), and a silent zero gradient would be wrong
+        raise NotImplementedError("scflow::corr_lookup_masked backward: no gradient w.r.t. flow "
+                                  "or mask — detach them (detach_flow / detach_mask)")
+    return corr_lookup_masked_backward(dout, flow, mask, numel, L, r), None, None, None, None, None
+
+
+corr_lookup_masked.register_autograd(_corr_lookup_masked_backward,
+                                     setup_context=_corr_lookup_masked_setup)
+
+
 # ------------------------------------------------------------------------------------ a8 + a10
 @torch.library.custom_op("scflow::pose_update_flow", mutates_args=(), device_types="cuda")
 def pose_update_flow(drot: Tensor, dt: Tensor, R: Tensor, t: Tensor, K: Tensor, points: Tensor,

@@ -250,10 +250,21 @@ def pyramid_buffer(levels: Sequence[Tensor], n: int, h: int, w: int) -> Tensor:
 
 
 # ------------------------------------------------------------------------------- a2 lookup
+def _require_mask(mask: Tensor, m: int, like: Tensor) -> None:
+    """An occlusion mask of the masked entries: contiguous float32, one value per pixel."""
+    _require(mask, "mask")
+    if mask.numel() != m or mask.device != like.device:
+        raise ValueError(f"mask must hold {m} values on {like.device}, got {tuple(mask.shape)} on "
+                         f"{mask.device}")
+
+
 def corr_lookup(pyr: Tensor, flow: Tensor, n: int, h: int, w: int, num_levels: int, radius: int,
                 out: Optional[Chan] = None, flow_layout: str = "nchw",
-                align_corners: bool = True, tiled: bool = False) -> Tensor:
-    """Window lookup.  ``out=None`` → NCHW ``[n, L(2r+1)², h, w]`` (the reference's layout,
+                align_corners: bool = True, tiled: bool = False,
+                mask: Optional[Tensor] = None) -> Tensor:
+    """Window lookup.  ``mask`` ([n·h·w] or [n·h·w, 1], default None): every sample of pixel m
+    is multiplied by ``mask[m]`` where it is stored (scflow_corr_lookup_masked, the reference's
+    ``mask_corr``); None calls the unmasked exports.  ``out=None`` → NCHW ``[n, L(2r+1)², h, w]`` (the reference's layout,
     corr_lookup.py:135-136); otherwise written channels-last into ``out``.  ``align_corners``:
     grid_sample's (SCFlow's config True; False: bilinear_sample's default, corr_lookup.py:35).
     ``tiled``: ``pyr`` is a ``corr_pyramid_tiled`` buffer."""
@@ -267,7 +278,11 @@ def corr_lookup(pyr: Tensor, flow: Tensor, n: int, h: int, w: int, num_levels: i
     else:
         res = out.buf
         ptr, olay, ostride = out.ptr, _lib.LAYOUT_NHWC, out.stride
-    if tiled:
+    if mask is not None:
+        _require_mask(mask, n * h * w, flow)
+        _launch("scflow_corr_lookup_masked", flow, _p(pyr), _p(flow), lay, _p(mask), ptr, olay,
+                ostride, n, h, w, num_levels, radius, int(bool(align_corners)), int(bool(tiled)))
+    elif tiled:
         _launch("scflow_corr_lookup_tiled", flow, _p(pyr), _p(flow), lay, ptr, olay, ostride, n, h,
                 w, num_levels, radius, int(bool(align_corners)))
     elif align_corners:
@@ -281,9 +296,11 @@ def corr_lookup(pyr: Tensor, flow: Tensor, n: int, h: int, w: int, num_levels: i
 
 def corr_lookup_conv1x1(pyr: Tensor, flow: Tensor, packed: Tensor, bias: Optional[Tensor], out: Chan,
                         n: int, h: int, w: int, num_levels: int, radius: int, cout: int,
-                        act: Optional[str] = "ReLU", align_corners: bool = True) -> None:
+                        act: Optional[str] = "ReLU", align_corners: bool = True,
+                        mask: Optional[Tensor] = None) -> None:
     """The tiled lookup and corr_net.0 (1×1, weights packed with ``_lib.CONV_1X1W``) in one launch
-    (scflow_corr_lookup_conv1x1): ``out`` ← act(W·lookup + bias); ``flow`` [n·h·w, 2] (NHWC)."""
+    (scflow_corr_lookup_conv1x1): ``out`` ← act(W·lookup + bias); ``flow`` [n·h·w, 2] (NHWC).
+    ``mask`` ([n·h·w]): act(W·(mask·lookup) + bias) (scflow_corr_lookup_conv1x1_masked)."""
     _require(pyr, "pyramid")
     _require(flow, "flow", contiguous=False)
     _require(packed, "packed weight")
@@ -291,6 +308,12 @@ def corr_lookup_conv1x1(pyr: Tensor, flow: Tensor, packed: Tensor, bias: Optiona
         _require(bias, "bias")
     if out.c != cout:
         raise ValueError(f"out has {out.c} channels, expected {cout}")
+    if mask is not None:
+        _require_mask(mask, n * h * w, flow)
+        _launch("scflow_corr_lookup_conv1x1_masked", flow, _p(pyr), _p(flow), _p(mask), _p(packed),
+                _p(bias), out.ptr, out.stride, n, h, w, num_levels, radius, cout,
+                _lib.SCFLOW_ACT[act], int(bool(align_corners)))
+        return
     _launch("scflow_corr_lookup_conv1x1", flow, _p(pyr), _p(flow), _p(packed), _p(bias), out.ptr,
             out.stride, n, h, w, num_levels, radius, cout, _lib.SCFLOW_ACT[act], int(bool(align_corners)))
 
@@ -563,13 +586,17 @@ def pose_step(drot: Tensor, dt: Tensor, R: Tensor, t: Tensor, K: Tensor, points:
               mask_up: Optional[Tensor], h: int, w: int, up_scale: float,
               lr_next: Optional[Chan] = None, hx_next: Optional[Chan] = None,
               weight: float = 10.0, depth_transform: str = "exp", parts: int = 3,
-              heads: Optional[tuple] = None) -> None:
+              heads: Optional[tuple] = None, mask_next: Optional[Tensor] = None,
+              lrm_next: Optional[Chan] = None) -> None:
     """One launch: ``pose_update_flow`` + ``flow_upsample(lr, delta, mask → flow_up, mask_up)``
     + (if ``lr_next``) the next iteration's ``flow_downsample`` of the new pose flow into
     ``lr_next`` / ``hx_next``, computed from the pose directly (scflow_pose_step).  ``parts``
     (scflow_pose_step_part): 1 = only the full-resolution outputs, 2 = only the ↓8 flow.
     ``heads`` (``MultiClassPoseHead.heads_args``): the pose head's rotation / translation heads
-    in the same launch (scflow_pose_step_heads) — ``drot`` / ``dt`` are then written, not read."""
+    in the same launch (scflow_pose_step_heads) — ``drot`` / ``dt`` are then written, not read.
+    ``mask_next`` ([n·h·w], the mask just predicted) / ``lrm_next`` (scflow_pose_step_masked, the
+    reference's ``mask_flow``): ``lr_next`` still receives the unmasked ↓8 flow, ``lrm_next`` and
+    ``hx_next`` receive ``lr_next · mask_next``."""
     for nm, x in (("drot", drot), ("dt", dt), ("R", R), ("t", t), ("K", K), ("points", points),
                   ("R_out", R_out), ("t_out", t_out), ("flow_out", flow_out), ("lr", lr),
                   ("flow_up", flow_up)):
@@ -587,6 +614,21 @@ def pose_step(drot: Tensor, dt: Tensor, R: Tensor, t: Tensor, K: Tensor, points:
         x, xsplit, xbias, k, Wr, br, rch, Wt, bt, label, num_class = heads
         if label.dtype != torch.int64 or label.device != x.device:
             raise TypeError("label must be an int64 tensor on the same device")
+    if mask_next is not None or lrm_next is not None:
+        if lr_next is None:
+            raise ValueError("pose_step: mask_next / lrm_next need lr_next")
+        if mask_next is not None:
+            _require_mask(mask_next, n * h * w, lr)
+        if lrm_next is not None and lrm_next.buf.data_ptr() in (lr.data_ptr(),
+                                                                lr_next.buf.data_ptr()):
+            raise ValueError("pose_step: lrm_next must alias neither lr nor lr_next")
+        hd = ((None, 0, None, 0, None, None, 0, None, None, None, 0) if heads is None else
+              (_p(x), int(xsplit), _p(xbias), int(k), _p(Wr), _p(br), int(rch), _p(Wt), _p(bt),
+               _p(label), int(num_class)))
+        _launch("scflow_pose_step_masked", drot, *hd, *args[:24], _p(mask_next),
+                None if lrm_next is None else lrm_next.ptr,
+                0 if lrm_next is None else lrm_next.stride, *args[24:], int(parts))
+    elif heads is not None:
         _launch("scflow_pose_step_heads", drot, _p(x), int(xsplit), _p(xbias), int(k), _p(Wr), _p(br),
                 int(rch), _p(Wt), _p(bt), _p(label), int(num_class), *args, int(parts))
     elif parts == 3:
@@ -614,9 +656,20 @@ def pose_step_given(R: Tensor, t: Tensor, K: Tensor, points: Tensor, flow_out: T
 
 # ------------------------------------------------------------------------------- resampling
 def flow_downsample(flow: Tensor, out0: Chan, h: int, w: int, value_scale: float,
-                    out1: Optional[Chan] = None) -> None:
+                    out1: Optional[Chan] = None, mask: Optional[Tensor] = None,
+                    outm: Optional[Chan] = None) -> None:
+    """``mask`` ([n·h·w]) / ``outm`` (scflow_flow_downsample_masked): ``out0`` keeps the unmasked
+    flow, ``out1`` and ``outm`` receive flow · mask."""
     _require(flow, "flow")
     n, _, H, W = flow.shape
+    if mask is not None or outm is not None:
+        if mask is not None:
+            _require_mask(mask, n * h * w, flow)
+        _launch("scflow_flow_downsample_masked", flow, _p(flow), out0.ptr, out0.stride,
+                None if out1 is None else out1.ptr, 0 if out1 is None else out1.stride, _p(mask),
+                None if outm is None else outm.ptr, 0 if outm is None else outm.stride, n, H, W, h,
+                w, float(value_scale))
+        return
     _launch("scflow_flow_downsample", flow,
         _p(flow), out0.ptr, out0.stride, None if out1 is None else out1.ptr,
         0 if out1 is None else out1.stride, n, H, W, h, w, float(value_scale))
@@ -1163,12 +1216,18 @@ def col2im(cols: Tensor, n: int, h: int, w: int, cin: int, kh: int, kw: int, str
 
 def corr_lookup_backward(dout: Tensor, flow: Tensor, dpyr: Tensor, n: int, h: int, w: int,
                          num_levels: int, radius: int, out_layout: str = "nhwc",
-                         flow_layout: str = "nhwc") -> None:
-    """dpyr (zeroed, pyramid layout) += adjoint of corr_lookup applied to dout."""
+                         flow_layout: str = "nhwc", mask: Optional[Tensor] = None) -> None:
+    """dpyr (zeroed, pyramid layout) += adjoint of corr_lookup applied to dout; with ``mask``
+    ([n·h·w]) to mask · dout (scflow_corr_lookup_backward_masked; no gradient for the mask)."""
     for nm, t in (("dout", dout), ("flow", flow), ("dpyr", dpyr)):
         _require(t, nm)
     lay = {"nchw": _lib.LAYOUT_NCHW, "nhwc": _lib.LAYOUT_NHWC}
     stride = dout.shape[-1] if out_layout == "nhwc" else 0
+    if mask is not None:
+        _require_mask(mask, n * h * w, dout)
+        _launch("scflow_corr_lookup_backward_masked", dout, _p(dout), lay[out_layout], stride,
+                _p(flow), lay[flow_layout], _p(mask), _p(dpyr), n, h, w, num_levels, radius)
+        return
     _launch("scflow_corr_lookup_backward", dout,_p(dout), lay[out_layout], stride, _p(flow),
                                                   lay[flow_layout], _p(dpyr), n, h, w, num_levels,
                                                   radius)

@@ -1060,38 +1060,47 @@ class _CorrLookup(torch.autograd.Function):
     sees the complete sum, without a zeroed buffer and a full-size add per iteration."""
 
     @staticmethod
-    def forward(ctx, pyr, flow_nhwc, n, h, w, num_levels, radius):
+    def forward(ctx, pyr, flow_nhwc, mask, n, h, w, num_levels, radius):
         flow_nhwc = flow_nhwc.contiguous()
-        ctx.save_for_backward(flow_nhwc)
+        ctx.masked = mask is not None
+        if ctx.masked:  # detached [n·h·w] occlusion mask: scales the samples, and dout below
+            ctx.save_for_backward(flow_nhwc, mask)
+        else:
+            ctx.save_for_backward(flow_nhwc)
         holder = ctx.holder = _dpyr_holder(pyr)
         holder["uses"] += 1
         ctx.dims = (n, h, w, num_levels, radius, pyr.numel())
         out = torch.empty(n * h * w, num_levels * (2 * radius + 1) ** 2, device=pyr.device)
         ops.corr_lookup(pyr, flow_nhwc, n, h, w, num_levels, radius, out=Chan.whole(out),
-                        flow_layout="nhwc")
+                        flow_layout="nhwc", mask=mask)
         return out.view(n, h, w, -1)
 
     @staticmethod
     def backward(ctx, dout):
-        (flow,) = ctx.saved_tensors
+        flow, mask = ctx.saved_tensors if ctx.masked else (ctx.saved_tensors[0], None)
         n, h, w, L, r, size = ctx.dims
         hd = ctx.holder
         first = hd["buf"] is None
         if first:
             hd["buf"] = torch.zeros(size, device=dout.device)
         dpyr = hd["buf"]
-        ops.corr_lookup_backward(dout.contiguous().view(n * h * w, -1), flow, dpyr, n, h, w, L, r)
+        ops.corr_lookup_backward(dout.contiguous().view(n * h * w, -1), flow, dpyr, n, h, w, L, r,
+                                 mask=mask)
         hd["seen"] += 1
         if hd["seen"] >= hd["uses"]:  # every lookup of this pass added its share: release it
             hd["buf"] = None
             hd["seen"] = 0
-        return (dpyr if first else None), None, None, None, None, None, None
+        return (dpyr if first else None), None, None, None, None, None, None, None
 
 
 def corr_lookup(pyr: Tensor, flow_nhwc: Tensor, n: int, h: int, w: int, num_levels: int = 4,
-                radius: int = 4) -> Tensor:
-    """[n, h, w, L·(2r+1)²] channels-last lookup; differentiable w.r.t. the pyramid only."""
-    return _CorrLookup.apply(pyr, flow_nhwc.detach(), n, h, w, num_levels, radius)
+                radius: int = 4, mask: Optional[Tensor] = None) -> Tensor:
+    """[n, h, w, L·(2r+1)²] channels-last lookup; differentiable w.r.t. the pyramid only.
+    ``mask`` ([n·h·w], detached here): the occlusion-masked lookup and its masked adjoint
+    (scflow_corr_lookup_masked / scflow_corr_lookup_backward_masked)."""
+    if mask is not None:
+        mask = mask.detach().contiguous().view(-1)
+    return _CorrLookup.apply(pyr, flow_nhwc.detach(), mask, n, h, w, num_levels, radius)
 
 
 # ------------------------------------------------------------------------------- upsampling

@@ -170,14 +170,28 @@ def pose_update(drot: Tensor, dt: Tensor, R: Tensor, t: Tensor, weight: float = 
 
 
 # ------------------------------------------------------------------------------- decoder
+def check_train_flags(dec) -> None:
+    """The decoder flags the training path supports, checked before any device work:
+    detach_flow=True, and detach_mask=True whenever mask_flow / mask_corr is set (every shipped
+    config, configs/refine_models/*.py) — the lookup and the flow branch give the flow and the
+    mask no gradient."""
+    if not dec.detach_flow:
+        raise NotImplementedError("training path follows the configured decoder: detach_flow=True "
+                                  "(scflow_ycbv_real.py:213-218)")
+    if (dec.mask_flow or dec.mask_corr) and not dec.detach_mask:
+        raise NotImplementedError("training with mask_flow / mask_corr needs detach_mask=True: "
+                                  "detach_mask=False would need the gradient with respect to the "
+                                  "mask through the lookup and the flow branch, which is not "
+                                  "implemented")
+
+
 def decoder_train(dec, feat_render: Tensor, feat_real: Tensor, h: Tensor, cxt: Tensor, R0: Tensor,
                   t0: Tensor, depth: Tensor, K: Tensor, label: Tensor, iters: int,
                   invalid_flow_num: float = 0.0) -> Tuple[List[Tensor], ...]:
     """SCFlowDecoder.forward with autograd (scflow_decoder.py:151-252); features channels-last
     [N, h, w, C].  Returns (flow_from_pose, flow_from_pred, R, t, mask, Δrot, Δt) lists."""
-    if not dec.detach_flow or dec.mask_flow or dec.mask_corr:
-        raise NotImplementedError("training path follows the configured decoder: detach_flow=True, "
-                                  "mask_flow=mask_corr=False (scflow_ycbv_real.py:213-218)")
+    check_train_flags(dec)
+    masked = dec.mask_flow or dec.mask_corr
     N, hh, ww, _ = feat_render.shape
     _, H, W = depth.shape
     dt = feat_render.dtype
@@ -215,22 +229,36 @@ def decoder_train(dec, feat_render: Tensor, feat_real: Tensor, h: Tensor, cxt: T
                    and fl[0].conv.padding == ml[0].conv.padding and fl[0].conv.stride == (1, 1)
                    and ml[0].conv.stride == (1, 1) and fl[0].act_type == ml[0].act_type
                    and (fl[0].conv.bias is None) == (ml[0].conv.bias is None))
+    mask = None
     for _ in range(iters):
+        # occlusion masking (scflow_decoder.py:189-207): the previous iteration's low-resolution
+        # mask, detached (detach_mask=True); all ones before the first prediction, i.e. no mask
+        mk = mask.detach().contiguous().view(N * hh * ww) if masked and mask is not None else None
         with torch.no_grad():  # flow is detached every iteration (detach_flow=True)
             f2 = torch.empty(N * hh * ww, 2, device=depth.device, dtype=dt)
-            ops.flow_downsample(flow_full.contiguous(), Chan.whole(f2), hh, ww, 1.0 / scale)
+            if dec.mask_flow and mk is not None:  # f2m = f2 · mask in the same launch
+                f2m = torch.empty_like(f2)
+                ops.flow_downsample(flow_full.contiguous(), Chan.whole(f2), hh, ww, 1.0 / scale,
+                                    mask=mk, outm=Chan.whole(f2m))
+            else:
+                f2m = f2
+                ops.flow_downsample(flow_full.contiguous(), Chan.whole(f2), hh, ww, 1.0 / scale)
         f2 = f2.view(N, hh, ww, 2)
-        corr = corr_lookup(pyr, f2, N, hh, ww, L, r)
+        f2m = f2m.view(N, hh, ww, 2)  # the flow branch's input and the motion features' flow
+        if dec.mask_corr and mk is not None:
+            corr = corr_lookup(pyr, f2, N, hh, ww, L, r, mask=mk)
+        else:
+            corr = corr_lookup(pyr, f2, N, hh, ww, L, r)
         c = corr
         for m in enc.corr_net:
             c = _cm(c, m)
-        f = f2
+        f = f2m
         for m in enc.flow_net:
             f = _cm(f, m)
         out = _cm(c, enc.out_net[0], x1=f)
         for m in enc.out_net[1:]:
             out = _cm(out, m)
-        motion = torch.cat([out, f2], -1)
+        motion = torch.cat([out, f2m], -1)
         for (w_zr, w_q, pad), (pre_zr, pre_q) in zip(it_w, ctx_pre):  # SeqConv: 1×5 then 5×1
             if _GRU_FUSED:
                 h = gru_step(h, motion, w_zr, w_q, pre_zr, pre_q, pad)  # (1 − z)·h + z·q
@@ -285,8 +313,9 @@ def refiner_train_forward(refiner, batch: Dict[str, Tensor], model_points: Seque
     render_images, real_images [N,3,S,S]; ref_rotation, ref_translation, gt_rotation,
     gt_translation, internel_k, depth, label; optional head_label (the pose head's class label,
     default label — a data-parallel shard passes the global batch's label[:1], dist.shard_batch)."""
-    begin_forward()  # per-weight use counts of this pass (batched weight gradients)
     dec = refiner.decoder
+    check_train_flags(dec)
+    begin_forward()  # per-weight use counts of this pass (batched weight gradients)
     iters = int(dec.iters if iters is None else iters)
     real = batch["real_images"].permute(0, 2, 3, 1).contiguous()
     render = batch["render_images"].permute(0, 2, 3, 1).contiguous()

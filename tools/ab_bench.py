@@ -3,6 +3,9 @@
 usage: python tools/ab_bench.py [--batch 16] [--rounds 5] [--steps 10] attr=v1,v2 [attr=...]
 e.g.   python tools/ab_bench.py split_pose_conv1=1,0 hoist_context=1,0
        python tools/ab_bench.py env:SCFLOW_WINO4_DEPTH=0,1   (switches read per launch)
+       python tools/ab_bench.py mask_flow=0,1 mask_corr=0,1 rep=0,1   (occlusion masking; `rep` is
+       not an attribute the decoder reads: its two values repeat every variant, which gives the
+       spread between identical runs of one session)
 Every combination is timed `rounds` times in round-robin order; prints median ms/forward.
 """
 import argparse
@@ -77,7 +80,8 @@ def main():
     for c in combos:
         med = statistics.median(res[c])
         print(" ".join(f"{k}={v}" for k, v in zip(names, c)) or "default",
-              f"median {med:.3f} ms/fwd  {a.batch * a.iters / med * 1e3:.0f} iters/s  "
+              f"median {med:.3f} ms/fwd  (min {min(res[c]):.3f} max {max(res[c]):.3f})  "
+              f"{a.batch * a.iters / med * 1e3:.0f} iters/s  "
               f"runs {[round(x, 3) for x in res[c]]}", flush=True)
 
 
