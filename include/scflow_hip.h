@@ -26,6 +26,9 @@
  *   scflow_flow_upsample     <- 8·F.interpolate(flow+Δflow, ×8) and mask ×8 (same)          scflow_decoder.py:223-228
  *   scflow_pose_step         <- one iteration's tail fused: pose update + pose flow + the ×8
  *                               prediction + the next iteration's ↓8 flow   scflow_decoder.py:197-198, 223-244
+ *   scflow_convex_upsample   <- RAFT's convex ×8 upsampling of the flow and the occlusion (softmax over
+ *                               the 3×3 neighbourhood per sub-pixel)   raft_decoder.py:381-416,
+ *                               raft_decoder_mask.py:104-160
  *   scflow_transpose         <- layout plumbing (NCHW <-> channels-last slices), no reference equivalent
  *   scflow_ph_*              <- MultiClassPoseHead.forward                models/head/pose_head.py:201-211
  *   scflow_enc_*             <- RAFTEncoder.forward (Basic; IN / BN)      models/encoder/raft_encoder.py:286-314
@@ -288,6 +291,31 @@ int scflow_flow_downsample_masked(const float* flow, float* out0, int s0, float*
 int scflow_flow_upsample(const float* lr, const float* delta, const float* mask, float* flow_out,
                          float* mask_out, int n, int h, int w, int H, int W, float value_scale,
                          void* stream);
+
+/* RAFT's convex upsampling (RAFTDecoder._upsample, raft_decoder.py:381-416; RAFTDecoderMask.
+ * upsample_flow / upsample_mask, raft_decoder_mask.py:104-160), one launch.  With s = scale = 8 and
+ * k = ky·3 + kx over the 3×3 neighbourhood (grid_side = 3):
+ *   w[k][sy][sx]                 = softmax over k of logit_scale · logits[pixel][k·64 + sy·8 + sx]
+ *   flow_up[n][c][8y+sy][8x+sx]  = value_scale · Σ_k w[k][sy][sx] · (lr + delta)[n][y+ky-1][x+kx-1][c]
+ *   occ_up [n][0][8y+sy][8x+sx]  =               Σ_k w[k][sy][sx] ·  occ        [n][y+ky-1][x+kx-1]
+ * Neighbours outside the map count as zero (F.unfold(padding=1)) and are never loaded.  One softmax
+ * (maximum subtracted) serves both outputs.  logits: channels-last [n·h·w][≥ 576] with pixel stride
+ * ls; lr, delta (may be NULL): channels-last [n·h·w][2]; occ (may be NULL, then occ_up is not
+ * written): [n·h·w][1].  flow_up [n][2][8h][8w] and occ_up [n][1][8h][8w] are NCHW and 16-byte
+ * aligned (float4 stores along the rows; else SCFLOW_EALIGN).  next0 / next1 (either may be NULL;
+ * pixel strides s0 / s1 ≥ 2) receive lr + delta channels-last, the next iteration's flow — as
+ * out0 / out1 of scflow_flow_downsample; they must not alias lr or delta (a workgroup reads its
+ * neighbours' pixels).  scale ≠ 8 or grid_side ≠ 3: SCFLOW_EUNSUPPORTED. */
+int scflow_convex_upsample(const float* logits, int ls, const float* lr, const float* delta,
+                           const float* occ, float* flow_up, float* occ_up, float* next0, int s0,
+                           float* next1, int s1, int n, int h, int w, int scale, int grid_side,
+                           float logit_scale, float value_scale, void* stream);
+
+/* The RAFT decoders' bilinear branch (convex_unsample_flow=False) has no launch that produces the
+ * next iteration's flow: out0 (pixel stride s0) and, if not NULL, out1 (stride s1) = lr + delta,
+ * all channels-last [n·h·w][2].  out0 / out1 must not alias lr or delta. */
+int scflow_flow_add(const float* lr, const float* delta, float* out0, int s0, float* out1, int s1,
+                    int n, int h, int w, void* stream);
 
 /* One launch = scflow_pose_update_flow(drot6 .. invalid_num; flow is [n][2][H][W]) +
  * scflow_flow_upsample(lr, delta, mask, flow_up, mask_up, n, h, w, H, W, up_scale) when flow_up

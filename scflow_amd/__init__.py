@@ -15,6 +15,9 @@ def __getattr__(name):
     if name in ("SCFlowDecoder",):
         from .decoder import SCFlowDecoder
         return SCFlowDecoder
+    if name in ("RAFTDecoder", "RAFTDecoderMask"):
+        from . import raft_decoder
+        return getattr(raft_decoder, name)
     if name in ("CorrelationPyramid", "CorrLookup", "MotionEncoder", "ConvGRU", "XHead",
                 "MultiClassPoseHead", "ConvModule"):
         from . import modules

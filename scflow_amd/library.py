@@ -13,6 +13,8 @@ op                             reference                                        
 ``scflow::pose_update_flow``   get_pose_from_delta_pose + get_flow_from_delta_pose_   no (the
                                and_points, pose.py:66-88,124-169                      decoder
                                                                                       detaches)
+``scflow::convex_upsample``    RAFTDecoder._upsample, raft_decoder.py:381-416, and    no (infer-
+                               RAFTDecoderMask.upsample_mask, raft_decoder_mask.py    ence only)
 =============================  =====================================================  =========
 
 The two backward formulas are ops of their own (``scflow::corr_pyramid_backward``,
@@ -26,7 +28,7 @@ loudly off-GPU, ``ScflowError``).
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 
@@ -240,3 +242,35 @@ def pose_update_flow(drot: Tensor, dt: Tensor, R: Tensor, t: Tensor, K: Tensor, 
 def _(drot, dt, R, t, K, points, invalid_num, weight, depth_transform):
     n, H, W, _ = points.shape
     return torch.empty_like(R), torch.empty_like(t), R.new_empty(n, 2, H, W)
+
+
+# ------------------------------------------------------------------------------------ RAFT tail
+@torch.library.custom_op("scflow::convex_upsample", mutates_args=(), device_types="cuda")
+def convex_upsample(flow: Tensor, logits: Tensor, occ: Optional[Tensor], logit_scale: float,
+                    value_scale: float) -> Tuple[Tensor, Tensor]:
+    """RAFT's convex ×8 upsampling (RAFTDecoder._upsample, raft_decoder.py:381-416, and
+    RAFTDecoderMask.upsample_mask, raft_decoder_mask.py:141-160) with the reference's NCHW
+    operands: flow [N, 2, h, w], raw mask logits [N, 576, h, w] (the decoder's ``.25 *`` is
+    ``logit_scale``), occ [N, 1, h, w] or None → (value_scale · upsampled flow [N, 2, 8h, 8w],
+    upsampled occ [N, 1, 8h, 8w]; an empty tensor without occ).  One scflow_convex_upsample launch
+    behind two layout transposes; inference only (no autograd formula)."""
+    n, _, h, w = flow.shape
+    m = n * h * w
+    lg = torch.empty(m, logits.shape[1], device=flow.device, dtype=torch.float32)
+    ops.nchw_into(logits.contiguous().float(), ops.Chan.whole(lg))
+    lr = torch.empty(m, 2, device=flow.device, dtype=torch.float32)
+    ops.nchw_into(flow.contiguous().float(), ops.Chan.whole(lr))
+    oc = None if occ is None else occ.contiguous().float().view(m, 1)  # C = 1: already pixel-major
+    flow_up = torch.empty(n, 2, 8 * h, 8 * w, device=flow.device, dtype=torch.float32)
+    occ_up = flow_up.new_empty(0) if occ is None else flow_up.new_empty(n, 1, 8 * h, 8 * w)
+    ops.convex_upsample(ops.Chan.whole(lg), lr, None, oc, n, h, w, flow_up,
+                        None if occ is None else occ_up, logit_scale=logit_scale,
+                        value_scale=value_scale)
+    return flow_up, occ_up
+
+
+@convex_upsample.register_fake
+def _(flow, logits, occ, logit_scale, value_scale):
+    n, _, h, w = flow.shape
+    return flow.new_empty(n, 2, 8 * h, 8 * w), \
+        (flow.new_empty(0) if occ is None else flow.new_empty(n, 1, 8 * h, 8 * w))

@@ -683,6 +683,59 @@ def flow_upsample(lr: Tensor, delta: Optional[Tensor], mask: Optional[Tensor], n
                                            n, h, w, H, W, float(value_scale))
 
 
+def convex_upsample(logits: Chan, lr: Tensor, delta: Optional[Tensor], occ: Optional[Tensor],
+                    n: int, h: int, w: int, flow_out: Tensor, occ_out: Optional[Tensor] = None,
+                    next0: Optional[Chan] = None, next1: Optional[Chan] = None,
+                    logit_scale: float = 0.25, value_scale: float = 8.0, scale: int = 8,
+                    grid_side: int = 3) -> None:
+    """RAFT's convex upsampling (scflow_convex_upsample): ``logits`` channels-last [n·h·w, 576]
+    (a ``Chan``), ``lr`` / ``delta`` [n·h·w, 2], ``occ`` [n·h·w, 1] (or None) →
+    ``flow_out`` [n, 2, 8h, 8w] = value_scale · Σ softmax(logit_scale · logits) · (lr + delta) over
+    the 3×3 neighbourhood, ``occ_out`` [n, 1, 8h, 8w] likewise (no scale); ``next0`` / ``next1``
+    receive lr + delta (the next iteration's flow; they must not alias ``lr`` / ``delta``)."""
+    _require(logits.buf, "logits")
+    _require(lr, "lr flow")
+    _require(flow_out, "flow_out")
+    m = n * h * w
+    if logits.c != grid_side * grid_side * scale * scale:
+        raise ValueError(f"convex upsampling expects {grid_side * grid_side * scale * scale} logit "
+                         f"channels, got {logits.c}")
+    if logits.buf.numel() < m * logits.stride or lr.numel() != 2 * m or \
+            (delta is not None and delta.numel() != 2 * m) or (occ is not None and occ.numel() != m):
+        raise ValueError("convex_upsample: inputs do not have n·h·w pixels")
+    if tuple(flow_out.shape) != (n, 2, scale * h, scale * w) or \
+            (occ is not None and (occ_out is None or
+                                  tuple(occ_out.shape) != (n, 1, scale * h, scale * w))):
+        raise ValueError("convex_upsample: outputs must be [n, 2, 8h, 8w] and [n, 1, 8h, 8w]")
+    for nm, c in (("next0", next0), ("next1", next1)):
+        if c is not None and (c.c != 2 or c.buf.numel() < m * c.stride):
+            raise ValueError(f"convex_upsample: {nm} must be 2 channels of an n·h·w-pixel buffer")
+    if delta is not None:
+        _require(delta, "delta flow")
+    if occ is not None:
+        _require(occ, "occlusion")
+        _require(occ_out, "occ_out")
+    _launch("scflow_convex_upsample", lr, logits.ptr, logits.stride, _p(lr), _p(delta), _p(occ),
+            _p(flow_out), _p(occ_out) if occ is not None else None,
+            None if next0 is None else next0.ptr, 0 if next0 is None else next0.stride,
+            None if next1 is None else next1.ptr, 0 if next1 is None else next1.stride,
+            n, h, w, scale, grid_side, float(logit_scale), float(value_scale))
+
+
+def flow_add(lr: Tensor, delta: Tensor, out0: Chan, n: int, h: int, w: int,
+             out1: Optional[Chan] = None) -> None:
+    """out0 (and out1) ← lr + delta, channels-last [n·h·w, 2] (scflow_flow_add)."""
+    _require(lr, "lr flow")
+    _require(delta, "delta flow")
+    m = n * h * w
+    if lr.numel() != 2 * m or delta.numel() != 2 * m or out0.c != 2 or \
+            out0.buf.numel() < m * out0.stride or \
+            (out1 is not None and (out1.c != 2 or out1.buf.numel() < m * out1.stride)):
+        raise ValueError("flow_add: operands must be 2 channels of n·h·w pixels")
+    _launch("scflow_flow_add", lr, _p(lr), _p(delta), out0.ptr, out0.stride,
+            None if out1 is None else out1.ptr, 0 if out1 is None else out1.stride, n, h, w)
+
+
 # ------------------------------------------------------------------------------- layout
 def nchw_into(x: Tensor, dst: Chan) -> None:
     """x [N,C,H,W] → channels [off, off+C) of channels-last ``dst.buf`` ([N,H,W,Ct] or [NHW,Ct])."""

@@ -78,4 +78,5 @@ class Registry:
 
 
 MODELS = Registry("model", locations=["scflow_amd.modules", "scflow_amd.decoder", "scflow_amd.encoder",
-                                       "scflow_amd.refiner"])
+                                       "scflow_amd.refiner", "scflow_amd.raft_decoder",
+                                       "scflow_amd.raft_refiner"])

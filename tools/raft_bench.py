@@ -1,0 +1,115 @@
+"""Timing of the RAFT baseline decoders (RAFTDecoderMask, RAFTDecoder), interleaved in one process.
+
+usage: python tools/raft_bench.py [--batch 16] [--size 256] [--iters 12] [--rounds 7] [--steps 10]
+                                  [--json out.json] [--once KIND]
+
+Each decoder is warmed up, then timed `rounds` times in round-robin order (`steps` forwards per
+round, a device synchronise at both ends); prints the median, minimum and maximum ms per forward
+of each and one JSON line with all of it.  It also prints the bytes the convex-upsampling launch
+moves per call (from the shapes: logits + flow, Δflow, occlusion in; ×8 flow / occlusion and the
+two next-flow destinations out), the figure a kernel trace's launch time is divided into.
+
+`--once KIND` runs `steps` forwards of one decoder and nothing else: the run to put under
+`rocprofv3 --kernel-trace --stats` (a run of its own; end-to-end numbers come from the untraced
+run).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+KINDS = ("RAFTDecoderMask", "RAFTDecoder")
+
+
+def decoder_cfg(kind, iters):
+    """The decoder block of the reference's configs/refine_models/raft.py:40-48."""
+    return dict(type=kind, net_type="Basic", num_levels=4, radius=4, iters=iters,
+                corr_lookup_cfg=dict(align_corners=True), gru_type="SeqConv",
+                act_cfg=dict(type="ReLU"))
+
+
+def tail_bytes(batch, size, occlusion):
+    """Bytes one scflow_convex_upsample launch has to move (fp32)."""
+    m = batch * (size // 8) ** 2
+    per_px = 576 + 2 + 2 + 64 * 2 + 2 + 2  # logits, lr, delta | ×8 flow, next0, next1
+    if occlusion:
+        per_px += 1 + 64
+    return 4 * m * per_px
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--iters", type=int, default=12)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--once", default=None, choices=KINDS)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("raft_bench.py needs a GPU (a CPU run measures nothing)")
+    from scflow_amd import MODELS, synthetic
+    dev = torch.device("cuda")
+    raw = synthetic.make_decoder_inputs(a.batch, a.size, seed=0)
+    h = a.size // 8
+    inp = dict(feat1=torch.from_numpy(raw["feat_render"]).to(dev),
+               feat2=torch.from_numpy(raw["feat_real"]).to(dev),
+               flow=torch.zeros(a.batch, 2, h, h, device=dev),
+               h_feat=torch.from_numpy(raw["h_feat"]).to(dev),
+               cxt_feat=torch.from_numpy(raw["cxt_feat"]).to(dev))
+    kinds = (a.once,) if a.once else KINDS
+    decs = {}
+    for kind in kinds:
+        dec = MODELS.build(decoder_cfg(kind, a.iters))
+        synthetic.fill_module_(dec)
+        with torch.no_grad():  # a softmax that is not flat (the golden fixtures' gain)
+            dec.mask_pred.predict_layer.weight.mul_(32.0)
+        decs[kind] = dec.to(dev).eval()
+    if a.once:
+        for _ in range(a.steps):
+            decs[a.once](**inp)
+        torch.cuda.synchronize()
+        print(f"{a.once}: {a.steps} forwards of {a.iters} iterations, B={a.batch}, {a.size}²; "
+              f"convex tail moves {tail_bytes(a.batch, a.size, a.once == KINDS[0])} B per launch")
+        return
+    for dec in decs.values():  # warm every shape (packing, allocator, code objects)
+        for _ in range(3):
+            dec(**inp)
+    torch.cuda.synchronize()
+    times = {k: [] for k in kinds}
+    for _ in range(a.rounds):
+        for kind in kinds:
+            dec = decs[kind]
+            dec(**inp)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                dec(**inp)
+            torch.cuda.synchronize()
+            times[kind].append((time.perf_counter() - t0) / a.steps * 1e3)
+    res = dict(batch=a.batch, size=a.size, iters=a.iters, rounds=a.rounds, steps=a.steps)
+    for kind in kinds:
+        v = times[kind]
+        res[kind] = dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v),
+                         ms_per_iteration=statistics.median(v) / a.iters, plan=decs[kind].last_plan,
+                         tail_bytes=tail_bytes(a.batch, a.size, kind == KINDS[0]))
+        print(f"{kind}: median {res[kind]['median_ms']:.3f} ms/forward "
+              f"(min {min(v):.3f}, max {max(v):.3f}; {res[kind]['ms_per_iteration']:.3f} ms/iteration)")
+    line = json.dumps(res)
+    print(line)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
