@@ -311,6 +311,28 @@ int scflow_convex_upsample(const float* logits, int ls, const float* lr, const f
                            float* next1, int s1, int n, int h, int w, int scale, int grid_side,
                            float logit_scale, float value_scale, void* stream);
 
+/* The adjoint of scflow_convex_upsample (training).  With the notation above, v_c = x channel c
+ * (vs_c = value_scale) or occ (vs_c = 1), g_c[p][s] the incoming gradient at output pixel
+ * (8y+sy, 8x+sx) of channel c and nb(p, k) = p + (ky-1, kx-1):
+ *   dw[k][s]                     = Σ_c vs_c · v_c[nb(p,k)] · g_c[p][s]      (out-of-map: 0)
+ *   dlogits[pixel][k·64 + s]     = logit_scale · w[k][s] · (dw[k][s] − Σ_j w[j][s] · dw[j][s])
+ *   dx[q][c], docc[q]            = vs_c · Σ_k Σ_s w[k][s] · g_c[p][s] over the in-map p with nb(p,k) = q
+ * The softmax is recomputed from the logits as the forward computes it; nothing is kept between
+ * the two.  No float atomics and a fixed summation order: the result is bitwise reproducible.
+ * logits [n·h·w][≥ 576] (pixel stride ls), x [n·h·w][2] (the flow that was upsampled, lr + delta),
+ * occ [n·h·w] or NULL; g_flow [n][2][8h][8w], g_occ [n][1][8h][8w] or NULL (also with occ given:
+ * its term is zero), both 16-byte aligned (else SCFLOW_EALIGN).  Outputs: dlogits [n·h·w][≥ 576]
+ * with pixel stride dls (channels 0..575 written, nothing else), dx [n·h·w][2], docc [n·h·w] or
+ * NULL (zeros when g_occ is NULL).  g_occ or docc without occ: SCFLOW_EINVAL.  ws: a workspace of
+ * at least n·h·w · 9 · C floats (C = 3 with occ and g_occ, else 2; 108·n·h·w bytes always do),
+ * ws_bytes its size; it holds the per-pixel partial sums between the two launches.  scale ≠ 8 or
+ * grid_side ≠ 3: SCFLOW_EUNSUPPORTED.  An error launches nothing. */
+int scflow_convex_upsample_bwd(const float* logits, int ls, const float* x, const float* occ,
+                               const float* g_flow, const float* g_occ, float* dlogits, int dls,
+                               float* dx, float* docc, void* ws, long long ws_bytes, int n, int h,
+                               int w, int scale, int grid_side, float logit_scale,
+                               float value_scale, void* stream);
+
 /* The RAFT decoders' bilinear branch (convex_unsample_flow=False) has no launch that produces the
  * next iteration's flow: out0 (pixel stride s0) and, if not NULL, out1 (stride s1) = lr + delta,
  * all channels-last [n·h·w][2].  out0 / out1 must not alias lr or delta. */

@@ -160,6 +160,9 @@ SIGNATURES = {
     "scflow_convex_upsample": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp,
                                        c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                        c_vp]),
+    "scflow_convex_upsample_bwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp,
+                                           c_vp, c_vp, c_ll, c_int, c_int, c_int, c_int, c_int,
+                                           c_float, c_float, c_vp]),
     "scflow_flow_add": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp]),
     "scflow_pose_step": (c_int, [c_vp] * 9 + [c_int, c_int, c_int, c_float, c_int, c_float] +
                          [c_vp] * 6 + [c_int, c_vp, c_int, c_int, c_int, c_float, c_float, c_vp]),

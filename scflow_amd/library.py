@@ -2,7 +2,7 @@
 SCFlowDecoder through torch.library.custom_op wrappers").
 
 Registered under the ``scflow`` namespace, each with a fake (meta) implementation so FX tracing,
-``torch.compile`` and ``torch.library.opcheck`` see through them, and the two differentiable
+``torch.compile`` and ``torch.library.opcheck`` see through them, and the differentiable
 ones with their HIP adjoints (``register_autograd``):
 
 =============================  =====================================================  =========
@@ -13,12 +13,14 @@ op                             reference                                        
 ``scflow::pose_update_flow``   get_pose_from_delta_pose + get_flow_from_delta_pose_   no (the
                                and_points, pose.py:66-88,124-169                      decoder
                                                                                       detaches)
-``scflow::convex_upsample``    RAFTDecoder._upsample, raft_decoder.py:381-416, and    no (infer-
-                               RAFTDecoderMask.upsample_mask, raft_decoder_mask.py    ence only)
+``scflow::convex_upsample``    RAFTDecoder._upsample, raft_decoder.py:381-416, and    yes (flow,
+                               RAFTDecoderMask.upsample_mask, raft_decoder_mask.py    logits,
+                                                                                      occ)
 =============================  =====================================================  =========
 
-The two backward formulas are ops of their own (``scflow::corr_pyramid_backward``,
-``scflow::corr_lookup_backward``), so AOT autograd traces the backward graph as well.
+The backward formulas are ops of their own (``scflow::corr_pyramid_backward``,
+``scflow::corr_lookup_backward``, ``scflow::convex_upsample_backward``), so AOT autograd traces
+the backward graph as well.
 
 The pyramid travels as ONE flat fp32 buffer (levels back to back, each ``[N·H·W, 1, H_l, W_l]``
 row-major — ``ops.pyramid_views`` turns it into the reference's list); the modules
@@ -253,7 +255,7 @@ def convex_upsample(flow: Tensor, logits: Tensor, occ: Optional[Tensor], logit_s
     operands: flow [N, 2, h, w], raw mask logits [N, 576, h, w] (the decoder's ``.25 *`` is
     ``logit_scale``), occ [N, 1, h, w] or None → (value_scale · upsampled flow [N, 2, 8h, 8w],
     upsampled occ [N, 1, 8h, 8w]; an empty tensor without occ).  One scflow_convex_upsample launch
-    behind two layout transposes; inference only (no autograd formula)."""
+    behind two layout transposes; its adjoint is ``scflow::convex_upsample_backward``."""
     n, _, h, w = flow.shape
     m = n * h * w
     lg = torch.empty(m, logits.shape[1], device=flow.device, dtype=torch.float32)
@@ -274,3 +276,55 @@ def _(flow, logits, occ, logit_scale, value_scale):
     n, _, h, w = flow.shape
     return flow.new_empty(n, 2, 8 * h, 8 * w), \
         (flow.new_empty(0) if occ is None else flow.new_empty(n, 1, 8 * h, 8 * w))
+
+
+def _convex_upsample_setup(ctx, inputs, output):
+    flow, logits, occ, logit_scale, value_scale = inputs
+    ctx.save_for_backward(flow, logits, *(() if occ is None else (occ,)))
+    ctx.scales = (logit_scale, value_scale)
+
+
+@torch.library.custom_op("scflow::convex_upsample_backward", mutates_args=(), device_types="cuda")
+def convex_upsample_backward(g_flow: Tensor, g_occ: Optional[Tensor], flow: Tensor, logits: Tensor,
+                             occ: Optional[Tensor], logit_scale: float, value_scale: float
+                             ) -> Tuple[Tensor, Tensor, Tensor]:
+    """The adjoint of ``scflow::convex_upsample`` with its NCHW operands: gradients of the ×8 flow
+    [N, 2, 8h, 8w] and the ×8 occlusion [N, 1, 8h, 8w] (None: zero) → (dflow [N, 2, h, w],
+    dlogits [N, 576, h, w], docc [N, 1, h, w]; an empty tensor without occ).  One
+    scflow_convex_upsample_bwd call (the softmax recomputed from the logits, no float atomics:
+    bitwise reproducible) between layout transposes — the training step's adjoint,
+    train/functions.py _ConvexUpsample."""
+    n, _, h, w = flow.shape
+    m = n * h * w
+    dev = flow.device
+    lg = torch.empty(m, logits.shape[1], device=dev, dtype=torch.float32)
+    ops.nchw_into(logits.contiguous().float(), ops.Chan.whole(lg))
+    x = torch.empty(m, 2, device=dev, dtype=torch.float32)
+    ops.nchw_into(flow.contiguous().float(), ops.Chan.whole(x))
+    oc = None if occ is None else occ.contiguous().float().view(m, 1)
+    dlg, dx, docc = ops.convex_upsample_backward(
+        ops.Chan.whole(lg), x, oc, g_flow.contiguous().float(),
+        None if g_occ is None or oc is None else g_occ.contiguous().float(), n, h, w,
+        logit_scale=logit_scale, value_scale=value_scale)
+    return (ops.chan_to_nchw(ops.Chan.whole(dx), n, h, w),
+            ops.chan_to_nchw(ops.Chan.whole(dlg), n, h, w),
+            dx.new_empty(0) if docc is None else docc.view(n, 1, h, w))
+
+
+@convex_upsample_backward.register_fake
+def _(g_flow, g_occ, flow, logits, occ, logit_scale, value_scale):
+    n, _, h, w = flow.shape
+    return flow.new_empty(n, 2, h, w), flow.new_empty(n, logits.shape[1], h, w), \
+        (flow.new_empty(0) if occ is None else flow.new_empty(n, 1, h, w))
+
+
+def _convex_upsample_backward(ctx, g_flow, g_occ):
+    flow, logits, *rest = ctx.saved_tensors
+    occ = rest[0] if rest else None
+    logit_scale, value_scale = ctx.scales
+    dflow, dlogits, docc = convex_upsample_backward(g_flow, None if occ is None else g_occ, flow,
+                                                    logits, occ, logit_scale, value_scale)
+    return dflow, dlogits, (None if occ is None else docc), None, None
+
+
+convex_upsample.register_autograd(_convex_upsample_backward, setup_context=_convex_upsample_setup)

@@ -722,6 +722,52 @@ def convex_upsample(logits: Chan, lr: Tensor, delta: Optional[Tensor], occ: Opti
             n, h, w, scale, grid_side, float(logit_scale), float(value_scale))
 
 
+def convex_upsample_backward(logits: Chan, x: Tensor, occ: Optional[Tensor], g_flow: Tensor,
+                             g_occ: Optional[Tensor], n: int, h: int, w: int,
+                             dlogits: Optional[Chan] = None, logit_scale: float = 0.25,
+                             value_scale: float = 8.0, scale: int = 8, grid_side: int = 3
+                             ) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+    """The adjoint of ``convex_upsample`` (scflow_convex_upsample_bwd): ``logits`` channels-last
+    [n·h·w, 576] (a ``Chan``), ``x`` [n·h·w, 2] the flow that was upsampled, ``occ`` [n·h·w, 1] or
+    None, ``g_flow`` [n, 2, 8h, 8w] and ``g_occ`` [n, 1, 8h, 8w] (or None: a zero gradient) →
+    (dlogits [n·h·w, 576] — or the buffer of the given ``Chan``, whose other channels are left
+    alone —, dx [n·h·w, 2], docc [n·h·w, 1] or None without ``occ``).  Bitwise reproducible."""
+    _require(logits.buf, "logits")
+    _require(x, "flow")
+    _require(g_flow, "g_flow")
+    m = n * h * w
+    taps = grid_side * grid_side * scale * scale
+    if logits.c != taps:
+        raise ValueError(f"convex upsampling expects {taps} logit channels, got {logits.c}")
+    if logits.buf.numel() < m * logits.stride or x.numel() != 2 * m or \
+            (occ is not None and occ.numel() != m):
+        raise ValueError("convex_upsample_backward: inputs do not have n·h·w pixels")
+    if tuple(g_flow.shape) != (n, 2, scale * h, scale * w) or \
+            (g_occ is not None and tuple(g_occ.shape) != (n, 1, scale * h, scale * w)):
+        raise ValueError("convex_upsample_backward: gradients must be [n, 2, 8h, 8w] and "
+                         "[n, 1, 8h, 8w]")
+    if g_occ is not None and occ is None:
+        raise ValueError("convex_upsample_backward: g_occ without occ")
+    if occ is not None:
+        _require(occ, "occlusion")
+    if g_occ is not None:
+        _require(g_occ, "g_occ")
+    if dlogits is None:
+        dlogits = Chan.whole(torch.empty(m, taps, device=x.device, dtype=torch.float32))
+    else:
+        _require(dlogits.buf, "dlogits")
+        if dlogits.c != taps or dlogits.buf.numel() < m * dlogits.stride:
+            raise ValueError(f"convex_upsample_backward: dlogits must be {taps} channels of an "
+                             "n·h·w-pixel buffer")
+    dx = torch.empty(m, 2, device=x.device, dtype=torch.float32)
+    docc = None if occ is None else torch.empty(m, 1, device=x.device, dtype=torch.float32)
+    ws = torch.empty(m * grid_side * grid_side * 3, device=x.device, dtype=torch.float32)
+    _launch("scflow_convex_upsample_bwd", x, logits.ptr, logits.stride, _p(x), _p(occ), _p(g_flow),
+            _p(g_occ), dlogits.ptr, dlogits.stride, _p(dx), _p(docc), _p(ws), ws.numel() * 4, n, h, w,
+            scale, grid_side, float(logit_scale), float(value_scale))
+    return dlogits.buf, dx, docc
+
+
 def flow_add(lr: Tensor, delta: Tensor, out0: Chan, n: int, h: int, w: int,
              out1: Optional[Chan] = None) -> None:
     """out0 (and out1) ← lr + delta, channels-last [n·h·w, 2] (scflow_flow_add)."""

@@ -13,11 +13,18 @@ the decoder's channels-last GRU working buffer, and the decoder runs with that b
 the decoder's lists (``upflow_preds``; with the mask decoder ``(upflow_preds,
 upocclusion_preds)``).
 
-Not covered: ``solve_pose`` / PnP (needs cv2), ``loss`` and the data formatting
-(``forward_single_view``, ``format_data_*``) — ``forward`` is ``get_flow``.
+``loss(batch)`` is the reference's training loss (``SequenceLoss(RAFTLoss)`` on the ×8 flows plus,
+with the mask decoder, ``SequenceLoss(L1Loss)`` on the ×8 occlusions) on the HIP autograd
+Functions, convex upsampling included (``scflow_convex_upsample_bwd``); ``train.step.TrainStep``
+takes these refiners.  The inference paths above stay under ``torch.no_grad()``.
+
+Not covered: ``solve_pose`` / PnP (needs cv2), the data formatting (``forward_single_view``,
+``format_data_*``: ``loss`` takes an already formatted batch), ``filter_invalid_flow_by_depth``
+and graph-mode training — ``forward`` is ``get_flow``.
 """
 from __future__ import annotations
 
+from collections import OrderedDict
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -114,6 +121,36 @@ class _RAFTFlowRefiner(nn.Module):
 
     def forward(self, *args, **kwargs):
         return self.get_flow(*args, **kwargs)
+
+    def loss(self, batch):
+        """raft_refiner_flow_mask.py:167-220 / raft_refiner_flow.py ``loss`` on an already
+        formatted batch (the keys of ``synthetic.make_train_batch``): the training forward on the
+        HIP autograd Functions (train/model.py ``raft_refiner_train_forward``) → ``(loss, None,
+        log_vars)`` with the reference's ``log_vars`` keys (``seq_{i}_flow_loss``,
+        ``seq_{i}_occ_loss``, ``loss_occ``, ``loss_flow``, ``loss``), fetched with one host
+        synchronisation.  ``loss`` carries the autograd graph.  RAFTRefinerFlow has no occlusion
+        terms (see ``raft_refiner_train_forward`` on the reference's own ``loss``)."""
+        from .train.model import raft_loss_terms, raft_refiner_train_forward
+        raft_loss_terms(self)  # configuration refusals come first
+        if batch["render_images"].device.type != "cuda":
+            raise ScflowError(f"{type(self).__name__}.loss runs on the gfx950 HIP kernels only "
+                              "(no CPU fallback)")
+        res = raft_refiner_train_forward(self, batch)
+        seq_f, seq_o = res["seq_flow_losses"], res["seq_occ_losses"]
+        names, vals = [], []
+        for i, f in enumerate(seq_f):
+            names.append(f"seq_{i}_flow_loss")
+            vals.append(f)
+            if seq_o:
+                names.append(f"seq_{i}_occ_loss")
+                vals.append(seq_o[i])
+        if seq_o:
+            names.append("loss_occ")
+            vals.append(res["loss_occ"])
+        names += ["loss_flow", "loss"]
+        vals += [res["loss_flow"], res["loss"]]
+        host = torch.stack([v.detach().reshape(()) for v in vals]).tolist()  # the one sync
+        return res["loss"], None, OrderedDict(zip(names, host))
 
     # ------------------------------------------------------------------ fused path
     def _get_flow(self, render, real, init_flow):

@@ -1186,6 +1186,50 @@ def upsample_bilinear_ac(x: Tensor, scale: int) -> Tensor:
     return _UpsampleAC.apply(x, scale)
 
 
+class _ConvexUpsample(torch.autograd.Function):
+    """RAFT's convex ×8 upsampling of the flow (and the occlusion, with the same weights):
+    scflow_convex_upsample forward, scflow_convex_upsample_bwd backward.  Only the inputs are
+    saved; the backward recomputes the softmax from the logits."""
+
+    @staticmethod
+    def forward(ctx, x, logits, occ, logit_scale, value_scale):
+        n, h, w, _ = x.shape
+        m = n * h * w
+        x = x.contiguous().view(m, 2)
+        logits = logits.contiguous().view(m, -1)
+        oc = None if occ is None else occ.contiguous().view(m, 1)
+        flow_up = torch.empty(n, 2, 8 * h, 8 * w, device=x.device, dtype=torch.float32)
+        occ_up = None if oc is None else torch.empty(n, 1, 8 * h, 8 * w, device=x.device,
+                                                     dtype=torch.float32)
+        ops.convex_upsample(Chan.whole(logits), x, None, oc, n, h, w, flow_up, occ_up,
+                            logit_scale=logit_scale, value_scale=value_scale)
+        ctx.save_for_backward(x, logits, *(() if oc is None else (oc,)))
+        ctx.cfg = (n, h, w, logit_scale, value_scale)
+        if occ_up is None:
+            return flow_up, None
+        return flow_up, occ_up
+
+    @staticmethod
+    def backward(ctx, g_flow, g_occ):
+        x, logits, *rest = ctx.saved_tensors
+        oc = rest[0] if rest else None
+        n, h, w, logit_scale, value_scale = ctx.cfg
+        dlogits, dx, docc = ops.convex_upsample_backward(
+            Chan.whole(logits), x, oc, g_flow.contiguous(),
+            None if oc is None else g_occ.contiguous(), n, h, w,
+            logit_scale=logit_scale, value_scale=value_scale)
+        return (dx.view(n, h, w, 2), dlogits.view(n, h, w, -1),
+                None if docc is None else docc.view(n, h, w, 1), None, None)
+
+
+def convex_upsample(x_nhwc: Tensor, logits_nhwc: Tensor, occ_nhwc: Optional[Tensor] = None,
+                    logit_scale: float = .25, value_scale: float = 8.) -> Tuple[Tensor, Optional[Tensor]]:
+    """Channels-last flow [N, h, w, 2], raw mask logits [N, h, w, 576] and occlusion [N, h, w, 1]
+    (or None) → (value_scale · ×8 flow [N, 2, 8h, 8w], ×8 occlusion [N, 1, 8h, 8w] or None), both
+    NCHW as the losses take them; differentiable w.r.t. all three (gradients channels-last)."""
+    return _ConvexUpsample.apply(x_nhwc, logits_nhwc, occ_nhwc, float(logit_scale), float(value_scale))
+
+
 # ------------------------------------------------------------------------------- group norm
 class _GroupNormNHWC(torch.autograd.Function):
     """GroupNorm (+ReLU) on channels-last data, 4 channels per group (the pose head's GN(32) on

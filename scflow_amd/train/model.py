@@ -10,11 +10,19 @@ HIP Functions; the detached per-iteration geometry (2D-3D lift, pose-induced flo
 downsampling, GT flow) runs on the inference kernels without autograd.  Normalisations,
 activations, the GRU gate algebra, the pose update and the losses are torch ops (pointwise /
 per-sample); FCs are plain library GEMMs.
+
+``raft_refiner_train_forward`` does the same for the reference's RAFT + PnP baseline
+(``RAFTRefinerFlowMask.loss`` / ``RAFTRefinerFlow.loss``, models/refiner/
+raft_refiner_flow_mask.py:167-220) on the same pieces: ``raft_decoder_train`` restates the RAFT
+decoders' loop (flow detached every iteration, occlusion head, raw mask logits) and upsamples
+through ``convex_upsample`` (scflow_convex_upsample forward, scflow_convex_upsample_bwd backward);
+the flow and occlusion sequence losses are the torch restatements of losses.py with the weights
+of the refiner's stored loss configs.
 """
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -22,11 +30,12 @@ import torch.nn.functional as F
 from .. import ops
 from ..ops import Chan
 from .functions import (ResidualGrad, batch_norm_nhwc, begin_forward, bn_fusable, conv2d_nhwc,
-                        conv2d_nhwc_split, corr_lookup, corr_pyramid, dual_conv2d_nhwc,
-                        group_norm_nhwc, gru_step, instance_norm_nhwc,
+                        conv2d_nhwc_split, convex_upsample, corr_lookup, corr_pyramid,
+                        dual_conv2d_nhwc, group_norm_nhwc, gru_step, instance_norm_nhwc,
                         instance_norm_residual_relu_nhwc, linear, pose_update6, share_weight,
                         upsample_bilinear_ac)
-from .losses import LowRes, filter_flow_by_mask, matmul3, refine_losses
+from .losses import (LowRes, filter_flow_by_mask, flow_l1_loss, flow_valid, mask_l1_loss, matmul3,
+                     refine_losses, sequence_loss)
 
 Tensor = torch.Tensor
 _GRU_FUSED = os.environ.get("SCFLOW_TRAIN_GRU_FUSED", "1") != "0"  # A/B switch (tuning)
@@ -185,6 +194,38 @@ def check_train_flags(dec) -> None:
                                   "implemented")
 
 
+def _hoist_context(gru, cxt: Tensor, hc: int, cc: int):
+    """The loop-invariant context contribution of every GRU conv, once per forward (its gradient
+    is the sum over the iterations, so dgrad/wgrad of the context part also run once).  Returns
+    (per-conv (w_zr, w_q, padding) without the context's input channels, per-conv (z|r, q)
+    pre-activation maps)."""
+    it_w, ctx_pre = [], []
+    for zc, rc, qc in zip(gru.conv_z, gru.conv_r, gru.conv_q):
+        z, rr, q = zc.conv, rc.conv, qc.conv
+        wzr = torch.cat([z.weight, rr.weight], 0)
+        bzr = torch.cat([z.bias, rr.bias], 0)
+        ctx_pre.append((conv2d_nhwc(cxt, wzr[:, hc:hc + cc], bzr, 1, q.padding),
+                        conv2d_nhwc(cxt, q.weight[:, hc:hc + cc], q.bias, 1, q.padding)))
+        w_zr = torch.cat([wzr[:, :hc], wzr[:, hc + cc:]], 1)
+        w_q = torch.cat([q.weight[:, :hc], q.weight[:, hc + cc:]], 1)
+        if _GRU_FUSED:  # one batched weight gradient over the iterations' uses
+            w_zr, w_q = share_weight(w_zr), share_weight(w_q)
+        it_w.append((w_zr, w_q, q.padding))
+    return it_w, ctx_pre
+
+
+def _gru_iteration(h: Tensor, motion: Tensor, it_w, ctx_pre, hc: int) -> Tensor:
+    for (w_zr, w_q, pad), (pre_zr, pre_q) in zip(it_w, ctx_pre):  # SeqConv: 1×5 then 5×1
+        if _GRU_FUSED:
+            h = gru_step(h, motion, w_zr, w_q, pre_zr, pre_q, pad)  # (1 − z)·h + z·q
+        else:  # the same step as separate autograd ops (A/B reference)
+            z, rg = conv2d_nhwc_split(h, w_zr, hc, None, 1, pad, act="Sigmoid", x1=motion,
+                                      bias_map=pre_zr)
+            qq = conv2d_nhwc(rg * h, w_q, None, 1, pad, act="Tanh", x1=motion, bias_map=pre_q)
+            h = torch.lerp(h, qq, z)
+    return h
+
+
 def decoder_train(dec, feat_render: Tensor, feat_real: Tensor, h: Tensor, cxt: Tensor, R0: Tensor,
                   t0: Tensor, depth: Tensor, K: Tensor, label: Tensor, iters: int,
                   invalid_flow_num: float = 0.0) -> Tuple[List[Tensor], ...]:
@@ -209,20 +250,7 @@ def decoder_train(dec, feat_render: Tensor, feat_real: Tensor, h: Tensor, cxt: T
     enc = dec.encoder
     gru = dec.gru
     hc, cc = dec.h_channels, dec.cxt_channels
-    # loop-invariant context contribution of every GRU conv, once per forward (its gradient is
-    # the sum over the iterations, so dgrad/wgrad of the context part also run once)
-    it_w, ctx_pre = [], []
-    for zc, rc, qc in zip(gru.conv_z, gru.conv_r, gru.conv_q):
-        z, rr, q = zc.conv, rc.conv, qc.conv
-        wzr = torch.cat([z.weight, rr.weight], 0)
-        bzr = torch.cat([z.bias, rr.bias], 0)
-        ctx_pre.append((conv2d_nhwc(cxt, wzr[:, hc:hc + cc], bzr, 1, q.padding),
-                        conv2d_nhwc(cxt, q.weight[:, hc:hc + cc], q.bias, 1, q.padding)))
-        w_zr = torch.cat([wzr[:, :hc], wzr[:, hc + cc:]], 1)
-        w_q = torch.cat([q.weight[:, :hc], q.weight[:, hc + cc:]], 1)
-        if _GRU_FUSED:  # one batched weight gradient over the 8 iterations' uses
-            w_zr, w_q = share_weight(w_zr), share_weight(w_q)
-        it_w.append((w_zr, w_q, q.padding))
+    it_w, ctx_pre = _hoist_context(gru, cxt, hc, cc)
     fl, ml = dec.flow_pred.layers, dec.mask_pred.layers
     heads_fused = (_HEADS_FUSED and len(fl) == 1 and len(ml) == 1 and h.is_cuda
                    and fl[0].conv.kernel_size == ml[0].conv.kernel_size
@@ -259,14 +287,7 @@ def decoder_train(dec, feat_render: Tensor, feat_real: Tensor, h: Tensor, cxt: T
         for m in enc.out_net[1:]:
             out = _cm(out, m)
         motion = torch.cat([out, f2m], -1)
-        for (w_zr, w_q, pad), (pre_zr, pre_q) in zip(it_w, ctx_pre):  # SeqConv: 1×5 then 5×1
-            if _GRU_FUSED:
-                h = gru_step(h, motion, w_zr, w_q, pre_zr, pre_q, pad)  # (1 − z)·h + z·q
-            else:  # the same step as separate autograd ops (A/B reference)
-                z, rg = conv2d_nhwc_split(h, w_zr, hc, None, 1, pad, act="Sigmoid", x1=motion,
-                                          bias_map=pre_zr)
-                qq = conv2d_nhwc(rg * h, w_q, None, 1, pad, act="Tanh", x1=motion, bias_map=pre_q)
-                h = torch.lerp(h, qq, z)
+        h = _gru_iteration(h, motion, it_w, ctx_pre, hc)
         fl, ml = dec.flow_pred.layers, dec.mask_pred.layers
         if heads_fused:  # both XHeads' hidden convs as one launch each way
             fh, mh = dual_conv2d_nhwc(h, fl[0].conv.weight, fl[0].conv.bias, ml[0].conv.weight,
@@ -348,3 +369,174 @@ def refiner_train_forward(refiner, batch: Dict[str, Tensor], model_points: Seque
                                gt_flow, render_mask, batch["label"], model_points, diameters,
                                refiner.max_flow)
     return dict(loss=lp + lf + lm, loss_pose=lp, loss_flow=lf, loss_mask=lm, outs=outs, gt_flow=gt_flow)
+
+
+# ------------------------------------------------------------------------------- RAFT baseline
+def _hidden_heads(h: Tensor, heads) -> List[Tensor]:
+    """The XHeads' hidden ConvModules on the GRU state; the first two as one launch each way where
+    ``dual_conv2d_nhwc`` allows (one 3×3 layer each, same shape and activation)."""
+    def fusable(a, b):
+        la, lb = a.layers, b.layers
+        return (_HEADS_FUSED and h.is_cuda and len(la) == 1 and len(lb) == 1
+                and la[0].conv.kernel_size == lb[0].conv.kernel_size
+                and la[0].conv.padding == lb[0].conv.padding and la[0].conv.stride == (1, 1)
+                and lb[0].conv.stride == (1, 1) and la[0].act_type == lb[0].act_type
+                and (la[0].conv.bias is None) == (lb[0].conv.bias is None))
+    outs, rest = [], list(heads)
+    if len(rest) >= 2 and fusable(rest[0], rest[1]):
+        a, b = rest[0].layers[0], rest[1].layers[0]
+        outs += list(dual_conv2d_nhwc(h, a.conv.weight, a.conv.bias, b.conv.weight, b.conv.bias,
+                                      a.conv.padding, a.act_type))
+        rest = rest[2:]
+    for hd in rest:
+        x = h
+        for m in hd.layers:
+            x = _cm(x, m)
+        outs.append(x)
+    return outs
+
+
+def raft_decoder_train(dec, feat_render: Tensor, feat_real: Tensor, h: Tensor, cxt: Tensor,
+                       iters: int, init_flow: Tensor = None
+                       ) -> Tuple[List[Tensor], List[Tensor], List[Tensor]]:
+    """RAFTDecoder.forward (raft_decoder.py:418-457) / RAFTDecoderMask.forward
+    (raft_decoder_mask.py:163-208) with autograd; features, h, cxt and ``init_flow`` channels-last
+    [N, h, w, C].  Returns (×8 flows [N, 2, 8h, 8w], ×8 occlusions [N, 1, 8h, 8w] — empty without
+    the occlusion head —, low-resolution flows [N, h, w, 2] after every iteration).  The flow is
+    detached at the top of every iteration, so its only gradient path is flow + Δflow → the
+    upsampling."""
+    if not dec.corr_lookup.align_corners:
+        raise NotImplementedError("RAFT training: corr_lookup align_corners=True only")
+    N, hh, ww, _ = feat_render.shape
+    L, r = dec.num_levels, dec.radius
+    scale = 2 ** (L - 1)
+    convex = bool(dec.convex_upsample_flow)
+    with_occ = hasattr(dec, "occlusion_pred")
+    if convex and (scale != 8 or 2 * r + 1 != 9):
+        raise NotImplementedError("convex upsampling: scale 8 (num_levels 4) and a 3×3 "
+                                  "neighbourhood (radius 4) only")
+    pyr = corr_pyramid(feat_render.permute(0, 3, 1, 2), feat_real.permute(0, 3, 1, 2), L)
+    enc = dec.encoder
+    hc, cc = dec.h_channels, dec.cxt_channels
+    it_w, ctx_pre = _hoist_context(dec.gru, cxt, hc, cc)
+    heads = [dec.flow_pred] + ([dec.mask_pred] if convex else []) + \
+        ([dec.occlusion_pred] if with_occ else [])
+    flow = init_flow if init_flow is not None else feat_render.new_zeros(N, hh, ww, 2)
+    upflows, upoccs, lr_flows = [], [], []
+    for _ in range(iters):
+        flow = flow.detach()
+        corr = corr_lookup(pyr, flow, N, hh, ww, L, r)
+        c = corr
+        for m in enc.corr_net:
+            c = _cm(c, m)
+        f = flow
+        for m in enc.flow_net:
+            f = _cm(f, m)
+        out = _cm(c, enc.out_net[0], x1=f)
+        for m in enc.out_net[1:]:
+            out = _cm(out, m)
+        h = _gru_iteration(h, torch.cat([out, flow], -1), it_w, ctx_pre, hc)
+        hid = _hidden_heads(h, heads)
+        flow = flow + _conv(hid[0], dec.flow_pred.predict_layer)
+        lr_flows.append(flow)
+        occ = None
+        if with_occ:  # 1×1 predictor, then the sigmoid (raft_decoder_mask.py:192-193)
+            pl = dec.occlusion_pred.predict_layer
+            occ = conv2d_nhwc(hid[-1], pl.weight, pl.bias, 1, pl.padding, act="Sigmoid")
+        if convex:  # raw logits; the reference's `.25 *` is the op's logit_scale
+            logits = _conv(hid[1], dec.mask_pred.predict_layer)
+            up, upo = convex_upsample(flow, logits, occ, 0.25, float(scale))
+        else:  # the reference's `mask is None` branch: bilinear, the occlusion unscaled
+            up = scale * upsample_bilinear_ac(flow.permute(0, 3, 1, 2), scale)
+            upo = None if occ is None else upsample_bilinear_ac(occ.permute(0, 3, 1, 2), scale)
+        upflows.append(up)
+        if upo is not None:
+            upoccs.append(upo)
+    return upflows, upoccs, lr_flows
+
+
+def _sequence_loss_cfg(cfg, func: str, what: str) -> Dict[str, float]:
+    """gamma / loss_weight / max_flow of a ``SequenceLoss`` over ``func`` (models/loss/
+    sequence_loss.py), the reference's defaults filled in; anything else is refused."""
+    if not isinstance(cfg, dict) or cfg.get("type") != "SequenceLoss":
+        raise NotImplementedError(f"RAFT training: {what} must be a SequenceLoss config, got {cfg!r}")
+    fc = cfg.get("loss_func_cfg")
+    if not isinstance(fc, dict) or fc.get("type") != func:
+        raise NotImplementedError(f"RAFT training: {what} must wrap {func}, got {fc!r}")
+    known = {"type", "loss_weight", "eps"} | ({"max_flow"} if func == "RAFTLoss" else set())
+    if set(fc) - known or set(cfg) - {"type", "gamma", "loss_func_cfg"}:
+        raise NotImplementedError(f"RAFT training: unknown keys in {what}: {cfg!r}")
+    return dict(gamma=float(cfg.get("gamma", 0.8)), weight=float(fc.get("loss_weight", 1.0)),
+                max_flow=float(fc.get("max_flow", 400)), eps=float(fc.get("eps", 1e-10)))
+
+
+def raft_loss_terms(refiner) -> Tuple[Dict[str, float], Optional[Dict[str, float]]]:
+    """(flow loss terms, occlusion loss terms or None) from the refiner's stored loss configs:
+    ``flow_loss_cfg`` + ``occlusion_loss_cfg`` (RAFTRefinerFlowMask) or ``loss_cfg``
+    (RAFTRefinerFlow).  Raises NotImplementedError for what the training path does not restate."""
+    if getattr(refiner, "filter_invalid_flow_by_depth", False):
+        raise NotImplementedError("RAFT training: filter_invalid_flow_by_depth is not supported "
+                                  "(it needs the GT pose's rendered depth)")
+    if hasattr(refiner, "flow_loss_cfg"):
+        return (_sequence_loss_cfg(refiner.flow_loss_cfg, "RAFTLoss", "flow_loss_cfg"),
+                _sequence_loss_cfg(refiner.occlusion_loss_cfg, "L1Loss", "occlusion_loss_cfg"))
+    return _sequence_loss_cfg(refiner.loss_cfg, "RAFTLoss", "loss_cfg"), None
+
+
+def raft_refiner_train_forward(refiner, batch: Dict[str, Tensor], iters: int = None
+                               ) -> Dict[str, Tensor]:
+    """Images → losses of the RAFT baseline, autograd graph attached: RAFTRefinerFlowMask.loss
+    (raft_refiner_flow_mask.py:167-220) — SequenceLoss(RAFTLoss) on the ×8 flows plus
+    SequenceLoss(L1Loss) on the ×8 occlusions against ``gt_flow.sum(1) < max_flow`` — and
+    RAFTRefinerFlow.loss.  The latter cannot run as the reference writes it (it unpacks
+    ``get_flow``'s list of flows into three names, raft_refiner_flow.py:184); its evident intent,
+    the flow sequence loss alone, is what runs here (loss_occ None, seq_occ_losses empty).
+    ``batch``: the keys of ``synthetic.make_train_batch`` (no label, model points or diameters are
+    needed).  Returns dict(loss, loss_flow, loss_occ, seq_flow_losses, seq_occ_losses, outs,
+    gt_flow); ``outs`` = raft_decoder_train's three lists."""
+    dec = refiner.decoder
+    f_cfg, o_cfg = raft_loss_terms(refiner)  # refusals before any device work
+    if (o_cfg is not None) != hasattr(dec, "occlusion_pred"):
+        raise NotImplementedError("RAFT training: an occlusion loss needs RAFTDecoderMask, and "
+                                  "RAFTDecoderMask an occlusion loss")
+    begin_forward()
+    iters = int(dec.iters if iters is None else iters)
+    real = batch["real_images"].permute(0, 2, 3, 1).contiguous()
+    render = batch["render_images"].permute(0, 2, 3, 1).contiguous()
+    N = real.shape[0]
+    dt = real.dtype
+    if refiner.real_encoder is refiner.render_encoder:  # shared: one batch of 2N images
+        feats = encoder_train(refiner.real_encoder, torch.cat([real, render], 0))
+        feat_real, feat_render = feats[:N], feats[N:]
+    else:
+        feat_real = encoder_train(refiner.real_encoder, real)
+        feat_render = encoder_train(refiner.render_encoder, render)
+    cx = encoder_train(refiner.context, render)
+    hc = refiner.h_channels
+    h, cxt = torch.tanh(cx[..., :hc]), torch.relu(cx[..., hc:])
+    outs = raft_decoder_train(dec, feat_render, feat_real, h, cxt, iters)
+    upflows, upoccs, _ = outs
+    max_flow = float(refiner.max_flow)
+    with torch.no_grad():  # GT flow: lift with the reference pose, project with the GT pose
+        depth = batch["depth"].contiguous().to(dt)
+        K = batch["internel_k"].contiguous().to(dt)
+        pts = ops.lift_points(depth, K, batch["ref_rotation"].contiguous().to(dt),
+                              batch["ref_translation"].contiguous().to(dt))
+        gt_flow = torch.empty(N, 2, *depth.shape[1:], device=depth.device, dtype=dt)
+        ops.pose_flow(batch["gt_rotation"].contiguous().to(dt), batch["gt_translation"].contiguous().to(dt),
+                      K, pts, max_flow, out=gt_flow)
+        if refiner.filter_invalid_flow_by_mask:
+            gt_flow = filter_flow_by_mask(gt_flow, batch["gt_masks"], max_flow)
+        render_mask = (depth > 0).to(dt)
+        v = flow_valid(gt_flow, render_mask, f_cfg["max_flow"])  # iteration-invariant
+        gt_occ = (gt_flow.sum(dim=1) < max_flow).to(dt)  # the reference's sum, not the magnitude
+    seq_f = [flow_l1_loss(f, gt_flow, render_mask, f_cfg["max_flow"], f_cfg["weight"], f_cfg["eps"], v=v)
+             for f in upflows]
+    loss_flow = sequence_loss(seq_f, f_cfg["gamma"])
+    seq_o, loss_occ, loss = [], None, loss_flow
+    if o_cfg is not None:
+        seq_o = [mask_l1_loss(o[:, 0], gt_occ, o_cfg["weight"]) for o in upoccs]
+        loss_occ = sequence_loss(seq_o, o_cfg["gamma"])
+        loss = loss_flow + loss_occ
+    return dict(loss=loss, loss_flow=loss_flow, loss_occ=loss_occ, seq_flow_losses=seq_f,
+                seq_occ_losses=seq_o, outs=outs, gt_flow=gt_flow)

@@ -23,7 +23,8 @@ import torch.distributed as dist
 
 from .._lib import bump_weights_generation
 from .functions import capture_cache, direct_weight_grads
-from .model import refiner_train_forward
+from ..raft_refiner import _RAFTFlowRefiner
+from .model import raft_loss_terms, raft_refiner_train_forward, refiner_train_forward
 from .schedule import OneCycleLR, reference_schedule
 
 Tensor = torch.Tensor
@@ -126,7 +127,13 @@ class TrainStep:
     float in eager mode.  ``lr_schedule``: "onecycle" (default: the configured OneCycleLR with
     ``eta_max = lr``, ``total_steps``, ``pct_start`` and linear annealing), a ``OneCycleLR``-like
     object with ``lr_at(step)``, or None for a constant ``lr``.  Every kernel of the forward + backward is one of ours (no vendor
-    GEMM: see functions.py), and eager steps and the capture run on the step's own stream."""
+    GEMM: see functions.py), and eager steps and the capture run on the step's own stream.
+
+    With a ``RAFTRefinerFlow`` / ``RAFTRefinerFlowMask`` the step runs
+    ``raft_refiner_train_forward`` (the baseline's flow and occlusion sequence losses; there is no
+    pose loss, so ``model_points`` and ``diameters`` may be None) in eager mode only. All
+    defaults stay SCFlow's: the reference's RAFT config (configs/refine_models/raft.py) clips at
+    ``max_norm=1.0``, which its caller passes."""
 
     def __init__(self, refiner, model_points: Sequence[Tensor], diameters: Sequence[float],
                  lr: float = 4e-4, weight_decay: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
@@ -134,6 +141,15 @@ class TrainStep:
                  group=None, overlap: bool = False, graph: bool = False,
                  lr_schedule="onecycle", total_steps: int = 100100, pct_start: float = 0.05) -> None:
         self.refiner = refiner
+        self.raft = isinstance(refiner, _RAFTFlowRefiner)
+        if self.raft:
+            if graph:
+                raise NotImplementedError("TrainStep(graph=True) with a RAFT refiner: graph-mode "
+                                          "training covers SCFlowRefiner only")
+            raft_loss_terms(refiner)  # an unsupported loss config fails here, not in step one
+            model_points, diameters = model_points or (), diameters or ()
+        elif model_points is None or diameters is None:
+            raise ValueError("TrainStep: SCFlowRefiner's pose loss needs model_points and diameters")
         self.graph = graph
         self._g = None
         self._g_opt = None
@@ -200,7 +216,10 @@ class TrainStep:
 
     def _fwd_bwd(self, batch: Dict[str, Tensor]) -> Dict[str, Tensor]:
         self.grads.zero()
-        out = refiner_train_forward(self.refiner, batch, self.model_points, self.diam_t, self.iters)
+        if self.raft:
+            out = raft_refiner_train_forward(self.refiner, batch, self.iters)
+        else:
+            out = refiner_train_forward(self.refiner, batch, self.model_points, self.diam_t, self.iters)
         # SCFLOW_TRAIN_MT_BACKWARD=0 runs backward on the calling thread (measured equal)
         with torch.autograd.set_multithreading_enabled(_MT_BACKWARD):
             if self.grads._hooks:  # per-parameter hooks must see every accumulation

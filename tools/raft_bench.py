@@ -1,13 +1,17 @@
 """Timing of the RAFT baseline decoders (RAFTDecoderMask, RAFTDecoder), interleaved in one process.
 
 usage: python tools/raft_bench.py [--batch 16] [--size 256] [--iters 12] [--rounds 7] [--steps 10]
-                                  [--json out.json] [--once KIND]
+                                  [--json out.json] [--once KIND] [--train]
 
 Each decoder is warmed up, then timed `rounds` times in round-robin order (`steps` forwards per
 round, a device synchronise at both ends); prints the median, minimum and maximum ms per forward
 of each and one JSON line with all of it.  It also prints the bytes the convex-upsampling launch
 moves per call (from the shapes: logits + flow, Δflow, occlusion in; ×8 flow / occlusion and the
 two next-flow destinations out), the figure a kernel trace's launch time is divided into.
+
+`--train` times one eager training step of RAFTRefinerFlowMask instead (`train.step.TrainStep`:
+forward, backward, gradient clipping at 1.0, AdamW; same defaults: B=16, 256², 12 iterations) and
+prints the median ms per step over the rounds and one JSON line.
 
 `--once KIND` runs `steps` forwards of one decoder and nothing else: the run to put under
 `rocprofv3 --kernel-trace --stats` (a run of its own; end-to-end numbers come from the untraced
@@ -44,8 +48,56 @@ def tail_bytes(batch, size, occlusion):
     return 4 * m * per_px
 
 
+def refiner_cfg(iters):
+    """The model block of the reference's configs/refine_models/raft.py (RAFTRefinerFlowMask)."""
+    enc = dict(type="RAFTEncoder", in_channels=3, out_channels=256, net_type="Basic")
+    seq = dict(type="SequenceLoss", gamma=0.8)
+    return dict(type="RAFTRefinerFlowMask", cxt_channels=128, h_channels=128, seperate_encoder=False,
+                max_flow=400., filter_invalid_flow_by_mask=True, filter_invalid_flow_by_depth=False,
+                encoder=dict(enc, norm_cfg=dict(type="IN")), cxt_encoder=dict(enc, norm_cfg=dict(type="BN")),
+                decoder=decoder_cfg(KINDS[0], iters),
+                flow_loss_cfg=dict(seq, loss_func_cfg=dict(type="RAFTLoss", loss_weight=1.0, max_flow=400.)),
+                occlusion_loss_cfg=dict(seq, loss_func_cfg=dict(type="L1Loss", loss_weight=100.)))
+
+
+def train(a):
+    """One eager training step of RAFTRefinerFlowMask (forward, backward, clip at 1.0, AdamW) on a
+    fixed synthetic batch: the median ms per step over `rounds` rounds of `steps` steps."""
+    import numpy as np
+    from scflow_amd import MODELS, synthetic
+    from scflow_amd.train.step import TrainStep
+    dev = torch.device("cuda")
+    r = MODELS.build(refiner_cfg(a.iters))
+    for i, m in enumerate((r.real_encoder, r.context, r.decoder)):
+        synthetic.fill_module_(m, seed=(1, 2, 0)[i])
+    with torch.no_grad():
+        r.decoder.mask_pred.predict_layer.weight.mul_(32.0)
+    r = r.to(dev)
+    batch = {}
+    for k, v in synthetic.make_train_batch(a.batch, a.size, seed=0).items():
+        x = torch.from_numpy(np.ascontiguousarray(v))
+        batch[k] = (x.float() if x.is_floating_point() else x).to(dev)
+    step = TrainStep(r, None, None, max_norm=1.0)
+    losses = [float(step(batch)["loss"]) for _ in range(3)]  # warm-up (packing, allocator)
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(a.rounds):
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            out = step(batch)
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) / a.steps * 1e3)
+    res = dict(mode="train", kind="RAFTRefinerFlowMask", batch=a.batch, size=a.size, iters=a.iters,
+               rounds=a.rounds, steps=a.steps, median_ms=statistics.median(times), min_ms=min(times),
+               max_ms=max(times), warmup_losses=losses, last_loss=float(out["loss"]))
+    print(f"RAFTRefinerFlowMask training step: median {res['median_ms']:.2f} ms/step "
+          f"(min {min(times):.2f}, max {max(times):.2f}); B={a.batch}, {a.size}², {a.iters} iterations")
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--train", action="store_true")
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--iters", type=int, default=12)
@@ -56,6 +108,14 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("raft_bench.py needs a GPU (a CPU run measures nothing)")
+    if a.train:
+        line = json.dumps(train(a))
+        print(line)
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, "w") as f:
+                f.write(line + "\n")
+        return
     from scflow_amd import MODELS, synthetic
     dev = torch.device("cuda")
     raw = synthetic.make_decoder_inputs(a.batch, a.size, seed=0)
