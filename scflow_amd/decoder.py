@@ -19,6 +19,11 @@ Forward, per call (B pairs, features h×w = image/8, M = B·h·w):
 
 No host synchronisation happens inside ``forward``; the whole call can be captured into a
 HIP graph (``graph.py``).  There is no CPU path: inputs must be on a ROCm device.
+
+The constructor's common part and the iteration up to the GRU (pyramid, ``HX``, a2–a4, the
+recorded segments, the tiled / fused-lookup planning) live in ``recurrent.py``, shared with the
+RAFT decoders; this file holds what follows the GRU (a5–a11), the streams, events, ping-pong and
+kernel-timer hooks.
 """
 from __future__ import annotations
 
@@ -30,9 +35,9 @@ import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import ScflowError
-from .modules import (ConvGRU, ConvModule, ConvRunner, CorrelationPyramid, CorrLookup,
-                      MotionEncoder, XHead, run_chain, run_chain_pair)
+from .modules import ConvModule, ConvRunner, XHead, run_chain, run_chain_pair
 from .ops import Chan
+from .recurrent import RecurrentCore, _RecurrentDecoder
 from .registry import MODELS
 
 Tensor = torch.Tensor
@@ -53,24 +58,15 @@ def _record_on(out, stream) -> None:
 
 
 @MODELS.register_module()
-class SCFlowDecoder(nn.Module):
-    _h_channels = {"Basic": 128, "Small": 96}
-    _cxt_channels = {"Basic": 128, "Small": 64}
-
+class SCFlowDecoder(_RecurrentDecoder):
     def __init__(self, net_type: str, num_levels: int, radius: int, iters: int, detach_flow: bool,
                  detach_mask: bool, detach_pose: bool, mask_flow: bool, mask_corr: bool,
                  pose_head_cfg: dict, depth_transform: str = "exp", detach_depth_for_xy: bool = False,
                  corr_lookup_cfg: dict = dict(align_corners=True), gru_type: str = "SeqConv",
                  feat_channels: Union[int, Sequence[int]] = 256, conv_cfg: Optional[dict] = None,
                  norm_cfg: Optional[dict] = None, act_cfg: Optional[dict] = None) -> None:
-        super().__init__()
-        assert net_type in ["Basic", "Small"]
-        assert type(feat_channels) in (int, tuple, list)
-        self.corr_block = CorrelationPyramid(num_levels=num_levels)
-        feat_channels = list(feat_channels) if isinstance(feat_channels, (tuple, list)) else [feat_channels]
-        self.net_type = net_type
-        self.num_levels = num_levels
-        self.radius = radius
+        super().__init__(net_type, num_levels, radius, iters, corr_lookup_cfg, gru_type,
+                         feat_channels, conv_cfg, norm_cfg, act_cfg)
         self.detach_flow = detach_flow
         self.detach_mask = detach_mask
         self.detach_pose = detach_pose
@@ -78,32 +74,20 @@ class SCFlowDecoder(nn.Module):
         self.mask_flow = mask_flow
         self.mask_corr = mask_corr
         self.depth_transform = depth_transform
-        self.h_channels = self._h_channels.get(net_type)
-        self.cxt_channels = self._cxt_channels.get(net_type)
-        self.iters = iters
-        corr_lookup_cfg = dict(corr_lookup_cfg)
-        corr_lookup_cfg["radius"] = radius
-        self.corr_lookup = CorrLookup(**corr_lookup_cfg)
-        self.encoder = MotionEncoder(num_levels=num_levels, radius=radius, net_type=net_type,
-                                     conv_cfg=conv_cfg, norm_cfg=norm_cfg, act_cfg=act_cfg)
-        self.gru_type = gru_type
-        self.gru = ConvGRU(self.h_channels, self.encoder.out_channels[0] + 2 + self.cxt_channels,
-                           net_type=gru_type)
         self.pose_pred = MODELS.build(pose_head_cfg)
-        self.flow_pred = XHead(self.h_channels, feat_channels, 2, x="flow")
-        self.mask_pred = XHead(self.h_channels, feat_channels, 1, x="mask")
+        self.flow_pred = XHead(self.h_channels, self.feat_channels, 2, x="flow")
+        self.mask_pred = XHead(self.h_channels, self.feat_channels, 1, x="mask")
         mk = dict(conv_cfg=conv_cfg, norm_cfg=norm_cfg, act_cfg=act_cfg)
         self.delta_flow_encoder = nn.Sequential(
             ConvModule(2, 128, 7, padding=3, **mk), ConvModule(128, 64, 3, padding=1, **mk))
         self.mask_encoder = nn.Sequential(
             ConvModule(1, 64, 3, padding=1, **mk), ConvModule(64, 32, 3, padding=1, **mk))
-        self._head_runner = None
         # optional per-kernel timing hooks (bench.py): name -> callable(start: bool)
         # name -> callable(start: bool) bracketing one launch (bench.py's live kernel timing):
         # gru_zr, gru_q, corr_pyramid, corr_lookup, pose_flow
         self.kernel_hooks: Dict[str, object] = {}
-        # compute the context features' (loop-invariant) GRU contribution once per forward
-        self.hoist_context = True
+        # (hoist_context, tiled_pyramid, fuse_lookup_conv and fuse_lookup_conv_max_px: the shared
+        # core's knobs, recurrent.py)
         # independent branches on a second HIP stream (else everything on the current stream)
         self.side_stream = True
         # the tail's flow-predictor / mask-predictor branches as paired launches on the main
@@ -121,13 +105,6 @@ class SCFlowDecoder(nn.Module):
         # the iteration's tail (pose update, pose flow, ×8 prediction, next ↓8 flow) as one
         # launch (scflow_pose_step; under mask_flow scflow_pose_step_masked)
         self.fuse_tail = True
-        # the lookup and corr_net.0 (1×1 324→256) as ONE launch (scflow_corr_lookup_conv1x1: the
-        # correlation features stay in LDS) when the geometry allows (tiled pyramid, L = 4, r = 4)
-        # and the feature map has at most 32×32 pixels: measured 5.112 vs 5.131 ms/forward at
-        # configs[1] (round 5, tools/sess_r5d.sh), but 49.2 vs 48.0 ms at configs[4] (64×64),
-        # where the separate lookup (tile-row regions) and 1×1 conv win
-        self.fuse_lookup_conv = True
-        self.fuse_lookup_conv_max_px = 32 * 32
         # a batch of ≥ 2·pingpong_min pairs runs as two interleaved halves (_forward_pingpong).
         # Off: measured slower at B=16 (5.76 vs 5.33 ms/step) — a half's tail kernels do not get
         # CUs while the other half's convolutions hold every CU's LDS, so they serialise anyway
@@ -145,9 +122,6 @@ class SCFlowDecoder(nn.Module):
         # the deferred full-resolution part reads the pose the ↓8 part wrote instead of
         # recomputing the update per workgroup (ops.pose_step_given); SCFLOW_FULLRES_GIVEN=0: off
         self.fullres_given = os.environ.get("SCFLOW_FULLRES_GIVEN", "1") != "0"
-        # correlation pyramid in the tiled layout (4×4 tiles of 16 floats per map, pooling fused
-        # into the GEMM epilogue; ops.corr_pyramid_tiled) when the geometry allows it
-        self.tiled_pyramid = True
         # 0: every stream at the default priority; 1: the forward's critical stream is a
         # high-priority stream of the decoder's own (the side branches at the default), so the
         # CP dispatches its workgroups first when both queues hold work; 2: the side branches'
@@ -162,13 +136,7 @@ class SCFlowDecoder(nn.Module):
     # ------------------------------------------------------------------ helpers
     def _hidden_heads(self):
         """Both XHeads' first hidden conv as one launch when they have the same shape."""
-        fl, ml = self.flow_pred.layers, self.mask_pred.layers
-        if len(fl) == 1 and len(ml) == 1 and fl[0].conv.kernel_size == ml[0].conv.kernel_size \
-                and fl[0].conv.padding == ml[0].conv.padding:
-            if self._head_runner is None:
-                self._head_runner = ConvRunner([fl[0].conv, ml[0].conv], "ReLU")
-            return self._head_runner
-        return None
+        return super()._hidden_heads((("flow", self.flow_pred), ("mask", self.mask_pred)))
 
     def _xhead_pred_plan(self, head_runner, hid, HEAD, N, h, w, dev):
         """(hidden conv args, packed predictor weights, workspace, flow bias, mask bias) for
@@ -195,19 +163,6 @@ class SCFlowDecoder(nn.Module):
         fb = None if fp.bias is None else fp.bias.detach()
         mb = None if mp.bias is None else mp.bias.detach()
         return hargs, self._xpred_w, ws, fb, mb, fh
-
-    @property
-    def last_plan(self) -> Optional[dict]:
-        """The schedule the last forward took (read-only copy; None before the first): the
-        booleans ``fuse_tail``, ``defer``, ``pair_tail``, ``fuse_lc`` (fused lookup + 1×1),
-        ``tiled`` (tiled pyramid) and ``side_stream``.  The mask flags do not change it."""
-        plan = getattr(self, "_last_plan", None)
-        return None if plan is None else dict(plan)
-
-    @property
-    def hx_channels(self) -> int:
-        """Channels of the channels-last GRU working buffer: [h | cxt | motion | flow]."""
-        return self.h_channels + self.cxt_channels + self.encoder.out_channels[0] + 2
 
     def _sync_events(self, dev, slot=0):
         """The fork / join events of a side stream (created once per device and slot, on it)."""
@@ -397,45 +352,20 @@ class SCFlowDecoder(nn.Module):
         _, H, W = depth.shape
         scale = 2 ** (self.num_levels - 1)
         M = N * h * w
-        hc, xc = self.h_channels, self.cxt_channels
-        co = self.encoder.out_channels[0]
-        hx_c = self.hx_channels
         iters = int(self.iters)
 
-        # a1 + a9 (once per forward)
-        tiled = self.tiled_pyramid and ops.tiled_lookup_ok(h, w, self.num_levels, self.radius,
-                                                           self.corr_lookup.align_corners)
-        self._hook("corr_pyramid", True)
-        if tiled:
-            pyr = ops.corr_pyramid_tiled(feat_render, feat_real, self.num_levels)
-        else:
-            pyr, _ = ops.corr_pyramid(feat_render, feat_real, self.num_levels)
-        self._hook("corr_pyramid", False)
+        # a1 + a9 (once per forward), then the channels-last working set; the motion encoder's
+        # and the GRU's buffers and launches are the shared core's (recurrent.py)
+        core = RecurrentCore(self, feat_render, feat_real, self._hook, self._hooks_for)
         depth = depth.contiguous().float()
         K = K.contiguous().float()
         R_prev = R0.contiguous().float()
         t_prev = t0.contiguous().float()
         points = ops.lift_points(depth, K, R_prev, t_prev)
-
-        # channels-last working set
-        if hx is not None:
-            if hx.shape != (M, hx_c) or hx.dtype != f32 or not hx.is_contiguous():
-                raise ValueError(f"hx must be a contiguous float32 [{M}, {hx_c}] buffer")
-            HX = hx
-        else:
-            HX = torch.empty(M, hx_c, device=dev, dtype=f32)
-            ops.nchw_into(h_feat.contiguous().float(), Chan(HX, 0, hc))
-            ops.nchw_into(cxt_feat.contiguous().float(), Chan(HX, hc, xc))
-        # loop-invariant context share of the GRU pre-activations (once per forward)
-        ctx_map = self.gru.context_map(Chan(HX, hc, xc), N, h, w) if self.hoist_context else None
+        core.bind_state(h_feat, cxt_feat, hx)
+        segment, scratch = core.segment, core.scratch
+        hx_flow, hid = core.hx_flow, core.hid
         F2 = torch.empty(M, 2, device=dev, dtype=f32)
-        K_look = self.num_levels * (2 * self.radius + 1) ** 2
-        CORR = torch.empty(M, K_look, device=dev, dtype=f32)
-        cc = self.encoder.corr_net[-1].conv.out_channels
-        cf = self.encoder.flow_net[-1].conv.out_channels
-        MF = torch.empty(M, cc + cf, device=dev, dtype=f32)
-        Z = torch.empty(M, hc, device=dev, dtype=f32)
-        RH = torch.empty(M, hc, device=dev, dtype=f32)
         fh = self.flow_pred.layers[-1].conv.out_channels
         mh = self.mask_pred.layers[-1].conv.out_channels
         HEAD = torch.empty(M, fh + mh, device=dev, dtype=f32)
@@ -444,13 +374,6 @@ class SCFlowDecoder(nn.Module):
         dfc = self.delta_flow_encoder[-1].conv.out_channels
         mfc = self.mask_encoder[-1].conv.out_channels
         FM = torch.empty(M, dfc + mfc, device=dev, dtype=f32)  # [Δflow feat | mask feat]
-
-        def scratch(mods):
-            return [torch.empty(M, m.conv.out_channels, device=dev, dtype=f32) for m in mods[:-1]]
-
-        s_corr = scratch(self.encoder.corr_net)
-        s_flow = scratch(self.encoder.flow_net)
-        s_out = scratch(self.encoder.out_net)
         s_dfe = scratch(self.delta_flow_encoder)
         s_me = scratch(self.mask_encoder)
 
@@ -472,9 +395,6 @@ class SCFlowDecoder(nn.Module):
         label = (label if head_label is None else head_label).to(dev).long()
         masked = bool(self.mask_corr or self.mask_flow)
         flow_full = init_flow.contiguous().float()
-        hx_flow = Chan(HX, hx_c - 2, 2)
-        hx_motion = Chan(HX, hc + xc, co)
-        hid = Chan(HX, 0, hc)
         # independent branches run concurrently on a second stream, joined with events:
         # flow_net ‖ (lookup, corr_net); mask predictor + mask encoder ‖ flow predictor +
         # Δflow encoder.  Every buffer is allocated above on the main stream and outlives the
@@ -515,21 +435,7 @@ class SCFlowDecoder(nn.Module):
         # arguments change per iteration (flow in / out, poses, Δpose) go through the wrappers.
         # This keeps the host well ahead of the GPU (a Python wrapper costs more than several of
         # the pose head's kernels take to run).
-        rec = {}
         keep = []  # buffers the recorded pose-head launches write (alive for the forward)
-
-        def segment(name, fn):
-            calls = rec.get(name)
-            if calls is None:
-                calls = rec[name] = []
-                with ops.binding(calls):
-                    fn()
-            else:
-                for c in calls:
-                    c()
-
-        gru_step = self.gru.bind_step(Chan.whole(HX), Chan.whole(Z), Chan.whole(RH), N, h, w,
-                                      ctx_map=ctx_map, cxt_channels=xc)
         if outs is not None:
             o_drot, o_dt = outs["drot"], outs["dt"]
         else:
@@ -553,47 +459,7 @@ class SCFlowDecoder(nn.Module):
                 [torch.empty_like(F2)] * 2
         else:
             FLMs = F2s
-        flow_in = FLMs[0]
         mask_prev = None  # the mask buffer this iteration's masked launches read
-
-        def seg_flow_branch():
-            run_chain(self.encoder.flow_net, Chan.whole(flow_in), Chan(MF, cc, cf), N, h, w, s_flow,
-                      hooks=self._hooks_for(None, "flow_net1"))
-
-        def seg_lookup():
-            ops.corr_lookup(pyr, F2, N, h, w, self.num_levels, self.radius, out=Chan.whole(CORR),
-                            flow_layout="nhwc", align_corners=self.corr_lookup.align_corners,
-                            tiled=tiled, mask=mask_prev if self.mask_corr else None)
-
-        corr_net = self.encoder.corr_net
-        c0m = corr_net[0].conv
-        fuse_lc = (self.fuse_lookup_conv and h * w <= self.fuse_lookup_conv_max_px and tiled and
-                   len(corr_net) == 2 and
-                   tuple(c0m.kernel_size) == (1, 1) and tuple(c0m.stride) == (1, 1) and
-                   tuple(c0m.padding) == (0, 0) and
-                   ops.lookup_conv1x1_ok(h, w, self.num_levels, self.radius, c0m.in_channels,
-                                         c0m.out_channels))
-
-        def seg_lookup_conv():  # a2 + corr_net.0 in one launch
-            r0 = ConvRunner.of(c0m, corr_net[0].act_type)
-            packed, bias = r0.packed(c0m.in_channels, 0, w, _lib.CONV_1X1W)
-            ops.corr_lookup_conv1x1(pyr, F2, packed, bias, Chan.whole(s_corr[-1]), N, h, w,
-                                    self.num_levels, self.radius, c0m.out_channels,
-                                    corr_net[0].act_type, self.corr_lookup.align_corners,
-                                    mask=mask_prev if self.mask_corr else None)
-
-        def seg_corr_hidden():  # corr_net.0 (1×1 324→256)
-            if len(corr_net) > 1:
-                run_chain(corr_net[:-1], Chan.whole(CORR), Chan.whole(s_corr[-1]), N, h, w,
-                          s_corr[:-1])
-
-        def seg_corr_last():  # corr_net.1 (3×3 256→192), bracketed by the "corr_net1" hook
-            src = Chan.whole(s_corr[-1]) if len(corr_net) > 1 else Chan.whole(CORR)
-            ConvRunner.of(corr_net[-1].conv, corr_net[-1].act_type).run(src, Chan(MF, 0, cc), N, h, w)
-
-        def seg_out():
-            run_chain(self.encoder.out_net, Chan.whole(MF), hx_motion, N, h, w, s_out,
-                      hooks=self._hooks_for("out_net"))
 
         xpred = self._xhead_pred_plan(head_runner, hid, HEAD, N, h, w, dev)
 
@@ -646,8 +512,9 @@ class SCFlowDecoder(nn.Module):
         MASKs = [MASK, torch.empty_like(MASK)] if defer else [MASK, MASK]
         pt = self.pair_tail if self.pair_tail >= 0 else int(h * w <= 32 * 32)
         pair_tail = bool(pt) and len(self.delta_flow_encoder) == len(self.mask_encoder)
+        # last_plan's keys (the mask flags do not change it)
         self._last_plan = dict(fuse_tail=bool(fuse_tail), defer=bool(defer),
-                               pair_tail=bool(pair_tail), fuse_lc=bool(fuse_lc), tiled=bool(tiled),
+                               pair_tail=bool(pair_tail), fuse_lc=core.fuse_lc, tiled=core.tiled,
                                side_stream=bool(two))
         if masked:
             MASKs[1].fill_(1.0)  # before the first prediction: interpolate(ones, 1/8) == ones
@@ -690,20 +557,9 @@ class SCFlowDecoder(nn.Module):
             # a3 (flow branch) on the side stream
             fork()
             with torch.cuda.stream(side):
-                segment("flow_branch" + par, seg_flow_branch)
+                core.flow_branch(par, flow_in)
             # a2 + a3 (correlation branch)
-            if fuse_lc:
-                self._hook("corr_lookup_conv", True)
-                segment("lookup_conv" + par, seg_lookup_conv)
-                self._hook("corr_lookup_conv", False)
-            else:
-                self._hook("corr_lookup", True)
-                segment("lookup" + par, seg_lookup)
-                self._hook("corr_lookup", False)
-                segment("corr_hidden", seg_corr_hidden)
-            self._hook("corr_net1", True)
-            segment("corr_last", seg_corr_last)
-            self._hook("corr_net1", False)
+            core.correlation(par, F2, mask_prev if self.mask_corr else None)
             join()
             if pending:
                 # the previous iteration's full-resolution outputs on the side stream AFTER the
@@ -721,9 +577,9 @@ class SCFlowDecoder(nn.Module):
                         else:
                             ev_full.record(side)
                 pending = []
-            segment("out", seg_out)
+            core.motion_out()
             # a4 GRU (in place on HX[:, :hc])
-            gru_step(self.kernel_hooks)
+            core.gru(self.kernel_hooks)
             # a5 heads (with xpred: the predictors too, into this iteration's Δflow / mask)
             cur_par[0] = it % 2 if defer else 0
             self._hook("heads", True)

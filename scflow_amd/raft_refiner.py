@@ -7,9 +7,11 @@ Reference: ``models/refiner/raft_refiner_flow.py`` (``__init__`` :30-72, ``extra
 rendered images unless ``seperate_encoder`` (base_refiner.py:33-40), the context encoder is
 separate.  The loss configurations are accepted and kept, as ``SCFlowRefiner`` keeps them.
 
-``get_flow`` takes ``SCFlowRefiner._get_pose``'s device-side path: the shared feature encoder
-runs ONCE over cat[real, rendered], the context encoder writes tanh(h) | relu(cxt) straight into
-the decoder's channels-last GRU working buffer, and the decoder runs with that buffer.  It returns
+``get_flow`` takes ``SCFlowRefiner._get_pose``'s device-side path (``refiner.py``'s
+``_RefinerBase._features_into_hx``, which also holds the construction, ``freeze_bn`` and
+``extract_feat``): the shared feature encoder runs ONCE over cat[real, rendered], the context
+encoder writes tanh(h) | relu(cxt) straight into the decoder's channels-last GRU working buffer,
+and the decoder runs with that buffer.  It returns
 the decoder's lists (``upflow_preds``; with the mask decoder ``(upflow_preds,
 upocclusion_preds)``).
 
@@ -25,48 +27,28 @@ and graph-mode training — ``forward`` is ``get_flow``.
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import Optional, Sequence, Tuple
+from typing import Optional, Sequence
 
 import torch
-import torch.nn as nn
 
-from . import ops
 from ._lib import ScflowError
+from .refiner import _RefinerBase
 from .registry import MODELS
 
 Tensor = torch.Tensor
 
 
-def _build(cfg):
-    if isinstance(cfg, nn.Module):
-        return cfg
-    return MODELS.build(cfg)
-
-
-class _RAFTFlowRefiner(nn.Module):
-    """What the two refiners share (BaseFlowRefiner's constructor arguments, the context encoder,
-    ``extract_feat`` and ``get_flow``)."""
+class _RAFTFlowRefiner(_RefinerBase):
+    """What the two RAFT refiners add to the shared base (BaseFlowRefiner's constructor
+    arguments, ``get_flow`` and ``loss``)."""
 
     def __init__(self, seperate_encoder: bool, cxt_channels: int, h_channels: int, cxt_encoder: dict,
                  encoder: dict, decoder: dict, renderer: Optional[dict], max_flow: float,
                  render_augmentations: Optional[Sequence], filter_invalid_flow_by_mask: bool,
                  filter_invalid_flow_by_depth: bool, freeze_bn: bool, train_cfg: Optional[dict],
                  test_cfg: Optional[dict], init_cfg) -> None:
-        super().__init__()
-        self.seperate_encoder = seperate_encoder
-        if seperate_encoder:
-            self.render_encoder = _build(encoder)
-            self.real_encoder = _build(encoder)
-        else:
-            enc = _build(encoder)
-            self.render_encoder = enc
-            self.real_encoder = enc
-        self.decoder = _build(decoder)
-        self.context = _build(cxt_encoder)
-        self.h_channels, self.cxt_channels = h_channels, cxt_channels
-        assert self.h_channels == self.decoder.h_channels
-        assert self.cxt_channels == self.decoder.cxt_channels
-        assert self.h_channels + self.cxt_channels == self.context.out_channels
+        super().__init__(seperate_encoder, cxt_channels, h_channels, cxt_encoder, encoder, decoder,
+                         freeze_bn)
         self.max_flow = max_flow
         self.filter_invalid_flow_by_mask = filter_invalid_flow_by_mask
         self.filter_invalid_flow_by_depth = filter_invalid_flow_by_depth
@@ -77,37 +59,8 @@ class _RAFTFlowRefiner(nn.Module):
         self.init_cfg = init_cfg
         self.test_iter_num = self.test_cfg.get("iters") if "iters" in self.test_cfg \
             else self.decoder.iters
-        self.freeze_bn_flag = bool(freeze_bn)
-        if freeze_bn:
-            self.freeze_bn()
-
-    def freeze_bn(self) -> None:
-        """raft_refiner_flow.py:75-78: every BatchNorm2d in eval mode."""
-        self.freeze_bn_flag = True
-        for m in self.modules():
-            if isinstance(m, nn.BatchNorm2d):
-                m.eval()
-
-    def train(self, mode: bool = True):
-        super().train(mode)
-        if mode and self.freeze_bn_flag:
-            self.freeze_bn()
-        return self
 
     # ------------------------------------------------------------------ reference API
-    def extract_feat(self, render_images: Tensor, real_images: Tensor
-                     ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-        """raft_refiner_flow.py:90-113 — NCHW (render_feat, real_feat, tanh(h), relu(cxt))."""
-        real_feat = self.real_encoder(real_images)
-        render_feat = self.render_encoder(render_images)
-        n = render_images.shape[0]
-        c = self.context.forward_cl(render_images.contiguous().float(), act="Tanh", act2="ReLU",
-                                    act_split=self.h_channels)
-        _, h, w, _ = c.shape
-        h_feat = ops.chan_to_nchw(ops.Chan(c, 0, self.h_channels), n, h, w)
-        cxt_feat = ops.chan_to_nchw(ops.Chan(c, self.h_channels, self.cxt_channels), n, h, w)
-        return render_feat, real_feat, h_feat, cxt_feat
-
     def get_flow(self, render_images: Tensor, real_images: Tensor,
                  init_flow: Optional[Tensor] = None):
         """raft_refiner_flow.py:115-137 — images → encoders → the RAFT decoder's lists.
@@ -154,28 +107,10 @@ class _RAFTFlowRefiner(nn.Module):
 
     # ------------------------------------------------------------------ fused path
     def _get_flow(self, render, real, init_flow):
-        N = real.shape[0]
-        dev = real.device
-        dec = self.decoder
-        # feature encoder(s): one launch sequence over cat[real, render] when shared
-        if self.real_encoder is self.render_encoder:
-            both = torch.cat([real, render], 0)
-            fcl = self.real_encoder.forward_cl(both)
-            n2, h, w, _ = fcl.shape
-            feats = ops.chan_to_nchw(ops.Chan.whole(fcl), n2, h, w)
-            real_feat, render_feat = feats[:N], feats[N:]
-        else:
-            real_feat = self.real_encoder(real)
-            render_feat = self.render_encoder(render)
-            h, w = real_feat.shape[-2:]
-        # context encoder → tanh(h) | relu(cxt) straight into the decoder's GRU buffer
-        hx = torch.empty(N * h * w, dec.hx_channels, device=dev)
-        self.context.forward_cl(render, out=hx.view(N, h, w, dec.hx_channels), act="Tanh",
-                                act2="ReLU", act_split=self.h_channels)
+        render_feat, real_feat, hx, h, w = self._features_into_hx(render, real)
         if init_flow is None:
-            init_flow = torch.zeros(N, 2, h, w, device=dev)
-        return dec._forward(render_feat.contiguous(), real_feat.contiguous(), init_flow, None, None,
-                            hx=hx)
+            init_flow = torch.zeros(real.shape[0], 2, h, w, device=real.device)
+        return self.decoder._forward(render_feat, real_feat, init_flow, None, None, hx=hx)
 
 
 @MODELS.register_module()

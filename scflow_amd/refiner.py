@@ -18,6 +18,10 @@ losses live in ``scflow_amd.train``.
 * the context encoder writes tanh(h) | relu(cxt) — the split activation fused into its last
   conv — straight into the decoder's channels-last GRU working buffer;
 * the decoder then runs with that buffer (no NCHW round trip for h / cxt).
+
+``_RefinerBase`` holds what this refiner shares with the RAFT baseline's (``raft_refiner.py``):
+the encoder / decoder / context construction, ``freeze_bn``, ``extract_feat`` and the fused path up
+to the decoder call (``_features_into_hx``).
 """
 from __future__ import annotations
 
@@ -40,14 +44,13 @@ def _build(cfg):
     return MODELS.build(cfg)
 
 
-@MODELS.register_module()
-class SCFlowRefiner(nn.Module):
-    def __init__(self, cxt_channels: int, h_channels: int, seperate_encoder: bool, cxt_encoder: dict,
-                 encoder: dict, decoder: dict, renderer=None, render_augmentations=None,
-                 pose_loss_cfg=None, flow_loss_cfg=None, mask_loss_cfg=None, max_flow: float = 400.,
-                 filter_invalid_flow: bool = True, freeze_encoder: bool = False,
-                 freeze_bn: bool = False, train_cfg: Optional[dict] = None,
-                 test_cfg: Optional[dict] = None, init_cfg=None) -> None:
+class _RefinerBase(nn.Module):
+    """The encoders, the context encoder and the decoder of a refiner, and the two ways images
+    reach the decoder: ``extract_feat`` (the reference's NCHW tensors) and ``_features_into_hx``
+    (channels-last, straight into the decoder's GRU buffer)."""
+
+    def __init__(self, seperate_encoder: bool, cxt_channels: int, h_channels: int, cxt_encoder,
+                 encoder, decoder, freeze_bn: bool) -> None:
         super().__init__()
         self.seperate_encoder = seperate_encoder
         if seperate_encoder:
@@ -63,6 +66,74 @@ class SCFlowRefiner(nn.Module):
         assert self.h_channels == self.decoder.h_channels
         assert self.cxt_channels == self.decoder.cxt_channels
         assert self.h_channels + self.cxt_channels == self.context.out_channels
+        # scflow_refiner.py:58-61.  The flag is kept and re-applied by train(): the reference
+        # applies it once in __init__, so mmengine's later model.train() puts its BatchNorms
+        # back in train mode; here a frozen module stays frozen.
+        self.freeze_bn_flag = bool(freeze_bn)
+        if freeze_bn:
+            self.freeze_bn()
+
+    def freeze_bn(self) -> None:
+        """scflow_refiner.py:75-78, raft_refiner_flow.py:75-78: every BatchNorm2d in eval mode
+        (running statistics, no update); its affine parameters stay trainable."""
+        self.freeze_bn_flag = True
+        for m in self.modules():
+            if isinstance(m, nn.BatchNorm2d):
+                m.eval()
+
+    def train(self, mode: bool = True):
+        super().train(mode)
+        if mode and self.freeze_bn_flag:
+            self.freeze_bn()
+        return self
+
+    def extract_feat(self, render_images: Tensor, real_images: Tensor
+                     ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        """scflow_refiner.py:84-106, raft_refiner_flow.py:90-113 — NCHW (render_feat, real_feat,
+        tanh(h), relu(cxt))."""
+        real_feat = self.real_encoder(real_images)
+        render_feat = self.render_encoder(render_images)
+        n = render_images.shape[0]
+        c = self.context.forward_cl(render_images.contiguous().float(), act="Tanh", act2="ReLU",
+                                    act_split=self.h_channels)
+        _, h, w, _ = c.shape
+        h_feat = ops.chan_to_nchw(ops.Chan(c, 0, self.h_channels), n, h, w)
+        cxt_feat = ops.chan_to_nchw(ops.Chan(c, self.h_channels, self.cxt_channels), n, h, w)
+        return render_feat, real_feat, h_feat, cxt_feat
+
+    def _features_into_hx(self, render: Tensor, real: Tensor):
+        """The fused path up to the decoder call: (render_feat, real_feat, hx, h, w) with ``hx``
+        the decoder's channels-last GRU buffer, tanh(h) | relu(cxt) already in place."""
+        N = real.shape[0]
+        # feature encoder(s): one launch sequence over cat[real, render] when shared
+        if self.real_encoder is self.render_encoder:
+            both = torch.cat([real, render], 0)
+            fcl = self.real_encoder.forward_cl(both)
+            n2, h, w, _ = fcl.shape
+            feats = ops.chan_to_nchw(ops.Chan.whole(fcl), n2, h, w)
+            real_feat, render_feat = feats[:N], feats[N:]
+        else:
+            real_feat = self.real_encoder(real)
+            render_feat = self.render_encoder(render)
+            h, w = real_feat.shape[-2:]
+        # context encoder → tanh(h) | relu(cxt) straight into the decoder's GRU buffer
+        hx_c = self.decoder.hx_channels
+        hx = torch.empty(N * h * w, hx_c, device=real.device)
+        self.context.forward_cl(render, out=hx.view(N, h, w, hx_c), act="Tanh", act2="ReLU",
+                                act_split=self.h_channels)
+        return render_feat.contiguous(), real_feat.contiguous(), hx, h, w
+
+
+@MODELS.register_module()
+class SCFlowRefiner(_RefinerBase):
+    def __init__(self, cxt_channels: int, h_channels: int, seperate_encoder: bool, cxt_encoder: dict,
+                 encoder: dict, decoder: dict, renderer=None, render_augmentations=None,
+                 pose_loss_cfg=None, flow_loss_cfg=None, mask_loss_cfg=None, max_flow: float = 400.,
+                 filter_invalid_flow: bool = True, freeze_encoder: bool = False,
+                 freeze_bn: bool = False, train_cfg: Optional[dict] = None,
+                 test_cfg: Optional[dict] = None, init_cfg=None) -> None:
+        super().__init__(seperate_encoder, cxt_channels, h_channels, cxt_encoder, encoder, decoder,
+                         freeze_bn)
         self.max_flow = max_flow
         self.filter_invalid_flow = filter_invalid_flow
         self.train_cfg = train_cfg or {}
@@ -73,13 +144,9 @@ class SCFlowRefiner(nn.Module):
         if renderer is not None:
             from .renderer import Renderer
             self.renderer = renderer if isinstance(renderer, Renderer) else Renderer(**renderer)
-        # scflow_refiner.py:58-61.  The flags are kept and re-applied by train(): the reference
-        # applies them once in __init__, so mmengine's later model.train() puts its BatchNorms
-        # back in train mode; here a frozen module stays frozen (requires_grad=False persists
-        # in both).
-        self.freeze_bn_flag, self.freeze_encoder_flag = bool(freeze_bn), bool(freeze_encoder)
-        if freeze_bn:
-            self.freeze_bn()
+        # scflow_refiner.py:58-61; kept and re-applied by train() like freeze_bn
+        # (requires_grad=False persists in both)
+        self.freeze_encoder_flag = bool(freeze_encoder)
         if freeze_encoder:
             self.freeze_encoder()
 
@@ -93,18 +160,8 @@ class SCFlowRefiner(nn.Module):
                 for p in m.parameters():
                     p.requires_grad = False
 
-    def freeze_bn(self) -> None:
-        """scflow_refiner.py:75-78: every BatchNorm2d in eval mode (running statistics, no
-        update); its affine parameters stay trainable."""
-        self.freeze_bn_flag = True
-        for m in self.modules():
-            if isinstance(m, nn.BatchNorm2d):
-                m.eval()
-
     def train(self, mode: bool = True):
         super().train(mode)
-        if mode and self.freeze_bn_flag:
-            self.freeze_bn()
         if mode and self.freeze_encoder_flag:
             for enc in (self.real_encoder, self.render_encoder):
                 enc.eval()
@@ -157,19 +214,6 @@ class SCFlowRefiner(nn.Module):
         return R, t, out
 
     # ------------------------------------------------------------------ reference API
-    def extract_feat(self, render_images: Tensor, real_images: Tensor
-                     ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-        """scflow_refiner.py:84-106 — NCHW (render_feat, real_feat, tanh(h), relu(cxt))."""
-        real_feat = self.real_encoder(real_images)
-        render_feat = self.render_encoder(render_images)
-        n = render_images.shape[0]
-        c = self.context.forward_cl(render_images.contiguous().float(), act="Tanh", act2="ReLU",
-                                    act_split=self.h_channels)
-        _, h, w, _ = c.shape
-        h_feat = ops.chan_to_nchw(ops.Chan(c, 0, self.h_channels), n, h, w)
-        cxt_feat = ops.chan_to_nchw(ops.Chan(c, self.h_channels, self.cxt_channels), n, h, w)
-        return render_feat, real_feat, h_feat, cxt_feat
-
     def get_pose(self, render_images: Tensor, real_images: Tensor, ref_rotation: Tensor,
                  ref_translation: Tensor, depth: Tensor, internel_k: Tensor, label: Tensor,
                  init_flow: Optional[Tensor] = None, head_label: Optional[Tensor] = None):
@@ -187,24 +231,8 @@ class SCFlowRefiner(nn.Module):
     # ------------------------------------------------------------------ fused path
     def _get_pose(self, render, real, R, t, depth, K, label, init_flow, head_label=None):
         N, _, H, W = real.shape
-        dev = real.device
-        dec = self.decoder
-        # feature encoder(s): one launch sequence over cat[real, render] when shared
-        if self.real_encoder is self.render_encoder:
-            both = torch.cat([real, render], 0)
-            fcl = self.real_encoder.forward_cl(both)
-            n2, h, w, C = fcl.shape
-            feats = ops.chan_to_nchw(ops.Chan.whole(fcl), n2, h, w)
-            real_feat, render_feat = feats[:N], feats[N:]
-        else:
-            real_feat = self.real_encoder(real)
-            render_feat = self.render_encoder(render)
-            h, w = real_feat.shape[-2:]
-        # context encoder → tanh(h) | relu(cxt) straight into the decoder's GRU buffer
-        hx = torch.empty(N * h * w, dec.hx_channels, device=dev)
-        self.context.forward_cl(render, out=hx.view(N, h, w, dec.hx_channels), act="Tanh",
-                                act2="ReLU", act_split=self.h_channels)
+        render_feat, real_feat, hx, _, _ = self._features_into_hx(render, real)
         if init_flow is None:
-            init_flow = torch.zeros(N, 2, H, W, device=dev)
-        return dec._forward(render_feat.contiguous(), real_feat.contiguous(), None, None, R, t, depth,
-                            K, label, init_flow, 0.0, hx=hx, head_label=head_label)
+            init_flow = torch.zeros(N, 2, H, W, device=real.device)
+        return self.decoder._forward(render_feat, real_feat, None, None, R, t, depth, K, label,
+                                     init_flow, 0.0, hx=hx, head_label=head_label)

@@ -17,7 +17,8 @@ raft_refiner_flow_mask.py:167-220) on the same pieces: ``raft_decoder_train`` re
 decoders' loop (flow detached every iteration, occlusion head, raw mask logits) and upsamples
 through ``convex_upsample`` (scflow_convex_upsample forward, scflow_convex_upsample_bwd backward);
 the flow and occlusion sequence losses are the torch restatements of losses.py with the weights
-of the refiner's stored loss configs.
+of the refiner's stored loss configs.  The two forwards share ``_encode_images``, ``_gt_flow`` and,
+inside the decoder loops, ``_motion_features`` and ``_hidden_heads``.
 """
 from __future__ import annotations
 
@@ -226,6 +227,45 @@ def _gru_iteration(h: Tensor, motion: Tensor, it_w, ctx_pre, hc: int) -> Tensor:
     return h
 
 
+def _motion_features(enc, corr: Tensor, flow_in: Tensor) -> Tensor:
+    """MotionEncoder.forward (raft_decoder.py:61-166) without its final cat: corr_net and flow_net,
+    then out_net on their outputs (the first conv reads both in place)."""
+    c = corr
+    for m in enc.corr_net:
+        c = _cm(c, m)
+    f = flow_in
+    for m in enc.flow_net:
+        f = _cm(f, m)
+    out = _cm(c, enc.out_net[0], x1=f)
+    for m in enc.out_net[1:]:
+        out = _cm(out, m)
+    return out
+
+
+def _hidden_heads(h: Tensor, heads) -> List[Tensor]:
+    """The XHeads' hidden ConvModules on the GRU state; the first two as one launch each way where
+    ``dual_conv2d_nhwc`` allows (one 3×3 layer each, same shape and activation)."""
+    def fusable(a, b):
+        la, lb = a.layers, b.layers
+        return (_HEADS_FUSED and h.is_cuda and len(la) == 1 and len(lb) == 1
+                and la[0].conv.kernel_size == lb[0].conv.kernel_size
+                and la[0].conv.padding == lb[0].conv.padding and la[0].conv.stride == (1, 1)
+                and lb[0].conv.stride == (1, 1) and la[0].act_type == lb[0].act_type
+                and (la[0].conv.bias is None) == (lb[0].conv.bias is None))
+    outs, rest = [], list(heads)
+    if len(rest) >= 2 and fusable(rest[0], rest[1]):
+        a, b = rest[0].layers[0], rest[1].layers[0]
+        outs += list(dual_conv2d_nhwc(h, a.conv.weight, a.conv.bias, b.conv.weight, b.conv.bias,
+                                      a.conv.padding, a.act_type))
+        rest = rest[2:]
+    for hd in rest:
+        x = h
+        for m in hd.layers:
+            x = _cm(x, m)
+        outs.append(x)
+    return outs
+
+
 def decoder_train(dec, feat_render: Tensor, feat_real: Tensor, h: Tensor, cxt: Tensor, R0: Tensor,
                   t0: Tensor, depth: Tensor, K: Tensor, label: Tensor, iters: int,
                   invalid_flow_num: float = 0.0) -> Tuple[List[Tensor], ...]:
@@ -251,12 +291,6 @@ def decoder_train(dec, feat_render: Tensor, feat_real: Tensor, h: Tensor, cxt: T
     gru = dec.gru
     hc, cc = dec.h_channels, dec.cxt_channels
     it_w, ctx_pre = _hoist_context(gru, cxt, hc, cc)
-    fl, ml = dec.flow_pred.layers, dec.mask_pred.layers
-    heads_fused = (_HEADS_FUSED and len(fl) == 1 and len(ml) == 1 and h.is_cuda
-                   and fl[0].conv.kernel_size == ml[0].conv.kernel_size
-                   and fl[0].conv.padding == ml[0].conv.padding and fl[0].conv.stride == (1, 1)
-                   and ml[0].conv.stride == (1, 1) and fl[0].act_type == ml[0].act_type
-                   and (fl[0].conv.bias is None) == (ml[0].conv.bias is None))
     mask = None
     for _ in range(iters):
         # occlusion masking (scflow_decoder.py:189-207): the previous iteration's low-resolution
@@ -277,28 +311,9 @@ def decoder_train(dec, feat_render: Tensor, feat_real: Tensor, h: Tensor, cxt: T
             corr = corr_lookup(pyr, f2, N, hh, ww, L, r, mask=mk)
         else:
             corr = corr_lookup(pyr, f2, N, hh, ww, L, r)
-        c = corr
-        for m in enc.corr_net:
-            c = _cm(c, m)
-        f = f2m
-        for m in enc.flow_net:
-            f = _cm(f, m)
-        out = _cm(c, enc.out_net[0], x1=f)
-        for m in enc.out_net[1:]:
-            out = _cm(out, m)
-        motion = torch.cat([out, f2m], -1)
+        motion = torch.cat([_motion_features(enc, corr, f2m), f2m], -1)
         h = _gru_iteration(h, motion, it_w, ctx_pre, hc)
-        fl, ml = dec.flow_pred.layers, dec.mask_pred.layers
-        if heads_fused:  # both XHeads' hidden convs as one launch each way
-            fh, mh = dual_conv2d_nhwc(h, fl[0].conv.weight, fl[0].conv.bias, ml[0].conv.weight,
-                                      ml[0].conv.bias, fl[0].conv.padding, fl[0].act_type)
-        else:
-            fh = h
-            for m in fl:
-                fh = _cm(fh, m)
-            mh = h
-            for m in ml:
-                mh = _cm(mh, m)
+        fh, mh = _hidden_heads(h, [dec.flow_pred, dec.mask_pred])
         dflow = _conv(fh, dec.flow_pred.predict_layer)
         pl = dec.mask_pred.predict_layer
         mask = conv2d_nhwc(mh, pl.weight, pl.bias, 1, pl.padding, act="Sigmoid")
@@ -328,6 +343,38 @@ def decoder_train(dec, feat_render: Tensor, feat_real: Tensor, h: Tensor, cxt: T
     return outs
 
 
+def _encode_images(refiner, batch: Dict[str, Tensor]) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Channels-last (feat_real, feat_render, tanh(h), relu(cxt)) of a batch's images: the feature
+    encoder(s) on real and rendered, the context encoder on rendered."""
+    real = batch["real_images"].permute(0, 2, 3, 1).contiguous()
+    render = batch["render_images"].permute(0, 2, 3, 1).contiguous()
+    N = real.shape[0]
+    if refiner.real_encoder is refiner.render_encoder:  # shared: one batch of 2N images
+        feats = encoder_train(refiner.real_encoder, torch.cat([real, render], 0))
+        feat_real, feat_render = feats[:N], feats[N:]
+    else:
+        feat_real = encoder_train(refiner.real_encoder, real)
+        feat_render = encoder_train(refiner.render_encoder, render)
+    cx = encoder_train(refiner.context, render)
+    hc = refiner.h_channels
+    return feat_real, feat_render, torch.tanh(cx[..., :hc]), torch.relu(cx[..., hc:])
+
+
+def _gt_flow(batch: Dict[str, Tensor], max_flow: float, dt) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(gt_flow, render_mask, depth, K), no autograd: the GT flow lifts the rendered depth with the
+    reference pose and projects with the GT pose (unfiltered: each caller applies its own
+    filter); render_mask = depth > 0."""
+    with torch.no_grad():
+        depth = batch["depth"].contiguous().to(dt)
+        K = batch["internel_k"].contiguous().to(dt)
+        pts = ops.lift_points(depth, K, batch["ref_rotation"].contiguous().to(dt),
+                              batch["ref_translation"].contiguous().to(dt))
+        gt_flow = torch.empty(depth.shape[0], 2, *depth.shape[1:], device=depth.device, dtype=dt)
+        ops.pose_flow(batch["gt_rotation"].contiguous().to(dt), batch["gt_translation"].contiguous().to(dt),
+                      K, pts, max_flow, out=gt_flow)
+        return gt_flow, (depth > 0).to(dt), depth, K
+
+
 def refiner_train_forward(refiner, batch: Dict[str, Tensor], model_points: Sequence[Tensor],
                           diameters: Sequence[float], iters: int = None) -> Dict[str, Tensor]:
     """Images → losses (SCFlowRefiner.loss), autograd graph attached.  ``batch`` keys:
@@ -338,33 +385,15 @@ def refiner_train_forward(refiner, batch: Dict[str, Tensor], model_points: Seque
     check_train_flags(dec)
     begin_forward()  # per-weight use counts of this pass (batched weight gradients)
     iters = int(dec.iters if iters is None else iters)
-    real = batch["real_images"].permute(0, 2, 3, 1).contiguous()
-    render = batch["render_images"].permute(0, 2, 3, 1).contiguous()
-    N = real.shape[0]
-    dt = real.dtype
-    if refiner.real_encoder is refiner.render_encoder:  # shared: one batch of 2N images
-        feats = encoder_train(refiner.real_encoder, torch.cat([real, render], 0))
-        feat_real, feat_render = feats[:N], feats[N:]
-    else:
-        feat_real = encoder_train(refiner.real_encoder, real)
-        feat_render = encoder_train(refiner.render_encoder, render)
-    cx = encoder_train(refiner.context, render)
-    hc = refiner.h_channels
-    h, cxt = torch.tanh(cx[..., :hc]), torch.relu(cx[..., hc:])
+    feat_real, feat_render, h, cxt = _encode_images(refiner, batch)
+    dt = batch["real_images"].dtype
     outs = decoder_train(dec, feat_render, feat_real, h, cxt, batch["ref_rotation"],
                          batch["ref_translation"], batch["depth"], batch["internel_k"],
                          batch.get("head_label", batch["label"]), iters)
-    with torch.no_grad():  # GT flow: lift with the reference pose, project with the GT pose
-        depth = batch["depth"].contiguous().to(dt)
-        K = batch["internel_k"].contiguous().to(dt)
-        pts = ops.lift_points(depth, K, batch["ref_rotation"].contiguous().to(dt),
-                              batch["ref_translation"].contiguous().to(dt))
-        gt_flow = torch.empty(N, 2, *depth.shape[1:], device=depth.device, dtype=dt)
-        ops.pose_flow(batch["gt_rotation"].contiguous().to(dt), batch["gt_translation"].contiguous().to(dt),
-                      K, pts, refiner.max_flow, out=gt_flow)
-        if refiner.filter_invalid_flow and "gt_masks" in batch:
+    gt_flow, render_mask, _, _ = _gt_flow(batch, refiner.max_flow, dt)
+    if refiner.filter_invalid_flow and "gt_masks" in batch:
+        with torch.no_grad():
             gt_flow = filter_flow_by_mask(gt_flow, batch["gt_masks"], refiner.max_flow)
-        render_mask = (depth > 0).to(dt)
     lp, lf, lm = refine_losses(outs, batch["gt_rotation"].to(dt), batch["gt_translation"].to(dt),
                                gt_flow, render_mask, batch["label"], model_points, diameters,
                                refiner.max_flow)
@@ -372,30 +401,6 @@ def refiner_train_forward(refiner, batch: Dict[str, Tensor], model_points: Seque
 
 
 # ------------------------------------------------------------------------------- RAFT baseline
-def _hidden_heads(h: Tensor, heads) -> List[Tensor]:
-    """The XHeads' hidden ConvModules on the GRU state; the first two as one launch each way where
-    ``dual_conv2d_nhwc`` allows (one 3×3 layer each, same shape and activation)."""
-    def fusable(a, b):
-        la, lb = a.layers, b.layers
-        return (_HEADS_FUSED and h.is_cuda and len(la) == 1 and len(lb) == 1
-                and la[0].conv.kernel_size == lb[0].conv.kernel_size
-                and la[0].conv.padding == lb[0].conv.padding and la[0].conv.stride == (1, 1)
-                and lb[0].conv.stride == (1, 1) and la[0].act_type == lb[0].act_type
-                and (la[0].conv.bias is None) == (lb[0].conv.bias is None))
-    outs, rest = [], list(heads)
-    if len(rest) >= 2 and fusable(rest[0], rest[1]):
-        a, b = rest[0].layers[0], rest[1].layers[0]
-        outs += list(dual_conv2d_nhwc(h, a.conv.weight, a.conv.bias, b.conv.weight, b.conv.bias,
-                                      a.conv.padding, a.act_type))
-        rest = rest[2:]
-    for hd in rest:
-        x = h
-        for m in hd.layers:
-            x = _cm(x, m)
-        outs.append(x)
-    return outs
-
-
 def raft_decoder_train(dec, feat_render: Tensor, feat_real: Tensor, h: Tensor, cxt: Tensor,
                        iters: int, init_flow: Tensor = None
                        ) -> Tuple[List[Tensor], List[Tensor], List[Tensor]]:
@@ -426,16 +431,8 @@ def raft_decoder_train(dec, feat_render: Tensor, feat_real: Tensor, h: Tensor, c
     for _ in range(iters):
         flow = flow.detach()
         corr = corr_lookup(pyr, flow, N, hh, ww, L, r)
-        c = corr
-        for m in enc.corr_net:
-            c = _cm(c, m)
-        f = flow
-        for m in enc.flow_net:
-            f = _cm(f, m)
-        out = _cm(c, enc.out_net[0], x1=f)
-        for m in enc.out_net[1:]:
-            out = _cm(out, m)
-        h = _gru_iteration(h, torch.cat([out, flow], -1), it_w, ctx_pre, hc)
+        motion = torch.cat([_motion_features(enc, corr, flow), flow], -1)
+        h = _gru_iteration(h, motion, it_w, ctx_pre, hc)
         hid = _hidden_heads(h, heads)
         flow = flow + _conv(hid[0], dec.flow_pred.predict_layer)
         lr_flows.append(flow)
@@ -501,33 +498,15 @@ def raft_refiner_train_forward(refiner, batch: Dict[str, Tensor], iters: int = N
                                   "RAFTDecoderMask an occlusion loss")
     begin_forward()
     iters = int(dec.iters if iters is None else iters)
-    real = batch["real_images"].permute(0, 2, 3, 1).contiguous()
-    render = batch["render_images"].permute(0, 2, 3, 1).contiguous()
-    N = real.shape[0]
-    dt = real.dtype
-    if refiner.real_encoder is refiner.render_encoder:  # shared: one batch of 2N images
-        feats = encoder_train(refiner.real_encoder, torch.cat([real, render], 0))
-        feat_real, feat_render = feats[:N], feats[N:]
-    else:
-        feat_real = encoder_train(refiner.real_encoder, real)
-        feat_render = encoder_train(refiner.render_encoder, render)
-    cx = encoder_train(refiner.context, render)
-    hc = refiner.h_channels
-    h, cxt = torch.tanh(cx[..., :hc]), torch.relu(cx[..., hc:])
+    feat_real, feat_render, h, cxt = _encode_images(refiner, batch)
+    dt = batch["real_images"].dtype
     outs = raft_decoder_train(dec, feat_render, feat_real, h, cxt, iters)
     upflows, upoccs, _ = outs
     max_flow = float(refiner.max_flow)
-    with torch.no_grad():  # GT flow: lift with the reference pose, project with the GT pose
-        depth = batch["depth"].contiguous().to(dt)
-        K = batch["internel_k"].contiguous().to(dt)
-        pts = ops.lift_points(depth, K, batch["ref_rotation"].contiguous().to(dt),
-                              batch["ref_translation"].contiguous().to(dt))
-        gt_flow = torch.empty(N, 2, *depth.shape[1:], device=depth.device, dtype=dt)
-        ops.pose_flow(batch["gt_rotation"].contiguous().to(dt), batch["gt_translation"].contiguous().to(dt),
-                      K, pts, max_flow, out=gt_flow)
+    gt_flow, render_mask, _, _ = _gt_flow(batch, max_flow, dt)
+    with torch.no_grad():
         if refiner.filter_invalid_flow_by_mask:
             gt_flow = filter_flow_by_mask(gt_flow, batch["gt_masks"], max_flow)
-        render_mask = (depth > 0).to(dt)
         v = flow_valid(gt_flow, render_mask, f_cfg["max_flow"])  # iteration-invariant
         gt_occ = (gt_flow.sum(dim=1) < max_flow).to(dt)  # the reference's sum, not the magnitude
     seq_f = [flow_l1_loss(f, gt_flow, render_mask, f_cfg["max_flow"], f_cfg["weight"], f_cfg["eps"], v=v)
