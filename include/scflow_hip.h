@@ -143,9 +143,8 @@ int scflow_corr_lookup_conv1x1_masked(const float* pyr, const float* flow, const
 #define SCFLOW_ABI_VERSION 4
 int scflow_abi_version(void);
 long long scflow_conv_args_size(void);
-/* Tuning only: launch-time environment switches (SCFLOW_WINO4_DEPTH, SCFLOW_WINO4_XCD,
- * SCFLOW_GNR_CB, SCFLOW_SMALLCIN_SPLIT, SCFLOW_SMALLCIN_WGS, SCFLOW_THINZ) are read once and
- * cached; this makes their next use re-read the environment (in-process A/B). */
+/* Tuning only: the library's SCFLOW_* environment switches ("Switches") are read
+ * once and cached; this makes their next use re-read the environment (in-process A/B). */
 int scflow_debug_reload_switches(void);
 /* Profiling only: later LDS-kernel lookups (scflow_corr_lookup*) write 6 u64 real-time-clock
  * stamps per workgroup of 16 query pixels to `stamps` (phase boundaries; NULL turns it off). */

@@ -302,8 +302,9 @@ def load(path: str = LIB_PATH):
 
 
 def reload_switches() -> None:
-    """Make the library re-read its cached launch-time switches (SCFLOW_WINO4_DEPTH,
-    SCFLOW_GNR_CB, SCFLOW_SMALLCIN_SPLIT, SCFLOW_SMALLCIN_WGS) after os.environ changed."""
+    """Make the library re-read its SCFLOW_* switches after os.environ changed: every switch the
+    HIP library reads is cached until this call.  INTEGRATION.md ("Switches") lists them, and
+    which of them only act when a conv's kernel is picked and its weights packed."""
     check(load().scflow_debug_reload_switches(), "scflow_debug_reload_switches")
 
 

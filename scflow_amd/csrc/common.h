@@ -55,7 +55,9 @@ static inline int device_cus() {
 
 // Environment switch for A/B runs of a launch-time choice: read on first use and cached (these
 // sit on launch-bound paths — the decoder's recorded launches replay every iteration), re-read
-// after scflow_debug_reload_switches() bumps the generation (in-process A/B).
+// after scflow_debug_reload_switches() bumps the generation (in-process A/B).  Every SCFLOW_*
+// switch of the library is one of these; INTEGRATION.md ("Switches") lists them all with their
+// values and when a change takes effect.
 extern std::atomic<int> g_switch_gen;
 struct EnvSwitch {
   const char* name;
@@ -73,6 +75,18 @@ struct EnvSwitch {
     return val.load(std::memory_order_relaxed);
   }
 };
+
+// A launch with more than 64 KiB of dynamic LDS needs its kernel opted in (up to the CU's
+// 160 KiB): once per kernel, before its first such launch.
+template <auto Kernel>
+void allow_big_lds(size_t lds) {
+  static std::atomic<bool> done{false};
+  if (lds > 64 * 1024 && !done.load(std::memory_order_relaxed)) {
+    (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              160 * 1024);
+    done.store(true, std::memory_order_relaxed);
+  }
+}
 
 __device__ __forceinline__ float act_apply(float v, int act) {
   switch (act) {

@@ -1015,11 +1015,8 @@ long long wino_blocks(const scflow_conv_args& a) {
 // (measured per decoder shape at B = 16, tools/conv_bench.py: 3×3 256→192 85 vs 95 µs at 384
 // workgroups; 256→126, 128→64 and the GRU q convs at 256 or fewer prefer 32)
 int wino_nbw(const scflow_conv_args& a, int cus) {
-  static int forced = -1;
-  if (forced < 0) {
-    const char* e = getenv("SCFLOW_WINO_NBW");
-    forced = e ? atoi(e) : 0;
-  }
+  static EnvSwitch nbw_sw("SCFLOW_WINO_NBW", 0);
+  const int forced = nbw_sw.get();
   if (forced == 1 || forced == 2) return forced;
   if (a.cout <= 32) return 1;
   // 96 channels when that is exactly one workgroup per CU where 64 would leave 1.5 (3×3, W = 32)
@@ -1029,14 +1026,9 @@ int wino_nbw(const scflow_conv_args& a, int cus) {
   return 2 * wino_blocks(a) * (round_up(a.cout, 64) / 64) >= 3LL * cus ? 2 : 1;
 }
 bool wino_enabled(int kh) {
-  static int on3 = -1, on5 = -1;
-  if (on3 < 0) {
-    const char* e = getenv("SCFLOW_CONV_WINO");  // 0: off, 3: 3×3 only, 5: 1×5/5×1 only
-    const int v = e ? atoi(e) : 1;
-    on3 = v == 1 || v == 3;
-    on5 = v == 1 || v == 5;
-  }
-  return kh == 3 ? on3 : on5;
+  static EnvSwitch wino_sw("SCFLOW_CONV_WINO", 1);  // 0: off, 3: 3×3 only, 5: 1×5/5×1 only
+  const int v = wino_sw.get();
+  return v == 1 || v == (kh == 3 ? 3 : 5);
 }
 
 // XCD-aware block order for a (R row blocks) × (C column blocks) Winograd grid: the number of
@@ -1046,11 +1038,8 @@ bool wino_enabled(int kh) {
 #define WINO_SWZ_DEFAULT 0
 #endif
 int wino_swz(int R, int C) {
-  static int forced = -2;
-  if (forced == -2) {
-    const char* e = getenv("SCFLOW_WINO_SWZ");
-    forced = e ? atoi(e) : -1;
-  }
+  static EnvSwitch swz_sw("SCFLOW_WINO_SWZ", -1);
+  const int forced = swz_sw.get();
   int c = forced >= 0 ? forced : WINO_SWZ_DEFAULT;
   while (c > 1 && (C % c || 8 % c)) c >>= 1;  // largest usable power of two ≤ c
   if (c <= 0 || R % (8 / c)) return 0;
@@ -1082,11 +1071,8 @@ int wino_swz(int R, int C) {
 #define WINO4_MIN_COUT_MULTI 120
 #endif
 bool wino4_pick(const scflow_conv_args& a) {
-  static int mode = -1;
-  if (mode < 0) {
-    const char* e = getenv("SCFLOW_CONV_WINO4");
-    mode = e ? atoi(e) : WINO4_DEFAULT;
-  }
+  static EnvSwitch wino4_sw("SCFLOW_CONV_WINO4", WINO4_DEFAULT);
+  const int mode = wino4_sw.get();
   if (!mode || !wino4_shape(a)) return false;
   if (mode == 2 || a.cout >= WINO4_MIN_COUT) return true;
   const long long tiles = (long long)a.n * (a.h / 4) * (a.w / 4);
@@ -1099,12 +1085,7 @@ template <int W, int NBW>
 int launch_wino_w(WinoParams p, hipStream_t st) {
   using G = WinoGeom<W>;
   const size_t lds = wino_lds_bytes<W, NBW>();
-  static bool attr = false;
-  if (lds > 64 * 1024 && !attr) {
-    (void)hipFuncSetAttribute((const void*)conv_wino_kernel<W, NBW>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  allow_big_lds<conv_wino_kernel<W, NBW>>(lds);
   dim3 grid(p.a.n * (p.a.h / G::OROWS) * G::XB, round_up(p.a.cout, 32 * NBW) / (32 * NBW));
   p.swz_c = wino_swz(grid.x, grid.y);
   p.stamps = g_wino_stamps;
@@ -1116,12 +1097,7 @@ template <int DIR, int W, int NBW, int EPI>
 int launch_wino5_k(Wino5Params p, hipStream_t st) {
   using G = Wino5Geom<DIR, W>;
   const size_t lds = wino5_lds_bytes<DIR, W, NBW>();
-  static bool attr = false;
-  if (lds > 64 * 1024 && !attr) {
-    (void)hipFuncSetAttribute((const void*)conv_wino5_kernel<DIR, W, NBW, EPI>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  allow_big_lds<conv_wino5_kernel<DIR, W, NBW, EPI>>(lds);
   dim3 grid(p.a.n * (p.a.h / G::OROWS) * (W / G::OCOLS), round_up(p.a.cout, 32 * NBW) / (32 * NBW));
   p.swz_c = wino_swz(grid.x, grid.y);
   p.stamps = g_wino_stamps;
@@ -1175,11 +1151,8 @@ int launch_wino(const scflow_conv_args& a, hipStream_t st) {
 // N=64 convs: 85 vs 54 TF, N=192: 94 vs 91 TF; z|r and the 512-wide heads prefer 128).
 // SCFLOW_CONV_TILE_M=64|128 forces one (tuning only).
 int pick_tile_m(long long m, int ntiles) {
-  static int forced = -1;
-  if (forced < 0) {
-    const char* e = getenv("SCFLOW_CONV_TILE_M");
-    forced = e ? atoi(e) : 0;
-  }
+  static EnvSwitch tile_m_sw("SCFLOW_CONV_TILE_M", 0);
+  const int forced = tile_m_sw.get();
   if (forced == 64 || forced == 128) return forced;
   const long long wg = (m / 128) * ntiles;
   if (wg >= 512) return 128;
@@ -1196,11 +1169,8 @@ size_t mfma_lds(int hr, int hc, int taps, int bk) {
 // 1.5 rounds; 85 → 101 TFLOP/s at 8).  Resident workgroups per CU are capped by VGPRs at
 // 2 (128-pixel tiles) / 3 (64).  SCFLOW_CONV_BK=8|16 forces one (tuning only).
 int pick_bk(int kh, int kw, int tm, int hr, int hc, long long wgs, int cus) {
-  static int forced = -1;
-  if (forced < 0) {
-    const char* e = getenv("SCFLOW_CONV_BK");
-    forced = e ? atoi(e) : 0;
-  }
+  static EnvSwitch bk_sw("SCFLOW_CONV_BK", 0);
+  const int forced = bk_sw.get();
   if (forced == 8 || forced == 16) return forced;
   auto rounds = [&](int bk) {
     long long per_cu = (long long)(160 * 1024 / mfma_lds(hr, hc, kh * kw, bk));
@@ -1217,18 +1187,14 @@ int pick_bk(int kh, int kw, int tm, int hr, int hc, long long wgs, int cus) {
 // SCFLOW_SMALLCIN_SPLIT=1: the 128-channel small-cin MFMA conv as two workgroups per 64-pixel tile
 // (one per 64-channel half) instead of one (each wave 2 × 32 channels).  Measured: 13.1 -> 12.1 us
 // in isolation (7x7 2->128, B=16), no gain inside the decoder (5.263 vs 5.233 ms/forward), so off.
-bool smallcin_split() {  // cached (scflow_debug_reload_switches)
+bool smallcin_split() {
   static EnvSwitch sw("SCFLOW_SMALLCIN_SPLIT", 0);
   return sw.get() != 0;
 }
 
 bool conv1x1_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("SCFLOW_CONV1X1");
-    on = !(e && e[0] == '0');
-  }
-  return on != 0;
+  static EnvSwitch conv1x1_sw("SCFLOW_CONV1X1", 1);
+  return conv1x1_sw.get() != 0;
 }
 
 // tile rows / halo rows / tile size for a launch (shared by the launcher and scflow_conv_pick_bk)
@@ -1244,12 +1210,7 @@ template <int EPI, int KH, int KW, int TM, int BKS>
 int launch_mfma_bk(MfmaParams p, Geometry g, hipStream_t st) {
   p.nst = (g.cp0 + g.cp1) / BKS;
   const size_t lds = mfma_lds(g.hr, g.hc, g.taps, BKS);
-  static bool attr = false;
-  if (lds > 64 * 1024 && !attr) {
-    (void)hipFuncSetAttribute((const void*)conv_mfma_kernel<EPI, KH, KW, TM, BKS>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  allow_big_lds<conv_mfma_kernel<EPI, KH, KW, TM, BKS>>(lds);
   dim3 grid(p.a.n * (g.oh / g.tr), g.npad / BN);
   conv_mfma_kernel<EPI, KH, KW, TM, BKS><<<grid, 256, lds, st>>>(p);
   return scflow_launch_status();
@@ -1288,12 +1249,8 @@ int dispatch_mfma(const MfmaParams& p, const Geometry& g, hipStream_t st) {
 // ---- wide 1×1 (conv1x1w.h): which shapes, how packed, how launched
 // SCFLOW_CONV1X1W=0 keeps the 1×1 convs on conv1x1_kernel (A/B)
 bool conv1x1w_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("SCFLOW_CONV1X1W");
-    on = !(e && e[0] == '0');
-  }
-  return on != 0;
+  static EnvSwitch conv1x1w_sw("SCFLOW_CONV1X1W", 1);
+  return conv1x1w_sw.get() != 0;
 }
 int conv1x1w_kb(int c0) { return (c0 + 7) / 8; }
 bool conv1x1w_kb_ok(int kb) { return kb == 41 || kb == 32 || kb == 16; }
@@ -1311,12 +1268,7 @@ long long conv1x1w_packed_size(int cout, int c0) {
 template <int KB>
 int launch_conv1x1w_kb(const scflow_conv_args& a, hipStream_t st) {
   const size_t lds = conv1x1w_lds_bytes<KB>();
-  static bool attr = false;
-  if (lds > 64 * 1024 && !attr) {
-    (void)hipFuncSetAttribute((const void*)conv1x1w_kernel<KB>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  allow_big_lds<conv1x1w_kernel<KB>>(lds);
   const long long M = (long long)a.n * a.h * a.w;
   conv1x1w_kernel<KB><<<(unsigned)((M + W1_PX - 1) / W1_PX), 256, lds, st>>>(a);
   return scflow_launch_status();
@@ -1473,6 +1425,26 @@ bool conv_args_valid(const scflow_conv_args& a) {
   return false;
 }
 
+// The whole-halo thin conv (conv_thin_full_kernel) of a tiled, single-source launch when `a` is
+// a KH×KW conv to CO channels whose halo, weights and staging fit: true after launching.
+template <int CO, int KH, int KW>
+static bool try_thin_full(const scflow_conv_args& a, const Geometry& g, hipStream_t st) {
+  if (a.cout != CO || a.kh != KH || a.kw != KW) return false;
+  const int tr = 64 / g.ow;
+  const size_t nh4 = (size_t)(tr + KH - 1) * (g.ow + KW - 1) * (a.c0 / 4);
+  size_t lds = sizeof(float) * (size_t)(tr + KH - 1) * (g.ow + KW - 1) * thinf_ld(a.c0);
+  if (lds < sizeof(float) * THINF_WAVES * CO * 64) lds = sizeof(float) * THINF_WAVES * CO * 64;
+  const size_t nw4 = (size_t)KH * KW * a.c0 * CO / 4;
+  lds += 16 * nw4;  // the weights behind the halo
+  if (lds > 160 * 1024 || nh4 > (size_t)12 * THINF_WAVES * 64 || nw4 > (size_t)2 * THINF_WAVES * 64 ||
+      !aligned16(a.weight))
+    return false;
+  allow_big_lds<conv_thin_full_kernel<CO, KH, KW>>(lds);
+  const unsigned blocks = (unsigned)(a.n * (g.oh / tr));
+  conv_thin_full_kernel<CO, KH, KW><<<blocks, THINF_WAVES * 64, lds, st>>>(a, g.oh, g.ow, g_wino_stamps);
+  return true;
+}
+
 SCFLOW_API int scflow_conv2d(const scflow_conv_args* args, void* stream) {
   if (!args) return SCFLOW_EINVAL;
   const scflow_conv_args& a = *args;
@@ -1588,19 +1560,11 @@ SCFLOW_API int scflow_conv2d(const scflow_conv_args* args, void* stream) {
     return scflow_launch_status();
   }
   // whole-halo variant: one source, channels a multiple of 64, the halo within 160 KB of LDS
-  static const bool thin_full_off = [] {
-    const char* e = getenv("SCFLOW_THIN_FULL");
-    return e && e[0] == '0';
-  }();
-  if (tiled && !thin_full_off && a.c1 == 0 && a.c0 % (4 * THINF_WAVES) == 0) {
-    const int tr = 64 / g.ow;
-    const unsigned blocks = (unsigned)(a.n * (g.oh / tr));
-#define SCFLOW_THINF(CO, KH_, KW_)                                                                if (a.cout == CO && a.kh == KH_ && a.kw == KW_) {                                                 const size_t nh4 = (size_t)(tr + KH_ - 1) * (g.ow + KW_ - 1) * (a.c0 / 4);                      size_t lds = sizeof(float) * (size_t)(tr + KH_ - 1) * (g.ow + KW_ - 1) * thinf_ld(a.c0);        if (lds < sizeof(float) * THINF_WAVES * CO * 64) lds = sizeof(float) * THINF_WAVES * CO * 64;     const size_t nw4 = (size_t)KH_ * KW_ * a.c0 * CO / 4;                                           lds += 16 * nw4; /* the weights behind the halo */                                             if (lds <= 160 * 1024 && nh4 <= (size_t)12 * THINF_WAVES * 64 && nw4 <= (size_t)2 * THINF_WAVES * 64 && aligned16(a.weight)) {                                  static bool attr = false;                                                                       if (!attr) {                                                                                      (void)hipFuncSetAttribute((const void*)conv_thin_full_kernel<CO, KH_, KW_>,                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);              attr = true;                                                                                  }                                                                                               conv_thin_full_kernel<CO, KH_, KW_><<<blocks, THINF_WAVES * 64, lds, st>>>(a, g.oh, g.ow, g_wino_stamps);       return scflow_launch_status();                                                                }                                                                                             }
-    // (1×1: the chunked kernel below is faster — its 32-channel chunks need no halo)
-    SCFLOW_THINF(1, 3, 3)
-    SCFLOW_THINF(2, 3, 3)
-#undef SCFLOW_THINF
-  }
+  // (1×1: the chunked kernel below is faster — its 32-channel chunks need no halo)
+  static EnvSwitch thin_full_sw("SCFLOW_THIN_FULL", 1);
+  if (tiled && thin_full_sw.get() && a.c1 == 0 && a.c0 % (4 * THINF_WAVES) == 0 &&
+      (try_thin_full<1, 3, 3>(a, g, st) || try_thin_full<2, 3, 3>(a, g, st)))
+    return scflow_launch_status();
   if (tiled) {
     const int tr = 64 / g.ow;
     const unsigned blocks = (unsigned)(a.n * (g.oh / tr));
@@ -1609,9 +1573,7 @@ SCFLOW_API int scflow_conv2d(const scflow_conv_args* args, void* stream) {
     size_t lds = sizeof(float) * (size_t)(tr + KH_ - 1) * (g.ow + KW_ - 1) * THIN_LD;           \
     if (lds < sizeof(float) * 4 * CO * 64) lds = sizeof(float) * 4 * CO * 64;                    \
     lds += sizeof(float) * (size_t)KH_ * KW_ * (a.c0 + a.c1) * CO; /* weights */                \
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)conv_thin_kernel<CO, KH_, KW_>,  \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize,    \
-                                                  160 * 1024);                                   \
+    allow_big_lds<conv_thin_kernel<CO, KH_, KW_>>(lds);                                         \
     conv_thin_kernel<CO, KH_, KW_><<<blocks, 256, lds, st>>>(a, g.oh, g.ow);                    \
     return scflow_launch_status();                                                              \
   }

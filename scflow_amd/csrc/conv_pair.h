@@ -93,12 +93,7 @@ int launch_wino_pair(const WinoParams& pa, const WinoParams& pb, int gxa, int gy
                      hipStream_t st) {
   const size_t la = wino_lds_bytes<W, NA>(), lb = wino_lds_bytes<W, NB>();
   const size_t lds = la > lb ? la : lb;
-  static bool attr = false;
-  if (lds > 64 * 1024 && !attr) {
-    (void)hipFuncSetAttribute((const void*)wino_pair_kernel<W, NA, NB>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  allow_big_lds<wino_pair_kernel<W, NA, NB>>(lds);
   wino_pair_kernel<W, NA, NB><<<gxa * gya + gxb * gyb, 256, lds, st>>>(pa, pb, gxa, gya, gxb, gyb);
   return scflow_launch_status();
 }

@@ -475,22 +475,13 @@ long long wino4_workspace_bytes(const scflow_conv_args& a) {
   return ntb * nsub * W4P * 1024;
 }
 
-template <int ACT, int D>
-void w4_set_lds() {
-  (void)hipFuncSetAttribute((const void*)conv_wino4_kernel<ACT, D>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-
 template <int D>
 int launch_wino4_gemm(const Wino4Params& p, dim3 grid, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {  // W4_LDS > 64 KiB: opt every instantiation in once
-    w4_set_lds<SCFLOW_ACT_RELU, D>();
-    w4_set_lds<SCFLOW_ACT_SIGMOID, D>();
-    w4_set_lds<SCFLOW_ACT_TANH, D>();
-    w4_set_lds<SCFLOW_ACT_NONE, D>();
-    attr = true;
-  }
+  // W4_LDS > 64 KiB: every instantiation is opted in at the first launch of any
+  allow_big_lds<conv_wino4_kernel<SCFLOW_ACT_RELU, D>>(W4_LDS);
+  allow_big_lds<conv_wino4_kernel<SCFLOW_ACT_SIGMOID, D>>(W4_LDS);
+  allow_big_lds<conv_wino4_kernel<SCFLOW_ACT_TANH, D>>(W4_LDS);
+  allow_big_lds<conv_wino4_kernel<SCFLOW_ACT_NONE, D>>(W4_LDS);
   switch (p.a.act) {  // the activation as a template argument: one epilogue body per kernel
     case SCFLOW_ACT_RELU: conv_wino4_kernel<SCFLOW_ACT_RELU, D><<<grid, 256, W4_LDS, st>>>(p); break;
     case SCFLOW_ACT_SIGMOID: conv_wino4_kernel<SCFLOW_ACT_SIGMOID, D><<<grid, 256, W4_LDS, st>>>(p); break;

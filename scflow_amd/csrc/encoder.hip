@@ -567,12 +567,7 @@ int launch_enc(EncParams p, hipStream_t st) {
   p.arp4 = enc_row_pitch<S>(p.tc, TM, p.hc);
   const size_t lds = sizeof(float) * ((size_t)p.hr * p.arp4 * 4 + (size_t)KH * KW * EBN * ELDA);
   if ((size_t)p.hr * p.hc * (EBK / 4) > (size_t)256 * enc_na(TM, KH, KW, S)) return SCFLOW_EUNSUPPORTED;
-  static bool attr = false;
-  if (lds > 64 * 1024 && !attr) {
-    (void)hipFuncSetAttribute((const void*)enc_conv_kernel<KH, KW, S, TM, NORM>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  allow_big_lds<enc_conv_kernel<KH, KW, S, TM, NORM>>(lds);
   dim3 grid(p.a.n * (p.oh / p.tr) * (p.ow / p.tc), rup(p.a.cout, EBN) / EBN,
             p.a.ksplit > 1 ? p.a.ksplit : 1);
   enc_conv_kernel<KH, KW, S, TM, NORM><<<grid, 256, lds, st>>>(p);
@@ -662,18 +657,12 @@ SCFLOW_API int scflow_enc_stem(const float* img, const float* packed, const floa
   if (oh <= 0 || ow <= 0) return SCFLOW_EINVAL;
   const unsigned tiles = (unsigned)((long long)n * oh * ((ow + 31) / 32));
   hipStream_t st = (hipStream_t)stream;
-  static int mfma = -1;  // SCFLOW_STEM_MFMA=0 keeps the VALU kernel (A/B only)
-  if (mfma < 0) {
-    const char* e = getenv("SCFLOW_STEM_MFMA");
-    mfma = e ? atoi(e) != 0 : 1;
-  }
-  if (mfma && npad == 64 && cin == 3 && kh == 7 && kw == 7 && (stride == 1 || stride == 2)) {
-    static int srows = 0;  // output rows per workgroup (SCFLOW_STEM_ROWS=4|8|16, tuning)
-    if (!srows) {
-      const char* e = getenv("SCFLOW_STEM_ROWS");
-      srows = e ? atoi(e) : 8;  // 4 / 8 / 16 rows: 226 / 208 / 230 us per e2e stem call
-      if (srows != 4 && srows != 16) srows = 8;
-    }
+  static EnvSwitch mfma_sw("SCFLOW_STEM_MFMA", 1);  // 0 keeps the VALU kernel (A/B only)
+  if (mfma_sw.get() && npad == 64 && cin == 3 && kh == 7 && kw == 7 && (stride == 1 || stride == 2)) {
+    // output rows per workgroup (tuning): 4 / 8 / 16 rows, 226 / 208 / 230 us per e2e stem call
+    static EnvSwitch rows_sw("SCFLOW_STEM_ROWS", 8);
+    int srows = rows_sw.get();
+    if (srows != 4 && srows != 16) srows = 8;
     const unsigned rows = (unsigned)((long long)n * ((oh + srows - 1) / srows) * ((ow + 127) / 128));
 #define STEM_LAUNCH(S_, R_)                                                                   \
   enc_stem_mfma_kernel<3, 7, 7, S_, R_><<<rows, 256, 0, st>>>(img, packed, bias, out_scale, \

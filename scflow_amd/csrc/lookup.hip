@@ -676,23 +676,16 @@ static unsigned long long* g_lk_stamps = nullptr;
 // configs[4] (B=32, 64x64), where their 4 KB per pixel of LDS leaves 2 workgroups per CU instead
 // of 3.  SCFLOW_LK_TILEREG=0 / 1 forces them off / on.
 static bool lk_tile_regions(int h, int w) {
-  static int v = -2;
-  if (v == -2) {
-    const char* e = getenv("SCFLOW_LK_TILEREG");
-    v = e ? atoi(e) : -1;
-  }
+  static EnvSwitch tilereg_sw("SCFLOW_LK_TILEREG", -1);
+  const int v = tilereg_sw.get();
   return v < 0 ? (long long)h * w <= 32 * 32 : v != 0;
 }
 
 // TB tile-row regions for the tiled lookup on maps where the tile regions are off (round 5;
 // SCFLOW_LK_TB=0 gives the b32-gather regions)
 static bool lk_tile_rows() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("SCFLOW_LK_TB");
-    v = e ? (atoi(e) != 0) : 1;
-  }
-  return v != 0;
+  static EnvSwitch tb_sw("SCFLOW_LK_TB", 1);
+  return tb_sw.get() != 0;
 }
 
 static int corr_lookup_launch(const float* pyr, const float* flow, int flow_layout, float* out,

@@ -461,12 +461,7 @@ static int lookup_conv1x1_launch(const float* pyr, const float* flow, const floa
   a.stamps = g_lc_stamps;
 #endif
   const size_t lds = (size_t)scflow_corr_lookup_conv1x1_lds_bytes();
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)corr_lookup_conv1x1_kernel,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  allow_big_lds<corr_lookup_conv1x1_kernel>(lds);
   const long long M = (long long)n * h * w;
   corr_lookup_conv1x1_kernel<<<(unsigned)((M + LC_PX - 1) / LC_PX), LC_THREADS, lds, (hipStream_t)stream>>>(a);
   return scflow_launch_status();

@@ -369,12 +369,9 @@ __device__ __forceinline__ void pose_step_body(const PoseStepArgs& a, float* sh,
 // workgroups per image of the full-resolution part from a given pose (the decoder's deferred,
 // side-stream launch); SCFLOW_FULLRES_BLOCKS overrides the default 64 (tuning)
 static inline int fullres_blocks() {
-  static int v = 0;
-  if (v == 0) {
-    const char* e = getenv("SCFLOW_FULLRES_BLOCKS");
-    v = e && atoi(e) > 0 ? atoi(e) : 64;
-  }
-  return v;
+  static EnvSwitch blocks_sw("SCFLOW_FULLRES_BLOCKS", 64);
+  const int v = blocks_sw.get();
+  return v > 0 ? v : 64;
 }
 
 static inline int pose_step_args(PoseStepArgs* a, const float* drot6, const float* dt,

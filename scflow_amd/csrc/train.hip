@@ -680,10 +680,8 @@ bool wgrad_geometry(const scflow_wgrad_args& a, WgParams* P, int* splits) {
   const int tiles = P->co_tiles * ci_tiles;
   const int occ = a.kh * a.kw >= 9 ? 1 : 2;  // the kernel's resident workgroups per CU
   int want = (occ * device_cus() + tiles - 1) / tiles;
-  static const int forced = [] {  // SCFLOW_WGRAD_SPLITS=k forces k splits (tuning only)
-    const char* e = getenv("SCFLOW_WGRAD_SPLITS");
-    return e ? atoi(e) : 0;
-  }();
+  static EnvSwitch splits_sw("SCFLOW_WGRAD_SPLITS", 0);  // k > 0 forces k splits (tuning only)
+  const int forced = splits_sw.get();
   if (forced > 0) {
     want = forced < P->nchunks ? forced : P->nchunks;
     P->cps = (P->nchunks + want - 1) / want;
@@ -731,11 +729,8 @@ struct WtParams {
 
 // nseg = 0: the workspace query (the whole walk as one segment, rows for any segment count)
 bool wthin_geometry(const scflow_wgrad_args& a, WtParams* P, int nseg = 1) {
-  static const bool off = [] {
-    const char* e = getenv("SCFLOW_WGRAD_THIN");
-    return e && e[0] == '0';
-  }();
-  if (off) return false;
+  static EnvSwitch wthin_sw("SCFLOW_WGRAD_THIN", 1);
+  if (!wthin_sw.get()) return false;
   const int cin = a.cin0 + a.cin1;
   // 7×7 (the stem, the flow encoders' 2→128) stays on im2col + GEMM: measured faster there
   // (batched over the decoder's 8 uses too: 246 µs on this kernel, where the 14 scalar input
@@ -1856,17 +1851,13 @@ static int wgrad_direct_launch(const scflow_wgrad_args& a, const WgSegs& sg, hip
                    a.s0 % 4 == 0 && aligned16(a.src0) &&
                    (a.cin1 == 0 || (a.cin1 % 4 == 0 && a.s1 % 4 == 0 && aligned16(a.src1)));
   // (3×3: one workgroup per CU; SCFLOW_WGRAD_KS=1 keeps one wave set, tuning only)
-  static const int ks_env = [] {
-    const char* e = getenv("SCFLOW_WGRAD_KS");
-    return e ? atoi(e) : 2;
-  }();
+  static EnvSwitch ks_sw("SCFLOW_WGRAD_KS", 2);
+  const int ks_env = ks_sw.get();
   // the GRU's 1×5 / 5×1: two wave sets when cout ≤ 128 (q: 90 → 81 µs for 5×1, 80 → 71 for 1×5
   // at configs[3]); one for the 256-wide z | r, which two sets slow (131 → 137, 146 → 155 µs).
   // SCFLOW_WGRAD_KS5=0 never, 2 always (tuning)
-  static const int ks5_env = [] {
-    const char* e = getenv("SCFLOW_WGRAD_KS5");
-    return e ? atoi(e) : 1;
-  }();
+  static EnvSwitch ks5_sw("SCFLOW_WGRAD_KS5", 1);
+  const int ks5_env = ks5_sw.get();
   const size_t lds1 = sizeof(float) * (size_t)(P.cp + P.hr * P.hc) * WT;
   const bool ks5 = taps == 5 && (ks5_env == 2 || (ks5_env == 1 && a.cout <= 128));
   const int occ = taps >= 9 || ks5 ? 1 : 2;
@@ -2051,11 +2042,8 @@ static int corr_lookup_backward_launch(const float* dout, int out_layout, int ou
   const long long total = (long long)n * h * w * num_levels * D;
   const unsigned blocks = (unsigned)((total + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
-  static const bool win_off = [] {
-    const char* e = getenv("SCFLOW_LOOKUP_BWD_WIN");
-    return e && e[0] == '0';
-  }();
-  if (radius >= 1 && radius <= 4 && !win_off) {
+  static EnvSwitch win_sw("SCFLOW_LOOKUP_BWD_WIN", 1);
+  if (radius >= 1 && radius <= 4 && win_sw.get()) {
     const long long tw = (long long)n * h * w * num_levels;
     const unsigned bw = (unsigned)((tw + 255) / 256);
     switch (radius) {

@@ -157,11 +157,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_1x1_kernel(W1Params P, float* __
 }
 
 bool w1_geometry(const scflow_wgrad_args& a, int nseg, W1Params* P) {
-  static const bool off = [] {
-    const char* e = getenv("SCFLOW_WGRAD_1X1");
-    return e && e[0] == '0';
-  }();
-  if (off) return false;
+  static EnvSwitch w1_sw("SCFLOW_WGRAD_1X1", 1);
+  if (!w1_sw.get()) return false;
   if (a.kh != 1 || a.kw != 1 || a.ph != 0 || a.pw != 0 || (a.stride != 1 && a.stride != 2))
     return false;
   const int cin = a.cin0 + a.cin1;

@@ -444,11 +444,8 @@ __global__ __launch_bounds__(256) void wwino_reduce_kernel(
 
 // shapes: 3×3, stride 1, pad 1, h % 4 == 0, w % 32 == 0, float4-aligned channel groups
 bool wwino_geometry(const scflow_wgrad_args& a, WwParams* P) {
-  static const int off = [] {
-    const char* e = getenv("SCFLOW_WGRAD_WINO");
-    return e && e[0] == '0';
-  }();
-  if (off) return false;
+  static EnvSwitch wwino_sw("SCFLOW_WGRAD_WINO", 1);
+  if (!wwino_sw.get()) return false;
   const int cin = a.cin0 + a.cin1;
   if (a.kh != 3 || a.kw != 3 || a.stride != 1 || a.ph != 1 || a.pw != 1) return false;
   if (a.h % 4 || a.w % 32) return false;
@@ -488,12 +485,7 @@ int wwino_launch(const WwParams& P, hipStream_t st) {
   float* slab = a.workspace;
   float* bslab = a.db ? a.workspace + (size_t)splits * 16 * P.copad * P.cinp : nullptr;
   const size_t lds = sizeof(float) * (size_t)(2 * (WWD_FL + WWX_FL));
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)wgrad_wino_kernel,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  allow_big_lds<wgrad_wino_kernel>(lds);
   const dim3 grid((unsigned)(P.co_tiles * (P.cinp / WWCI)), (unsigned)splits);
   wgrad_wino_kernel<<<grid, WW_NT, lds, st>>>(P, slab, bslab);
   int rc = scflow_launch_status();

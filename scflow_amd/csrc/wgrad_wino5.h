@@ -374,11 +374,8 @@ __global__ __launch_bounds__(256) void wwino5_reduce_kernel(
 // shapes: 1×5 (pad 0, 2) or 5×1 (pad 2, 0), stride 1, h % 4 == 0, w % 32 == 0, float4-aligned
 // channel groups, cout ≥ 64 (narrower outputs stay on wgrad_kernel / wthin)
 bool wwino5_geometry(const scflow_wgrad_args& a, W5wParams* P) {
-  static const int off = [] {
-    const char* e = getenv("SCFLOW_WGRAD_WINO5");
-    return e && e[0] == '0';
-  }();
-  if (off) return false;
+  static EnvSwitch wwino5_sw("SCFLOW_WGRAD_WINO5", 1);
+  if (!wwino5_sw.get()) return false;
   const int cin = a.cin0 + a.cin1;
   if (a.stride != 1) return false;
   if (a.kh == 1 && a.kw == 5 && a.ph == 0 && a.pw == 2) {
@@ -424,12 +421,7 @@ int wwino5_launch(const W5wParams& P, hipStream_t st) {
   float* slab = a.workspace;
   float* bslab = a.db ? a.workspace + (size_t)splits * 8 * P.copad * P.cinp : nullptr;
   const size_t lds = sizeof(float) * (size_t)(W5W_DFL + W5W_XFL) * 2;  // double-buffered
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)wgrad_wino5_kernel,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  allow_big_lds<wgrad_wino5_kernel>(lds);
   const dim3 grid((unsigned)(P.co_tiles * (P.cinp / W5W_CI)), (unsigned)splits);
   wgrad_wino5_kernel<<<grid, W5W_NT, lds, st>>>(P, slab, bslab);
   int rc = scflow_launch_status();

@@ -86,12 +86,7 @@ __global__ __launch_bounds__(256) void xhead_pred_sum_kernel(const float* __rest
 
 template <int D>
 int launch_wino4_pred_gemm(const Wino4Params& p, dim3 grid, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv_wino4_kernel<SCFLOW_ACT_RELU, D, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  allow_big_lds<conv_wino4_kernel<SCFLOW_ACT_RELU, D, true>>(W4_PRED_LDS);
   conv_wino4_kernel<SCFLOW_ACT_RELU, D, true><<<grid, 256, W4_PRED_LDS, st>>>(p);
   return scflow_launch_status();
 }

@@ -1,4 +1,5 @@
 """Shared test helpers: golden fixtures, synthetic inputs, the oracle's state dict."""
+import contextlib
 import os
 from functools import lru_cache
 
@@ -22,6 +23,21 @@ def golden(name):
 def t(a, dtype=None):
     x = torch.from_numpy(np.ascontiguousarray(a))
     return x if dtype is None else x.to(dtype)
+
+
+@contextlib.contextmanager
+def switches(monkeypatch, **env):
+    """The HIP library's switches ("Switches") set for the block, in-process."""
+    from scflow_amd._lib import reload_switches
+    for k, v in env.items():
+        monkeypatch.setenv(k, str(v))
+    reload_switches()
+    try:
+        yield
+    finally:
+        for k in env:
+            monkeypatch.delenv(k)
+        reload_switches()
 
 
 def reference_state_shapes():

@@ -13,7 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.helpers import encoder_state_dict, golden, refine_inputs, refiner_state_dict, t
+from tests.helpers import encoder_state_dict, golden, refine_inputs, refiner_state_dict, switches, t
 
 orc = pytest.importorskip("oracle.scflow_oracle")
 pytestmark = pytest.mark.gpu
@@ -104,6 +104,24 @@ def test_enc_stem_stats_apply_match_torch():
     np.testing.assert_allclose(out.cpu().permute(0, 3, 1, 2).numpy(), ref.numpy(), rtol=1e-4, atol=1e-4)
     ref_y = torch.relu(F.instance_norm(ref, eps=1e-5) + idt.permute(0, 3, 1, 2))
     np.testing.assert_allclose(y.cpu().permute(0, 3, 1, 2).numpy(), ref_y.numpy(), rtol=1e-4, atol=2e-4)
+
+
+@pytest.mark.parametrize("env", [{"SCFLOW_STEM_MFMA": "0"}, {"SCFLOW_STEM_ROWS": "4"},
+                                 {"SCFLOW_STEM_ROWS": "16"}], ids=["valu", "rows4", "rows16"])
+def test_enc_stem_switches_match_torch(env, monkeypatch):
+    """The stem's VALU kernel (SCFLOW_STEM_MFMA = 0) and the MFMA kernel with 4 / 16 output rows
+    per workgroup (SCFLOW_STEM_ROWS), toggled in-process, at the stem test's tolerance."""
+    from scflow_amd import ops
+    g = torch.Generator().manual_seed(10)
+    x = torch.rand(1, 3, 64, 64, generator=g)
+    wt = torch.randn(64, 3, 7, 7, generator=g) / 12
+    b = torch.randn(64, generator=g) * 0.1
+    ref = F.conv2d(x, wt, b, stride=2, padding=3)
+    out = torch.empty(1, 32, 32, 64, device="cuda")
+    with switches(monkeypatch, **env):
+        ops.enc_stem(x.cuda(), ops.enc_stem_pack(wt.cuda()), b.cuda(), 64, 7, 2, 3, out)
+        torch.cuda.synchronize()
+    np.testing.assert_allclose(out.cpu().permute(0, 3, 1, 2).numpy(), ref.numpy(), rtol=1e-4, atol=1e-4)
 
 
 @pytest.mark.parametrize("norm,seed", [("IN", 1), ("BN", 2)])

@@ -13,7 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.helpers import golden, t
+from tests.helpers import golden, switches, t
 
 pytestmark = pytest.mark.gpu
 
@@ -272,6 +272,65 @@ def test_conv2d_thin_contraction(ops, case, thinz, monkeypatch):
         monkeypatch.delenv("SCFLOW_THINZ")
         reload_switches()
     close(got, ref, 2e-6 * np.sqrt(c0 * k * k) * 4, 1e-5, f"thin conv {case} thinz={thinz}")
+
+
+@pytest.mark.parametrize("env,case", [
+    # channels per workgroup forced: a channel tail on both sides (36 in, 100 out)
+    ({"SCFLOW_WINO_NBW": 1}, (2, 8, 32, 36, 0, 100, 3, 1, None)),
+    ({"SCFLOW_WINO_NBW": 2}, (2, 8, 32, 36, 0, 100, 3, 1, None)),
+    # XCD-aware block order: 16 row blocks × 4 column blocks as 4 × 2 and 2 × 4 parts
+    ({"SCFLOW_WINO_NBW": 1, "SCFLOW_WINO_SWZ": 2}, (2, 32, 32, 32, 0, 128, 3, 1, "ReLU")),
+    ({"SCFLOW_WINO_NBW": 1, "SCFLOW_WINO_SWZ": 4}, (2, 32, 32, 32, 0, 128, 3, 1, "ReLU")),
+], ids=["nbw1", "nbw2", "swz2", "swz4"])
+def test_conv2d_winograd_switches(ops, env, case, monkeypatch):
+    """F(2×2,3×3) with its tuning switches forced (SCFLOW_WINO_NBW, SCFLOW_WINO_SWZ), against the
+    fp64 conv at test_conv2d_winograd's tolerance."""
+    from scflow_amd._lib import CONV_WINO
+    n, h, w, c0, c1, cout, k, pad, act = case
+    with switches(monkeypatch, **env):
+        got, ref = _conv_case(ops, n, h, w, c0, c1, cout, k, pad, act, bk=CONV_WINO)
+    close(got, ref, 2e-6 * np.sqrt((c0 + c1) * k * k) * 4, 1e-5, f"winograd conv {case} {env}")
+
+
+@pytest.mark.parametrize("env,case", [
+    # 1×1 on 128-pixel tiles (512 workgroups) kept on conv_mfma_kernel
+    ({"SCFLOW_CONV1X1": 0}, (4, 64, 64, 32, 0, 256, 1, 0, "ReLU")),
+    # thin 3×3 → 2 on the chunked kernel instead of the whole-halo one
+    ({"SCFLOW_THIN_FULL": 0}, (1, 2, 32, 64, 0, 2, 3, 1, None)),
+], ids=["conv1x1_off", "thin_full_off"])
+def test_conv2d_direct_switches(ops, env, case, monkeypatch):
+    """The kernels that SCFLOW_CONV1X1 = 0 / SCFLOW_THIN_FULL = 0 fall back to, against the fp64
+    conv at test_conv2d_variants' tolerance."""
+    n, h, w, c0, c1, cout, k, pad, act = case
+    with switches(monkeypatch, **env):
+        got, ref = _conv_case(ops, n, h, w, c0, c1, cout, k, pad, act, seed=5)
+    close(got, ref, 2e-6 * np.sqrt((c0 + c1) * k * k) * 4, 1e-5, f"conv {case} {env}")
+
+
+@pytest.mark.parametrize("h,w,radius,env", [
+    (h, w, 4, env) for h, w in ((32, 32), (32, 64))
+    for env in ({"SCFLOW_LK_TILEREG": 0}, {"SCFLOW_LK_TILEREG": 1},
+                {"SCFLOW_LK_TILEREG": 0, "SCFLOW_LK_TB": 0})
+] + [(32, 32, 1, {"SCFLOW_LK_TB": 1}), (32, 32, 1, {"SCFLOW_LK_TB": 0})],
+    ids=lambda v: "-".join(f"{k[10:].lower()}{x}" for k, x in v.items()) if isinstance(v, dict) else None)
+def test_corr_lookup_tiled_region_switches(ops, h, w, radius, env, monkeypatch):
+    """Each region form of the tiled lookup (tile regions: SCFLOW_LK_TILEREG, r = 4 only;
+    tile-row regions; b32-gather regions: SCFLOW_LK_TB = 0) gives exactly the row-major
+    lookup's output, as test_corr_pyramid_tiled_bit_identical asserts for the default form."""
+    g = torch.Generator().manual_seed(29)
+    n, L = 1, 4
+    f1 = torch.randn(n, 16, h, w, generator=g).cuda()
+    f2 = torch.randn(n, 16, h, w, generator=g).cuda()
+    _, lv = ops.corr_pyramid(f1, f2, L)
+    buf = ops.pyramid_buffer(lv, n, h, w)
+    tb = ops.corr_pyramid_tiled(f1, f2, L)
+    flow = ((torch.rand(n, 2, h, w, generator=g) - 0.5) * 1.5 * h).cuda()
+    flow[:, :, 0, 0] = torch.tensor([0.5, -0.5])
+    assert ops.tiled_lookup_ok(h, w, L, radius, True)
+    ref = ops.corr_lookup(buf, flow, n, h, w, L, radius)
+    with switches(monkeypatch, **env):
+        got = ops.corr_lookup(tb, flow, n, h, w, L, radius, tiled=True)
+    assert torch.equal(ref, got), f"tiled lookup {env}: {(ref - got).abs().max().item():.3e}"
 
 
 @pytest.mark.parametrize("bk", [8, 16])
@@ -603,6 +662,37 @@ def test_pose_step_matches_separate_launches(ops, S, s, nxt):
     torch.cuda.synchronize()
     for a, b, nm in ((fa, fc, "flow (given pose)"), (upa, upc, "flow ×8 (given pose)"),
                      (ma, mc, "mask ×8 (given pose)")):
+        assert torch.equal(a, b), nm
+
+
+@pytest.mark.parametrize("blocks", [1, 7])
+def test_pose_step_given_fullres_blocks(ops, blocks, monkeypatch):
+    """The deferred full-resolution part with SCFLOW_FULLRES_BLOCKS workgroups per image (1: one
+    workgroup strides over the whole image; 7: a ragged last stride): bit-identical to
+    pose_update_flow + flow_upsample, as in test_pose_step_matches_separate_launches."""
+    from scflow_amd import synthetic
+    n, S, s = 3, 128, 16
+    sc = synthetic.make_scene(n, S, seed=5)
+    R0, t0, K, depth = (t(sc[k]).cuda() for k in ("ref_rotation", "ref_translation", "internel_k",
+                                                   "depth"))
+    g = torch.Generator().manual_seed(8)
+    drot = (torch.tensor([[1.0, 0, 0, 0, 1.0, 0]]).repeat(n, 1) +
+            0.03 * torch.randn(n, 6, generator=g)).cuda()
+    dt = (0.05 * torch.randn(n, 3, generator=g)).cuda()
+    pts = ops.lift_points(depth, K, R0, t0)
+    lr = torch.randn(n * s * s, 2, generator=g).cuda()
+    delta = torch.randn(n * s * s, 2, generator=g).cuda()
+    mask = torch.rand(n * s * s, 1, generator=g).cuda()
+    Ra, ta = torch.empty(n, 3, 3, device="cuda"), torch.empty(n, 3, device="cuda")
+    fa = torch.empty(n, 2, S, S, device="cuda")
+    ops.pose_update_flow(drot, dt, R0, t0, K, pts, Ra, ta, fa, 400.0)
+    upa, ma = torch.empty(n, 2, S, S, device="cuda"), torch.empty(n, 1, S, S, device="cuda")
+    ops.flow_upsample(lr, delta, mask, n, s, s, S, S, float(S // s), upa, ma)
+    fc, upc, mc = torch.full_like(fa, 7.0), torch.full_like(upa, 7.0), torch.full_like(ma, 7.0)
+    with switches(monkeypatch, SCFLOW_FULLRES_BLOCKS=blocks):
+        ops.pose_step_given(Ra, ta, K, pts, fc, 400.0, lr, delta, mask, upc, mc, s, s, float(S // s))
+        torch.cuda.synchronize()
+    for a, b, nm in ((fa, fc, "flow"), (upa, upc, "flow ×8"), (ma, mc, "mask ×8")):
         assert torch.equal(a, b), nm
 
 

@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.helpers import switches
+
 pytestmark = pytest.mark.gpu
 orc = pytest.importorskip("oracle.scflow_oracle")
 
@@ -392,16 +394,69 @@ def test_corr_pyramid_backward():
     _close(a2.grad, r2.grad, 1e-5, 1e-4, "df2")
 
 
+@pytest.mark.parametrize("env,case", [
+    # (n, h, w, c0, c1, cout, kh, kw)
+    ({"SCFLOW_WGRAD_WINO": 0}, (2, 32, 32, 128, 0, 64, 3, 3)),   # 3×3 on the implicit GEMM
+    # 16-wide 3×3 (implicit GEMM by default): the split count forced, one wave set
+    ({"SCFLOW_WGRAD_SPLITS": 1}, (2, 16, 16, 128, 0, 128, 3, 3)),
+    ({"SCFLOW_WGRAD_SPLITS": 3}, (2, 16, 16, 128, 0, 128, 3, 3)),
+    ({"SCFLOW_WGRAD_KS": 1}, (2, 16, 16, 128, 0, 128, 3, 3)),
+    # 1×5 on the implicit GEMM; one wave set at cout ≤ 128, two above it
+    ({"SCFLOW_WGRAD_WINO5": 0}, (2, 8, 64, 64, 32, 96, 1, 5)),
+    ({"SCFLOW_WGRAD_WINO5": 0, "SCFLOW_WGRAD_KS5": 0}, (2, 8, 64, 64, 32, 96, 1, 5)),
+    ({"SCFLOW_WGRAD_WINO5": 0, "SCFLOW_WGRAD_KS5": 2}, (2, 8, 64, 64, 32, 192, 1, 5)),
+    ({"SCFLOW_WGRAD_1X1": 0}, (2, 32, 32, 128, 64, 96, 1, 1)),   # 1×1 on the implicit GEMM
+    ({"SCFLOW_WGRAD_THIN": 0}, (4, 32, 32, 1, 0, 64, 3, 3)),     # cin 1 on the implicit GEMM
+], ids=["wino0", "splits1", "splits3", "ks1", "wino5_0", "ks5_0", "ks5_2", "1x1_0", "thin0"])
+def test_conv_wgrad_switches(env, case, monkeypatch):
+    """scflow_conv_wgrad with each kernel-choice switch off its default, toggled in-process: the
+    fp64 reference and tolerance of test_conv_wgrad_accumulate_and_split (2e-5 of the gradient's
+    magnitude for the 1×5 shapes, as test_conv_wgrad_wino5), accumulate = 1 onto dw / db."""
+    from scflow_amd import ops
+    from scflow_amd.ops import Chan
+    n, h, w, c0, c1, cout, kh, kw = case
+    g = torch.Generator().manual_seed(sum(case))
+    ph, pw = kh // 2, kw // 2
+    x0 = torch.randn(n, h, w, c0, generator=g)
+    buf = torch.randn(n, h, w, c1 + 8, generator=g)
+    dy = torch.randn(n, h, w, cout, generator=g)
+    xc = torch.cat([x0, buf[..., 4:4 + c1]], -1) if c1 else x0
+    ref = torch.nn.grad.conv2d_weight(xc.permute(0, 3, 1, 2).double(), (cout, c0 + c1, kh, kw),
+                                      dy.permute(0, 3, 1, 2).double(), padding=(ph, pw))
+    dw = torch.ones(cout, c0 + c1, kh, kw).cuda()
+    db = torch.ones(cout).cuda()
+    src1 = Chan(buf.cuda().view(-1, c1 + 8), 4, c1) if c1 else None
+    with switches(monkeypatch,**env):
+        ops.conv_wgrad(dy.cuda().view(-1, cout), x0.cuda(), src1, dw, db, n, h, w, kh, kw, 1, ph, pw,
+                       accumulate=True)
+        torch.cuda.synchronize()
+    if kw == 5:
+        _close(dw - 1, ref, 2e-5, 0.0, f"dw {env}")
+    else:
+        _close(dw - 1, ref, 1e-5, 1e-4 * np.sqrt(n * h * w), f"dw {env}")
+    _close(db - 1, dy.double().sum((0, 1, 2)), 1e-5, 1e-4 * np.sqrt(n * h * w), f"db {env}")
+
+
 @pytest.mark.parametrize("radius,flow_kind", [(4, "rand"), (1, "rand"), (4, "grid"), (6, "rand")])
 def test_corr_lookup_backward(radius, flow_kind):
     """The adjoint of the lookup: ⟨lookup(pyr), g⟩ differentiated w.r.t. the pyramid, with flow
     in ±6 px (zero padding) — against autograd of the oracle's explicit bilinear gather.  "grid":
     flows on the integer / half / quarter / eighth grid (zero where the reference's flow is
     invalid), the coordinates where the float unnormalisation rounds across a tap boundary."""
+    _lookup_backward_case(radius, flow_kind, 2, 16, 16)
+
+
+def test_corr_lookup_backward_per_tap_kernel(monkeypatch):
+    """The same adjoint on the per-tap kernel (SCFLOW_LOOKUP_BWD_WIN = 0), toggled in-process."""
+    with switches(monkeypatch,SCFLOW_LOOKUP_BWD_WIN=0):
+        _lookup_backward_case(4, "rand", 1, 32, 32)
+
+
+def _lookup_backward_case(radius, flow_kind, n, h, w):
     from scflow_amd import ops
     from scflow_amd.train.functions import corr_lookup
     g = torch.Generator().manual_seed(2 + radius)
-    n, c, h, w = 2, 16, 16, 16
+    c = 16
     f1 = torch.randn(n, c, h, w, generator=g)
     f2 = torch.randn(n, c, h, w, generator=g)
     levels = [lv.double().requires_grad_() for lv in orc.corr_pyramid(f1.double(), f2.double(), 4)]

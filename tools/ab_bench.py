@@ -2,7 +2,10 @@
 
 usage: python tools/ab_bench.py [--batch 16] [--rounds 5] [--steps 10] attr=v1,v2 [attr=...]
 e.g.   python tools/ab_bench.py split_pose_conv1=1,0 hoist_context=1,0
-       python tools/ab_bench.py env:SCFLOW_WINO4_DEPTH=0,1   (switches read per launch)
+       python tools/ab_bench.py env:SCFLOW_WINO4_DEPTH=0,1   (a switch of the HIP library: any
+       row of INTEGRATION.md's "Switches" table that takes effect "every launch"; the others do
+       nothing here — a pick/pack-time switch is cached by the decoder's ConvRunners, a Python
+       one was read at import or construction)
        python tools/ab_bench.py mask_flow=0,1 mask_corr=0,1 rep=0,1   (occlusion masking; `rep` is
        not an attribute the decoder reads: its two values repeat every variant, which gives the
        spread between identical runs of one session)
@@ -60,7 +63,7 @@ def main():
             if k.startswith("env:"):
                 os.environ[k[4:]] = str(v)
                 from scflow_amd._lib import reload_switches
-                reload_switches()  # launch-time switches are cached by the library
+                reload_switches()  # the library caches its switches
                 continue
             obj, attr = target(k)
             setattr(obj, attr, v)
