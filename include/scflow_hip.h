@@ -29,6 +29,9 @@
  *   scflow_convex_upsample   <- RAFT's convex ×8 upsampling of the flow and the occlusion (softmax over
  *                               the 3×3 neighbourhood per sub-pixel)   raft_decoder.py:381-416,
  *                               raft_decoder_mask.py:104-160
+ *   scflow_pnp_*             <- BaseFlowRefiner.solve_pose: 2D-3D correspondences + RANSAC-PnP (another
+ *                               algorithm than cv2.solvePnPRansac)   base_flow_refiner.py:99-155,
+ *                               models/utils/pose.py:182-249
  *   scflow_transpose         <- layout plumbing (NCHW <-> channels-last slices), no reference equivalent
  *   scflow_ph_*              <- MultiClassPoseHead.forward                models/head/pose_head.py:201-211
  *   scflow_enc_*             <- RAFTEncoder.forward (Basic; IN / BN)      models/encoder/raft_encoder.py:286-314
@@ -782,6 +785,58 @@ typedef struct {
 } scflow_render_args;
 long long scflow_render_workspace(int n_img, int size, int total_verts);
 int scflow_render(const scflow_render_args* args, void* stream);
+
+/* Batched RANSAC-PnP (replaces BaseFlowRefiner.solve_pose's per-sample host loop,
+ * models/refiner/base_flow_refiner.py:99-155, over get_2d_3d_corr_by_fw_flow and
+ * cv2.solvePnPRansac, models/utils/pose.py:182-249; deliberately not cv2's algorithm — DESIGN.md
+ * §12).  Four stages on the caller's stream, no host synchronisation in or between them, every
+ * result bitwise reproducible (integer sums are the only unordered ones).  hw = h·w pixels per
+ * sample; hyps ≤ SCFLOW_PNP_MAX_HYPS, n·hw < 2^31 and hw ≤ 2^24, else SCFLOW_EUNSUPPORTED.
+ *
+ * scflow_pnp_workspace: *bytes = the size of scflow_pnp_compact's workspace (host only, no GPU).
+ * scflow_pnp_compact: pixel p = y·w + x of sample b is valid when points[b][p].w > 0 (the float4 of
+ *   scflow_lift_points: depth > 0) and, with valid != NULL ([n][hw] floats), valid[b][p] != 0.  The
+ *   valid pixels' rows (X, Y, Z, x + flow_x, y + flow_y) go to corr[b][0 .. count[b]) in ascending
+ *   p (corr [n][hw][5]; later rows are not written), their number to count[b].  flow [n][2][h][w].
+ *   workspace: 16-byte aligned, ≥ scflow_pnp_workspace bytes.
+ * scflow_pnp_hypotheses: hypothesis h of sample b draws the rows s_k = (lowbias32(((b·hyps + h)·4
+ *   + k) ^ seed) · count[b]) >> 32, k = 0..3 (lowbias32: x ^= x>>16; x *= 0x7feb352d; x ^= x>>15;
+ *   x *= 0x846ca68b; x ^= x>>16 on 32 bits; samples [n][hyps][4] receives them, may be NULL),
+ *   solves Grunert's P3P on rows 0..2 in fp64 and keeps the root whose pose reprojects row 3 best.
+ *   Invalid (hyp_valid 0): count[b] < 4, a repeated row, rows 0..2 collinear in the object frame
+ *   (sin² of the angle at row 0 ≤ 1e-4), no positive real root, row 3 behind the camera, or a
+ *   non-finite value.  hyp [n][hyps][12] = K·[R|t] row-major 3×4, hyp_pose [n][hyps][12] = [R|t];
+ *   an invalid hypothesis holds a projection that puts every point behind the camera.  K [n][3][3].
+ * scflow_pnp_score: score[b][h] = the number of rows of corr[b] with camera-frame z > 0 and
+ *   reprojection error < thr under hyp[b][h] (fp32; tested as |(x, y) − z·(u, v)|² < thr²·z², no
+ *   division), 0 where hyp_valid is 0.  score [n][hyps] is cleared by the call.
+ * scflow_pnp_refine: per sample the winner (highest score, lowest h), then refine_iters
+ *   Gauss-Newton steps on the winner's inliers (the set re-derived from hyp with
+ *   scflow_pnp_score's test, fixed) from hyp_pose (its fp32 rotation made orthonormal again in
+ *   fp64, Gram-Schmidt on the rows), with the left perturbation R ← exp(ω)·R,
+ *   t ← exp(ω)·t + τ: residuals, Jacobians and the 6×6 normal equations in fp64, summed in a
+ *   fixed order and solved by Cholesky; a non-positive or non-finite pivot stops and
+ *   keeps the last pose.  K must be upper triangular with K[2][2] = 1.  ok[b] = 1 when count[b] ≥
+ *   4, the winner is valid, its score ≥ 4 and the result is finite: then R_out / t_out hold the
+ *   pose and inliers[b] the winner's score; else R_out / t_out are bit copies of R_ref / t_ref
+ *   and inliers[b] = 0.  pose64 (may be NULL) [n][12] doubles receives the same pose before its
+ *   rounding to fp32 (R row-major, then t): at t_z ≈ 1 m one fp32 ulp is 6e-5 mm, more than the
+ *   refinement's own error. */
+#define SCFLOW_PNP_MAX_HYPS 256
+int scflow_pnp_workspace(int n, int h, int w, int hyps, long long* bytes);
+int scflow_pnp_compact(const float* points, const float* flow, const float* valid, float* corr,
+                       int* count, void* workspace, long long workspace_bytes, int n, int h, int w,
+                       void* stream);
+int scflow_pnp_hypotheses(const float* corr, const int* count, const float* K, float* hyp,
+                          float* hyp_pose, int* hyp_valid, int* samples, int n, int hw, int hyps,
+                          unsigned seed, void* stream);
+int scflow_pnp_score(const float* corr, const int* count, const float* hyp, const int* hyp_valid,
+                     int* score, int n, int hw, int hyps, float thr, void* stream);
+int scflow_pnp_refine(const float* corr, const int* count, const float* hyp, const float* hyp_pose,
+                      const int* hyp_valid, const int* score, const float* K, const float* R_ref,
+                      const float* t_ref, float* R_out, float* t_out, int* ok, int* inliers,
+                      double* pose64, int n, int hw, int hyps, float thr, int refine_iters,
+                      void* stream);
 
 /* Profiling helper (bench.py roofline timing; no reference equivalent): a one-thread kernel
  * that stores the GPU's constant-rate wall clock (s_memrealtime) into stamps[idx].  Enqueued on

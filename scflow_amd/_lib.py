@@ -24,6 +24,7 @@ CONV_1X1W = 3  # scflow_conv_args.bk: wide 1x1 packing/kernel (SCFLOW_CONV_1X1W)
 CONV_WINO4 = 4  # scflow_conv_args.bk: Winograd F(4x4,3x3) packing/kernel (SCFLOW_CONV_WINO4)
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 ABI_VERSION = 4  # SCFLOW_ABI_VERSION of include/scflow_hip.h this binding mirrors
+PNP_MAX_HYPS = 256  # SCFLOW_PNP_MAX_HYPS
 
 
 class ConvArgs(ctypes.Structure):
@@ -253,6 +254,13 @@ SIGNATURES = {
     "scflow_gemm_f32_splits": (c_int, [c_int, c_int, c_int, c_int]),
     "scflow_gemm_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int] + [c_ll] * 9 +
                         [c_float, c_float, c_int, c_int, c_vp, c_vp]),
+    "scflow_pnp_workspace": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
+    "scflow_pnp_compact": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_int, c_int,
+                                   c_vp]),
+    "scflow_pnp_hypotheses": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
+                                      ctypes.c_uint, c_vp]),
+    "scflow_pnp_score": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_float, c_vp]),
+    "scflow_pnp_refine": (c_int, [c_vp] * 14 + [c_int, c_int, c_int, c_float, c_int, c_vp]),
     "scflow_timestamp": (c_int, [c_vp, c_int, c_vp]),
     "scflow_wallclock_khz": (c_ll, []),
 }

@@ -16,6 +16,8 @@ op                             reference                                        
 ``scflow::convex_upsample``    RAFTDecoder._upsample, raft_decoder.py:381-416, and    yes (flow,
                                RAFTDecoderMask.upsample_mask, raft_decoder_mask.py    logits,
                                                                                       occ)
+``scflow::pnp_ransac``         solve_pose_by_pnp (cv2.solvePnPRansac), pose.py:203-   no
+                               249, batched; another algorithm
 =============================  =====================================================  =========
 
 The backward formulas are ops of their own (``scflow::corr_pyramid_backward``,
@@ -328,3 +330,24 @@ def _convex_upsample_backward(ctx, g_flow, g_occ):
 
 
 convex_upsample.register_autograd(_convex_upsample_backward, setup_context=_convex_upsample_setup)
+
+
+# ------------------------------------------------------------------------------------ RANSAC-PnP
+@torch.library.custom_op("scflow::pnp_ransac", mutates_args=(), device_types="cuda")
+def pnp_ransac(flow: Tensor, depth: Tensor, R: Tensor, t: Tensor, K: Tensor,
+               valid: Optional[Tensor], hyps: int, thr: float, refine_iters: int, seed: int
+               ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Batched RANSAC-PnP on the device (``ops.pnp_ransac``; replaces solve_pose_by_pnp,
+    pose.py:203-249, per sample behind ``.cpu().numpy()``): flow [B, 2, H, W], rendered depth
+    [B, H, W], reference pose R [B, 3, 3] / t [B, 3], K [B, 3, 3], valid [B, H, W] or None →
+    (R [B, 3, 3], t [B, 3], ok [B] bool, inliers [B] int32).  Not differentiable."""
+    return ops.pnp_ransac(flow.contiguous().float(), depth.contiguous().float(),
+                          R.contiguous().float(), t.contiguous().float(), K.contiguous().float(),
+                          valid, hyps, thr, refine_iters, seed)
+
+
+@pnp_ransac.register_fake
+def _(flow, depth, R, t, K, valid, hyps, thr, refine_iters, seed):
+    B = flow.shape[0]
+    return (R.new_empty(B, 3, 3), t.new_empty(B, 3), R.new_empty(B, dtype=torch.bool),
+            R.new_empty(B, dtype=torch.int32))

@@ -654,6 +654,133 @@ def pose_step_given(R: Tensor, t: Tensor, K: Tensor, points: Tensor, flow_out: T
             1.0 / float(up_scale), 1)
 
 
+# ------------------------------------------------------------------------------- RANSAC-PnP
+PNP_MAX_HYPS = _lib.PNP_MAX_HYPS
+
+
+def pnp_workspace_bytes(n: int, h: int, w: int, hyps: int) -> int:
+    """Bytes of ``pnp_compact``'s workspace (scflow_pnp_workspace: host only, needs no GPU)."""
+    nb = ctypes.c_longlong(0)
+    check(_lib.load().scflow_pnp_workspace(n, h, w, hyps, ctypes.byref(nb)), "scflow_pnp_workspace")
+    return nb.value
+
+
+def pnp_compact(points: Tensor, flow: Tensor, valid: Optional[Tensor] = None
+                ) -> Tuple[Tensor, Tensor]:
+    """points [N, H, W, 4] (``lift_points``), flow [N, 2, H, W], valid [N, H, W] float (non-zero =
+    keep) or None → (corr [N, H·W, 5], count [N] int32): the valid pixels' (X, Y, Z, x + flow_x,
+    y + flow_y) in ascending pixel order in corr[b, :count[b]]; later rows are unspecified."""
+    _require(points, "points")
+    _require(flow, "flow")
+    n, h, w, _ = points.shape
+    if tuple(flow.shape) != (n, 2, h, w):
+        raise ValueError(f"flow must be {(n, 2, h, w)}, got {tuple(flow.shape)}")
+    if valid is not None:
+        _require(valid, "valid")
+        if valid.numel() != n * h * w:
+            raise ValueError(f"valid must have {n * h * w} elements, got {tuple(valid.shape)}")
+    ws = torch.empty(pnp_workspace_bytes(n, h, w, 1), device=points.device, dtype=torch.uint8)
+    corr = torch.empty(n, h * w, 5, device=points.device, dtype=torch.float32)
+    count = torch.empty(n, device=points.device, dtype=torch.int32)
+    _launch("scflow_pnp_compact", points, _p(points), _p(flow), _p(valid), _p(corr), _p(count),
+            _p(ws), ws.numel(), n, h, w)
+    return corr, count
+
+
+def _require_pnp(corr: Tensor, count: Tensor) -> Tuple[int, int]:
+    _require(corr, "corr")
+    _require(count, "count", dtype=torch.int32)
+    if corr.dim() != 3 or corr.shape[2] != 5 or count.numel() != corr.shape[0]:
+        raise ValueError(f"corr must be [N, H·W, 5] with count [N], got {tuple(corr.shape)} / "
+                         f"{tuple(count.shape)}")
+    return corr.shape[0], corr.shape[1]
+
+
+def pnp_hypotheses(corr: Tensor, count: Tensor, K: Tensor, hyps: int = 100, seed: int = 0
+                   ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """→ (hyp [N, hyps, 12] = K·[R|t], hyp_pose [N, hyps, 12] = [R|t], hyp_valid [N, hyps] int32,
+    samples [N, hyps, 4] int32): P3P in fp64 on counter-hashed 4-row samples (scflow_pnp_hypotheses)."""
+    n, hw = _require_pnp(corr, count)
+    _require(K, "K")
+    dev = corr.device
+    hyp = torch.empty(n, hyps, 12, device=dev, dtype=torch.float32)
+    pose = torch.empty(n, hyps, 12, device=dev, dtype=torch.float32)
+    hv = torch.empty(n, hyps, device=dev, dtype=torch.int32)
+    samples = torch.empty(n, hyps, 4, device=dev, dtype=torch.int32)
+    _launch("scflow_pnp_hypotheses", corr, _p(corr), _p(count), _p(K), _p(hyp), _p(pose), _p(hv),
+            _p(samples), n, hw, int(hyps), int(seed) & 0xFFFFFFFF)
+    return hyp, pose, hv, samples
+
+
+def pnp_score(corr: Tensor, count: Tensor, hyp: Tensor, hyp_valid: Tensor, thr: float = 3.0
+              ) -> Tensor:
+    """score [N, hyps] int32: rows in front of the camera with reprojection error < thr under each
+    hypothesis, 0 for invalid ones (scflow_pnp_score)."""
+    n, hw = _require_pnp(corr, count)
+    _require(hyp, "hyp")
+    _require(hyp_valid, "hyp_valid", dtype=torch.int32)
+    hyps = hyp.shape[1]
+    if tuple(hyp.shape) != (n, hyps, 12) or tuple(hyp_valid.shape) != (n, hyps):
+        raise ValueError(f"hyp / hyp_valid must be [N, hyps, 12] / [N, hyps], got "
+                         f"{tuple(hyp.shape)} / {tuple(hyp_valid.shape)}")
+    score = torch.empty(n, hyps, device=corr.device, dtype=torch.int32)
+    _launch("scflow_pnp_score", corr, _p(corr), _p(count), _p(hyp), _p(hyp_valid), _p(score), n, hw,
+            hyps, float(thr))
+    return score
+
+
+def pnp_refine(corr: Tensor, count: Tensor, hyp: Tensor, hyp_pose: Tensor, hyp_valid: Tensor,
+               score: Tensor, K: Tensor, R: Tensor, t: Tensor, thr: float = 3.0,
+               refine_iters: int = 10, pose64: Optional[Tensor] = None
+               ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Winner per sample + Gauss-Newton on its inliers (scflow_pnp_refine) → (R [N, 3, 3],
+    t [N, 3], ok [N] int32, inliers [N] int32); the reference pose R, t where ok is 0.  pose64
+    [N, 12] float64, when given, receives the pose before its rounding to fp32 (R, then t)."""
+    n, hw = _require_pnp(corr, count)
+    if pose64 is not None:
+        _require(pose64, "pose64", dtype=torch.float64)
+        if tuple(pose64.shape) != (n, 12):
+            raise ValueError(f"pose64 must be {(n, 12)}, got {tuple(pose64.shape)}")
+    for nm, x in (("hyp", hyp), ("hyp_pose", hyp_pose), ("K", K), ("R", R), ("t", t)):
+        _require(x, nm)
+    _require(hyp_valid, "hyp_valid", dtype=torch.int32)
+    _require(score, "score", dtype=torch.int32)
+    hyps = hyp.shape[1]
+    if tuple(hyp.shape) != (n, hyps, 12) or hyp_pose.shape != hyp.shape or \
+            tuple(hyp_valid.shape) != (n, hyps) or tuple(score.shape) != (n, hyps):
+        raise ValueError("hyp, hyp_pose [N, hyps, 12] and hyp_valid, score [N, hyps] must agree")
+    Ro, to = torch.empty_like(R), torch.empty_like(t)
+    ok = torch.empty(n, device=corr.device, dtype=torch.int32)
+    inl = torch.empty(n, device=corr.device, dtype=torch.int32)
+    _launch("scflow_pnp_refine", corr, _p(corr), _p(count), _p(hyp), _p(hyp_pose), _p(hyp_valid),
+            _p(score), _p(K), _p(R), _p(t), _p(Ro), _p(to), _p(ok), _p(inl), _p(pose64), n, hw,
+            hyps, float(thr), int(refine_iters))
+    return Ro, to, ok, inl
+
+
+def pnp_ransac(flow: Tensor, depth: Tensor, R: Tensor, t: Tensor, K: Tensor,
+               valid: Optional[Tensor] = None, hyps: int = 100, thr: float = 3.0,
+               refine_iters: int = 10, seed: int = 0, pose64: Optional[Tensor] = None
+               ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Batched RANSAC-PnP: flow [B, 2, H, W], rendered depth [B, H, W], reference
+    pose R [B, 3, 3], t [B, 3], intrinsics K [B, 3, 3], valid [B, H, W] (bool or float, non-zero =
+    use the pixel) → (R [B, 3, 3], t [B, 3], ok [B] bool, inliers [B] int32).  Lift → compact →
+    hypotheses → score → refine on the current stream, no host synchronisation; where ok is False
+    the pose is the reference pose bit for bit and inliers is 0.  pose64 [B, 12] float64, when
+    given, receives the pose before its rounding to fp32 (``pnp_refine``)."""
+    if hyps < 1 or hyps > PNP_MAX_HYPS:
+        raise ScflowError(f"pnp_ransac: hyps must be in [1, {PNP_MAX_HYPS}], got {hyps}")
+    if valid is not None and valid.dtype != torch.float32:
+        valid = valid.to(torch.float32)
+    points = lift_points(depth, K, R, t)
+    corr, count = pnp_compact(points, flow, None if valid is None else valid.contiguous())
+    hyp, pose, hv, _ = pnp_hypotheses(corr, count, K, hyps, seed)
+    score = pnp_score(corr, count, hyp, hv, thr)
+    Ro, to, ok, inl = pnp_refine(corr, count, hyp, pose, hv, score, K, R, t, thr, refine_iters,
+                                 pose64)
+    return Ro, to, ok != 0, inl
+
+
 # ------------------------------------------------------------------------------- resampling
 def flow_downsample(flow: Tensor, out0: Chan, h: int, w: int, value_scale: float,
                     out1: Optional[Chan] = None, mask: Optional[Tensor] = None,

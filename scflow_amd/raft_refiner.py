@@ -20,9 +20,18 @@ with the mask decoder, ``SequenceLoss(L1Loss)`` on the ×8 occlusions) on the HI
 Functions, convex upsampling included (``scflow_convex_upsample_bwd``); ``train.step.TrainStep``
 takes these refiners.  The inference paths above stay under ``torch.no_grad()``.
 
-Not covered: ``solve_pose`` / PnP (needs cv2), the data formatting (``forward_single_view``,
-``format_data_*``: ``loss`` takes an already formatted batch), ``filter_invalid_flow_by_depth``
-and graph-mode training — ``forward`` is ``get_flow``.
+``solve_pose`` (base_flow_refiner.py:99-155) and ``get_pose`` turn the last ×8 flow into poses on
+the batched HIP RANSAC-PnP (``ops.pnp_ransac``: compacted 2D-3D correspondences, P3P hypotheses on
+hashed samples, one scoring kernel, Gauss-Newton on the winner's inliers) instead
+of ``cv2.solvePnPRansac`` per sample behind ``.cpu().numpy()`` (pose.py:203-249).  It takes the
+reference's parameters (``occ_thresh``, ``sample_points``, ``solve_pose_param``) and returns its
+dict, but it is another algorithm: parity with cv2 is unpinned (cv2 is absent here).  Everything
+stays on the device; ``solve_pose``'s one host synchronisation is the final dropping of failed
+samples.  ``solve_pose_mode='progressive-x'`` and ``solve_pose_space='origin'`` raise.
+
+Not covered: the data formatting (``forward_single_view``, ``format_data_*``: ``loss`` takes an
+already formatted batch), ``remap_pose_to_origin_resoluaion``, ``filter_invalid_flow_by_depth`` and
+graph-mode training — ``forward`` is ``get_flow``.
 """
 from __future__ import annotations
 
@@ -104,6 +113,96 @@ class _RAFTFlowRefiner(_RefinerBase):
         vals += [res["loss_flow"], res["loss"]]
         host = torch.stack([v.detach().reshape(()) for v in vals]).tolist()  # the one sync
         return res["loss"], None, OrderedDict(zip(names, host))
+
+    # ------------------------------------------------------------------ RANSAC-PnP
+    def _pnp_valid(self, occlusion: Optional[Tensor], rendered_depths: Tensor) -> Optional[Tensor]:
+        """The validity mask ``solve_pose`` hands the PnP beside ``depth > 0``: occlusion >
+        ``occ_thresh`` (base_flow_refiner.py:110-114), thinned by ``sample_points``
+        (:117-126) — all torch ops on the device.  None: every rendered pixel."""
+        valid = None
+        if occlusion is not None:
+            occlusion = occlusion.reshape(rendered_depths.shape).float()
+            valid = occlusion > self.test_cfg.get("occ_thresh", 0.5)
+        cfg = self.test_cfg.get("sample_points", None)
+        if cfg is None:
+            return valid
+        num, mode = int(cfg.get("num", 1000)), cfg.get("mode", "random")
+        cand = rendered_depths > 0
+        if valid is not None:
+            cand = cand & valid
+        B = cand.shape[0]
+        flat = cand.reshape(B, -1)
+        if mode == "random":
+            # a uniform draw of `num` of the candidates (all of them when fewer): torch's generator,
+            # not the reference's randperm stream, and without its never-the-last-point quirk
+            key = torch.rand(flat.shape, device=flat.device)
+        elif occlusion is not None:
+            key = occlusion.reshape(B, -1)  # topk on the occlusion confidence (:54-63)
+        else:
+            raise ScflowError("sample_points mode 'topk' selects on the occlusion confidence: it "
+                              "needs the mask decoder's occlusion")
+        key = torch.where(flat, key.float(), key.new_full((), float("-inf"), dtype=torch.float32))
+        k = min(num, flat.shape[1])
+        idx = torch.topk(key, k, dim=1).indices
+        keep = torch.zeros_like(flat).scatter_(1, idx, True) & flat
+        return keep.reshape(cand.shape)
+
+    def _pnp(self, flow: Tensor, rendered_depths: Tensor, ref_rotations: Tensor,
+             ref_translations: Tensor, internel_k: Tensor, occlusion: Optional[Tensor]):
+        cfg = self.test_cfg
+        mode = cfg.get("solve_pose_mode", "ransacpnp")
+        if mode != "ransacpnp":
+            raise ScflowError(f"solve_pose_mode={mode!r} is not built: only 'ransacpnp' runs on the "
+                              "HIP kernels ('progressive-x' needs pyprogressivex)")
+        if cfg.get("solve_pose_space", "transformed") == "origin":
+            raise ScflowError("solve_pose_space='origin' is not built: poses are solved in the "
+                              "cropped patch's frame ('transformed')")
+        if flow.device.type != "cuda":
+            raise ScflowError(f"{type(self).__name__} runs on the gfx950 HIP kernels only (no CPU "
+                              "fallback)")
+        from .library import pnp_ransac
+        param = cfg.get("solve_pose_param", {})
+        valid = self._pnp_valid(occlusion, rendered_depths)
+        return pnp_ransac(
+            flow, rendered_depths, ref_rotations, ref_translations, internel_k,
+            None if valid is None else valid.float(), int(param.get("iterationscount", 100)),
+            float(param.get("reprojectionerror", 3.0)), 10, 0)
+
+    def solve_pose(self, batch_flow: Tensor, rendered_depths: Tensor, ref_rotations: Tensor,
+                   ref_translations: Tensor, internel_k: Tensor, labels: Tensor, per_img_patch_num,
+                   occlusion: Optional[Tensor] = None):
+        """base_flow_refiner.py:99-155 on the batched HIP RANSAC-PnP (``ops.pnp_ransac``) — the ×8
+        flow [B, 2, H, W], rendered depths [B, H, W], reference poses, intrinsics, labels [B] and
+        the patches per image → the reference's dict of per-image lists (``rotations``,
+        ``translations``, ``scores`` = ones, ``labels``) with the samples whose PnP failed dropped.
+        One host synchronisation, at the end (the boolean indexing).  ``test_cfg`` is read as the
+        reference reads it: ``occ_thresh``, ``sample_points``, ``solve_pose_param``."""
+        with torch.no_grad():
+            R, t, ok, _ = self._pnp(batch_flow, rendered_depths, ref_rotations, ref_translations,
+                                    internel_k, occlusion)
+        split = [int(v) for v in per_img_patch_num]
+        keep = torch.split(ok, split)
+        scores = torch.ones_like(labels, dtype=torch.float32)
+        out = {}
+        for name, x in (("rotations", R), ("translations", t), ("scores", scores),
+                        ("labels", labels)):
+            out[name] = [p[k] for p, k in zip(torch.split(x, split), keep)]
+        return out
+
+    def get_pose(self, render_images: Tensor, real_images: Tensor, rendered_depths: Tensor,
+                 ref_rotations: Tensor, ref_translations: Tensor, internel_k: Tensor):
+        """``get_flow`` at ``test_iter_num`` iterations, then RANSAC-PnP on the last ×8 flow (with
+        the mask decoder: restricted by the last occlusion) → (R [B, 3, 3], t [B, 3], ok [B] bool,
+        inliers [B] int32), all on the device; the reference pose where ``ok`` is False."""
+        iters, self.decoder.iters = self.decoder.iters, self.test_iter_num
+        try:
+            out = self.get_flow(render_images, real_images)
+        finally:
+            self.decoder.iters = iters
+        flows, occs = out if isinstance(out, tuple) else (out, None)
+        with torch.no_grad():
+            return self._pnp(flows[-1], rendered_depths.contiguous().float(), ref_rotations,
+                             ref_translations, internel_k, None if occs is None else occs[-1])
 
     # ------------------------------------------------------------------ fused path
     def _get_flow(self, render, real, init_flow):

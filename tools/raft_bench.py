@@ -1,7 +1,7 @@
 """Timing of the RAFT baseline decoders (RAFTDecoderMask, RAFTDecoder), interleaved in one process.
 
 usage: python tools/raft_bench.py [--batch 16] [--size 256] [--iters 12] [--rounds 7] [--steps 10]
-                                  [--json out.json] [--once KIND] [--train]
+                                  [--json out.json] [--once KIND] [--train] [--pnp [--hyps 100]]
 
 Each decoder is warmed up, then timed `rounds` times in round-robin order (`steps` forwards per
 round, a device synchronise at both ends); prints the median, minimum and maximum ms per forward
@@ -13,9 +13,13 @@ two next-flow destinations out), the figure a kernel trace's launch time is divi
 forward, backward, gradient clipping at 1.0, AdamW; same defaults: B=16, 256², 12 iterations) and
 prints the median ms per step over the rounds and one JSON line.
 
-`--once KIND` runs `steps` forwards of one decoder and nothing else: the run to put under
-`rocprofv3 --kernel-trace --stats` (a run of its own; end-to-end numbers come from the untraced
-run).
+`--pnp` times `ops.pnp_ransac` alone (the batched RANSAC-PnP that turns the last ×8 flow into poses:
+B=16, 256², `--hyps` 100 hypotheses) next to the RAFTDecoderMask forward it follows, alternating,
+each window between two device events; prints both medians and one JSON line.
+
+`--once KIND` runs `steps` forwards of one decoder (or `--once pnp_ransac`: `steps` PnP calls) and
+nothing else: the run to put under `rocprofv3 --kernel-trace --stats` (a run of its own; end-to-end
+numbers come from the untraced run).
 """
 import argparse
 import json
@@ -95,19 +99,83 @@ def train(a):
     return res
 
 
+def pnp_inputs(a, dev):
+    """flow, depth, R, t, K of a synthetic scene batch: the ground-truth flow of a known pose (the
+    reference pose perturbed) with 30 % of the rendered pixels moved by 10-40 px, the pattern the
+    RANSAC-PnP tests use."""
+    import numpy as np
+    from scflow_amd import ops, synthetic
+    sc = synthetic.make_scene(a.batch, a.size, seed=0)
+    tg = synthetic.make_train_targets(sc, a.size, seed=0)
+    T = lambda k, d=sc: torch.from_numpy(np.ascontiguousarray(d[k])).to(dev)  # noqa: E731
+    depth, K, R, t = T("depth"), T("internel_k"), T("ref_rotation"), T("ref_translation")
+    flow = ops.pose_flow(T("gt_rotation", tg), T("gt_translation", tg), K,
+                         ops.lift_points(depth, K, R, t), 0.0)
+    g = torch.Generator(device=dev).manual_seed(0)
+    moved = (torch.rand(depth.shape, device=dev, generator=g) < 0.3) & (depth > 0)
+    mag = 10 + 30 * torch.rand(depth.shape, device=dev, generator=g)
+    ang = 6.2831853 * torch.rand(depth.shape, device=dev, generator=g)
+    flow = flow + moved[:, None] * torch.stack([mag * torch.cos(ang), mag * torch.sin(ang)], 1)
+    return flow.contiguous(), depth, R, t, K
+
+
+def pnp(a, dec, inp):
+    """`ops.pnp_ransac` alone (lift → compact → hypotheses → score → refine) and the decoder forward
+    it follows, alternating in one process, each timed with device events around `steps` calls."""
+    from scflow_amd import ops
+    dev = torch.device("cuda")
+    args = pnp_inputs(a, dev)
+    run = {"pnp_ransac": lambda: ops.pnp_ransac(*args, hyps=a.hyps), KINDS[0]: lambda: dec(**inp)}
+    for f in run.values():  # warm every shape (code objects, packing, allocator)
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    times = {k: [] for k in run}
+    for _ in range(a.rounds):
+        for k, f in run.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.steps):
+                out = f()
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1) / a.steps)
+    ok, inl = run["pnp_ransac"]()[2:]
+    res = dict(mode="pnp", batch=a.batch, size=a.size, iters=a.iters, hyps=a.hyps, rounds=a.rounds,
+               steps=a.steps, ok=int(ok.sum()), inliers=inl.tolist(),
+               valid_pixels=(args[1] > 0).flatten(1).sum(1).tolist())
+    for k, v in times.items():
+        res[k] = dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v))
+        print(f"{k}: median {res[k]['median_ms']:.3f} ms/call (min {min(v):.3f}, max {max(v):.3f}); "
+              f"B={a.batch}, {a.size}²" + (f", {a.hyps} hypotheses" if k == "pnp_ransac"
+                                           else f", {a.iters} iterations"))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--train", action="store_true")
+    ap.add_argument("--pnp", action="store_true")
+    ap.add_argument("--hyps", type=int, default=100)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--iters", type=int, default=12)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--once", default=None, choices=KINDS)
+    ap.add_argument("--once", default=None, choices=KINDS + ("pnp_ransac",))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("raft_bench.py needs a GPU (a CPU run measures nothing)")
+    if a.once == "pnp_ransac":
+        from scflow_amd import ops
+        args = pnp_inputs(a, torch.device("cuda"))
+        for _ in range(a.steps):
+            ok = ops.pnp_ransac(*args, hyps=a.hyps)[2]
+        torch.cuda.synchronize()
+        print(f"pnp_ransac: {a.steps} calls, B={a.batch}, {a.size}², {a.hyps} hypotheses; "
+              f"{int(ok.sum())} of {a.batch} poses found")
+        return
     if a.train:
         line = json.dumps(train(a))
         print(line)
@@ -125,7 +193,7 @@ def main():
                flow=torch.zeros(a.batch, 2, h, h, device=dev),
                h_feat=torch.from_numpy(raw["h_feat"]).to(dev),
                cxt_feat=torch.from_numpy(raw["cxt_feat"]).to(dev))
-    kinds = (a.once,) if a.once else KINDS
+    kinds = (a.once,) if a.once else (KINDS[:1] if a.pnp else KINDS)
     decs = {}
     for kind in kinds:
         dec = MODELS.build(decoder_cfg(kind, a.iters))
@@ -139,6 +207,14 @@ def main():
         torch.cuda.synchronize()
         print(f"{a.once}: {a.steps} forwards of {a.iters} iterations, B={a.batch}, {a.size}²; "
               f"convex tail moves {tail_bytes(a.batch, a.size, a.once == KINDS[0])} B per launch")
+        return
+    if a.pnp:
+        line = json.dumps(pnp(a, decs[KINDS[0]], inp))
+        print(line)
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, "w") as f:
+                f.write(line + "\n")
         return
     for dec in decs.values():  # warm every shape (packing, allocator, code objects)
         for _ in range(3):
