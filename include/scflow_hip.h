@@ -32,6 +32,8 @@
  *   scflow_pnp_*             <- BaseFlowRefiner.solve_pose: 2D-3D correspondences + RANSAC-PnP (another
  *                               algorithm than cv2.solvePnPRansac)   base_flow_refiner.py:99-155,
  *                               models/utils/pose.py:182-249
+ *   scflow_patch_*           <- ComputeBbox, Crop, Resize, Pad, RemapPose, Normalize: 256² patches and their
+ *                               intrinsics from full frames   datasets/pipelines/geometry_transform.py:155-500
  *   scflow_transpose         <- layout plumbing (NCHW <-> channels-last slices), no reference equivalent
  *   scflow_ph_*              <- MultiClassPoseHead.forward                models/head/pose_head.py:201-211
  *   scflow_enc_*             <- RAFTEncoder.forward (Basic; IN / BN)      models/encoder/raft_encoder.py:286-314
@@ -837,6 +839,56 @@ int scflow_pnp_refine(const float* corr, const int* count, const float* hyp, con
                       const float* t_ref, float* R_out, float* t_out, int* ok, int* inliers,
                       double* pose64, int n, int hw, int hyps, float thr, int refine_iters,
                       void* stream);
+
+/* Patches from full frames: the reference's test-time formatting ComputeBbox → Crop →
+ * Resize → Pad → RemapPose(adapt_intrinsic) → Normalize (datasets/pipelines/geometry_transform.py:
+ * 155-500, formatting.py:42-91; keep_ratio=False, aspect_ratio=1, clip_border=False, min_expand=0)
+ * as two launches on the caller's stream with no host work between them.
+ *
+ * scflow_patch_boxes: object i of class labels[i] projects points[labels[i]][0 .. counts[labels[i]])
+ *   (points [num_classes][max_points][3]) as K·(R·X + t) in fp32, K = ori_k[i] or, with k_per_frame,
+ *   ori_k[frame_index[i]] (frame_index may be NULL without k_per_frame), and reduces the box
+ *   bbox[i] = (l, t, r, b).  side = max(r−l, b−t), centre ((l+r)/2, (t+b)/2), half = side·ratio[i]/2;
+ *   x1 = trunc(xc − half), x2 = trunc(xc + half), y likewise (toward zero); the crop is inclusive,
+ *   cw = x2−x1+1, ch = y2−y1+1, m = max(cw, ch), sf = size/m, nw = (2·cw·size + m) div 2m (nh
+ *   likewise), left = (size−nw) div 2, top = (size−nh) div 2.  geom[i] = (x1, y1, x2, y2, nw, nh, left,
+ *   top); T[i] = translate(left, top)·diag(sf, sf, 1)·translate(−x1, −y1) and k[i] = T[i]·K as fp32
+ *   3×3 products, left to right, each element summed over its three terms in order.  valid[i] = 0
+ *   (then geom = 0, T = identity, k = K) when a projected z ≤ 0, the box is not finite or empty,
+ *   side·ratio < 1, m > SCFLOW_PATCH_MAX_CROP, the crop does not meet the height × width frame, the
+ *   label is outside [0, num_classes) or frame_index[i] outside [0, num_frames) (K = identity then
+ *   with k_per_frame).  size: a multiple of 4 in [4, 4096].
+ * scflow_patch_extract: out [n][channels][size][size] fp32 from frames [num_frames][height][width]
+ *   [channels] (dtype SCFLOW_PATCH_U8 with 1 or 3 channels, SCFLOW_PATCH_F32 with 1) under geom /
+ *   valid of the call above.  Crop pixel (i, j) is frame[y1+i][x1+j] inside the frame and pad
+ *   outside; output pixel (left+dx, top+dy), dx < nw, dy < nh, is cv2's INTER_LINEAR of the crop:
+ *   source x = ((2·dx+1)·cw − nw)/(2·nw) exactly, x0 its floor, fx = remainder/(2·nw) the only rounded
+ *   quantity, x0 < 0 → (0, 0), x0 ≥ cw−1 → (cw−1, 0), y likewise, value (1−fy)·((1−fx)·a + fx·b) +
+ *   fy·((1−fx)·c + fx·d) in fp32 without contraction; SCFLOW_PATCH_QUANTIZE rounds it with rintf;
+ *   SCFLOW_PATCH_NEAREST takes crop[min(dy·ch div nh, ch−1)][min(dx·cw div nw, cw−1)] instead.  Every
+ *   other output pixel, and the whole patch of an invalid object or of a geom that is not one, is
+ *   pad.  Then (v − mean[c])/std[c] per output channel c, after SCFLOW_PATCH_TO_RGB reversed the
+ *   channel order; mean / std: HOST arrays of `channels` floats read by the call, NULL = 0 / 1.
+ *   out: 16-byte aligned.  The taps are read directly; with SCFLOW_PATCH_LDS != 0 the two source
+ *   rows of an output row are staged in LDS where the crop row fits the budget
+ *   (scflow_patch_staged says whether, under the switch's current value: 1 staged, 0 direct); both
+ *   routes give the same bits. */
+#define SCFLOW_PATCH_MAX_CROP 8192
+#define SCFLOW_PATCH_U8 0
+#define SCFLOW_PATCH_F32 1
+#define SCFLOW_PATCH_TO_RGB 1
+#define SCFLOW_PATCH_QUANTIZE 2
+#define SCFLOW_PATCH_NEAREST 4
+int scflow_patch_boxes(const float* points, const int* counts, const int* labels, const float* R,
+                       const float* t, const float* ori_k, const int* frame_index, const float* ratio,
+                       float* bbox, int* geom, float* T, float* k, unsigned char* valid, int n,
+                       int num_classes, int max_points, int k_per_frame, int num_frames, int height,
+                       int width, int size, void* stream);
+int scflow_patch_extract(const void* frames, const int* frame_index, const int* geom,
+                         const unsigned char* valid, float* out, int n, int num_frames, int height,
+                         int width, int channels, int dtype, int size, float pad, const float* mean,
+                         const float* std, int flags, void* stream);
+int scflow_patch_staged(int cw, int channels, int dtype, int size);
 
 /* Profiling helper (bench.py roofline timing; no reference equivalent): a one-thread kernel
  * that stores the GPU's constant-rate wall clock (s_memrealtime) into stamps[idx].  Enqueued on

@@ -25,6 +25,9 @@ CONV_WINO4 = 4  # scflow_conv_args.bk: Winograd F(4x4,3x3) packing/kernel (SCFLO
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 ABI_VERSION = 4  # SCFLOW_ABI_VERSION of include/scflow_hip.h this binding mirrors
 PNP_MAX_HYPS = 256  # SCFLOW_PNP_MAX_HYPS
+PATCH_MAX_CROP = 8192  # SCFLOW_PATCH_MAX_CROP
+PATCH_U8, PATCH_F32 = 0, 1  # scflow_patch_extract's dtype
+PATCH_TO_RGB, PATCH_QUANTIZE, PATCH_NEAREST = 1, 2, 4  # scflow_patch_extract's flags
 
 
 class ConvArgs(ctypes.Structure):
@@ -261,6 +264,9 @@ SIGNATURES = {
                                       ctypes.c_uint, c_vp]),
     "scflow_pnp_score": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_float, c_vp]),
     "scflow_pnp_refine": (c_int, [c_vp] * 14 + [c_int, c_int, c_int, c_float, c_int, c_vp]),
+    "scflow_patch_boxes": (c_int, [c_vp] * 13 + [c_int] * 8 + [c_vp]),
+    "scflow_patch_extract": (c_int, [c_vp] * 5 + [c_int] * 7 + [c_float, c_vp, c_vp, c_int, c_vp]),
+    "scflow_patch_staged": (c_int, [c_int, c_int, c_int, c_int]),
     "scflow_timestamp": (c_int, [c_vp, c_int, c_vp]),
     "scflow_wallclock_khz": (c_ll, []),
 }

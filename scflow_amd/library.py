@@ -18,6 +18,10 @@ op                             reference                                        
                                                                                       occ)
 ``scflow::pnp_ransac``         solve_pose_by_pnp (cv2.solvePnPRansac), pose.py:203-   no
                                249, batched; another algorithm
+``scflow::patch_boxes``        ComputeBbox + the Crop / Resize / Pad / RemapPose       no
+                               geometry, geometry_transform.py:155-500
+``scflow::extract_patches``    mmcv imcrop, imrescale, impad, imnormalize of the       no
+                               same pipeline, all objects in one launch
 =============================  =====================================================  =========
 
 The backward formulas are ops of their own (``scflow::corr_pyramid_backward``,
@@ -32,7 +36,7 @@ loudly off-GPU, ``ScflowError``).
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -351,3 +355,48 @@ def _(flow, depth, R, t, K, valid, hyps, thr, refine_iters, seed):
     B = flow.shape[0]
     return (R.new_empty(B, 3, 3), t.new_empty(B, 3), R.new_empty(B, dtype=torch.bool),
             R.new_empty(B, dtype=torch.int32))
+
+
+# ------------------------------------------------------------------------------------ patches
+@torch.library.custom_op("scflow::patch_boxes", mutates_args=(), device_types="cuda")
+def patch_boxes(points: Tensor, counts: Tensor, labels: Tensor, R: Tensor, t: Tensor, ori_k: Tensor,
+                ratio: Tensor, frame_index: Optional[Tensor], k_per_frame: bool, num_frames: int,
+                height: int, width: int, size: int
+                ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Crop geometry from the projected model points (``ops.patch_boxes``; replaces ComputeBbox,
+    Crop / Resize / Pad's bookkeeping and RemapPose's ``adapt_intrinsic``, geometry_transform.py:
+    155-500, per object on the host): → (bbox [N, 4], geom [N, 8] int32, T [N, 3, 3], k [N, 3, 3],
+    valid [N] uint8).  Integer arguments of any integer dtype.  Not differentiable."""
+    i32 = torch.int32
+    return ops.patch_boxes(points.contiguous().float(), counts.contiguous().to(i32),
+                           labels.contiguous().to(i32), R.contiguous().float(),
+                           t.contiguous().float(), ori_k.contiguous().float(),
+                           ratio.contiguous().float(), height, width, size,
+                           None if frame_index is None else frame_index.contiguous().to(i32),
+                           num_frames, k_per_frame)
+
+
+@patch_boxes.register_fake
+def _(points, counts, labels, R, t, ori_k, ratio, frame_index, k_per_frame, num_frames, height,
+      width, size):
+    n = labels.shape[0]
+    return (R.new_empty(n, 4, dtype=torch.float32), R.new_empty(n, 8, dtype=torch.int32),
+            R.new_empty(n, 3, 3, dtype=torch.float32), R.new_empty(n, 3, 3, dtype=torch.float32),
+            R.new_empty(n, dtype=torch.uint8))
+
+
+@torch.library.custom_op("scflow::extract_patches", mutates_args=(), device_types="cuda")
+def extract_patches(frames: Tensor, frame_index: Tensor, geom: Tensor, valid: Tensor, size: int,
+                    pad: float, mean: Optional[List[float]], std: Optional[List[float]],
+                    to_rgb: bool, quantize: bool, nearest: bool) -> Tensor:
+    """Crop → Resize → Pad → Normalize of N patches in one launch (``ops.extract_patches``;
+    replaces mmcv's imcrop / imrescale / impad / imnormalize per object on the host): frames
+    [F, H, W, C] uint8 or float32 → [N, C, size, size] float32.  Not differentiable."""
+    return ops.extract_patches(frames.contiguous(), frame_index.contiguous().to(torch.int32),
+                               geom.contiguous(), valid.contiguous(), size, pad, mean, std, to_rgb,
+                               quantize, nearest)
+
+
+@extract_patches.register_fake
+def _(frames, frame_index, geom, valid, size, pad, mean, std, to_rgb, quantize, nearest):
+    return frames.new_empty(frame_index.shape[0], frames.shape[3], size, size, dtype=torch.float32)

@@ -781,6 +781,133 @@ def pnp_ransac(flow: Tensor, depth: Tensor, R: Tensor, t: Tensor, K: Tensor,
     return Ro, to, ok != 0, inl
 
 
+# ------------------------------------------------------------------------------- patches
+PATCH_MAX_CROP = _lib.PATCH_MAX_CROP
+
+
+def _require_patch(t: Tensor, name: str, dtype, shape: Optional[tuple] = None) -> None:
+    """The patch ops' argument check: every refusal (type, device, dtype, contiguity, shape; a
+    None in ``shape`` matches any extent) is a ``ScflowError`` raised before device work."""
+    dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+    if not isinstance(t, torch.Tensor):
+        raise ScflowError(f"{name} must be a tensor, got {type(t).__name__}")
+    if t.device.type != "cuda":
+        raise ScflowError(f"{name} is on {t.device}: the patch kernels only run on a ROCm GPU "
+                          "(no CPU fallback)")
+    if t.dtype not in dtypes:
+        raise ScflowError(f"{name} must be {' or '.join(map(str, dtypes))}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ScflowError(f"{name} must be contiguous")
+    if shape is not None and (t.dim() != len(shape) or any(
+            s is not None and s != d for s, d in zip(shape, t.shape))):
+        want = "[" + ", ".join("*" if s is None else str(s) for s in shape) + "]"
+        raise ScflowError(f"{name} must be {want}, got {list(t.shape)}")
+
+
+def _require_patch_size(size: int) -> None:
+    if size < 4 or size > 4096 or size % 4:
+        raise ScflowError(f"the patch side must be a multiple of 4 in [4, 4096], got {size}")
+
+
+def patch_staged(cw: int, channels: int, dtype=torch.uint8, size: int = 256) -> bool:
+    """Whether ``extract_patches`` stages the source rows of a crop ``cw`` pixels wide in LDS
+    (scflow_patch_staged: host only, follows SCFLOW_PATCH_LDS) or reads its taps directly."""
+    rc = _lib.load().scflow_patch_staged(int(cw), int(channels),
+                                         _lib.PATCH_U8 if dtype == torch.uint8 else _lib.PATCH_F32,
+                                         int(size))
+    if rc < 0:
+        check(rc, "scflow_patch_staged")
+    return rc == 1
+
+
+def patch_boxes(points: Tensor, counts: Tensor, labels: Tensor, R: Tensor, t: Tensor, ori_k: Tensor,
+                ratio: Tensor, height: int, width: int, size: int,
+                frame_index: Optional[Tensor] = None, num_frames: int = 0,
+                k_per_frame: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Crop geometry of N objects from their projected model points (scflow_patch_boxes; DESIGN.md
+    §15): points [C, P, 3] with counts [C] int32, labels [N] int32, R [N, 3, 3], t [N, 3], ori_k
+    [N, 3, 3] — or [num_frames, 3, 3] with ``k_per_frame``, indexed by frame_index [N] int32 —
+    ratio [N], the frame's height × width and the patch side → (bbox [N, 4] (l, t, r, b), geom
+    [N, 8] int32 (x1, y1, x2, y2, nw, nh, left, top), T [N, 3, 3], k [N, 3, 3] = T·ori_k, valid [N]
+    uint8).  One launch on the current stream; with frame_index an index outside [0, num_frames)
+    makes its object invalid.  N = 0 returns empty tensors without a launch."""
+    _require_patch_size(size)
+    _require_patch(points, "points", torch.float32, (None, None, 3))
+    c, p, _ = points.shape
+    _require_patch(counts, "counts", torch.int32, (c,))
+    _require_patch(labels, "labels", torch.int32, (None,))
+    n = labels.shape[0]
+    _require_patch(R, "R", torch.float32, (n, 3, 3))
+    _require_patch(t, "t", torch.float32, (n, 3))
+    _require_patch(ratio, "ratio", torch.float32, (n,))
+    if k_per_frame and frame_index is None:
+        raise ScflowError("patch_boxes: ori_k per frame needs frame_index")
+    if frame_index is not None:
+        _require_patch(frame_index, "frame_index", torch.int32, (n,))
+        if num_frames < 1:
+            raise ScflowError(f"patch_boxes: frame_index needs num_frames ≥ 1, got {num_frames}")
+    _require_patch(ori_k, "ori_k", torch.float32, (num_frames if k_per_frame else n, 3, 3))
+    if c < 1 or p < 1 or height < 1 or width < 1:
+        raise ScflowError(f"patch_boxes: empty point table {list(points.shape)} or frame "
+                          f"{height}×{width}")
+    dev = labels.device
+    bbox = torch.empty(n, 4, device=dev, dtype=torch.float32)
+    geom = torch.empty(n, 8, device=dev, dtype=torch.int32)
+    T = torch.empty(n, 3, 3, device=dev, dtype=torch.float32)
+    k = torch.empty(n, 3, 3, device=dev, dtype=torch.float32)
+    valid = torch.empty(n, device=dev, dtype=torch.uint8)
+    if n:
+        _launch("scflow_patch_boxes", labels, _p(points), _p(counts), _p(labels), _p(R), _p(t),
+                _p(ori_k), _p(frame_index), _p(ratio), _p(bbox), _p(geom), _p(T), _p(k), _p(valid),
+                n, c, p, int(bool(k_per_frame)), int(num_frames), int(height), int(width),
+                int(size))
+    return bbox, geom, T, k, valid
+
+
+def extract_patches(frames: Tensor, frame_index: Tensor, geom: Tensor, valid: Tensor, size: int,
+                    pad: float = 128.0, mean: Optional[Sequence[float]] = None,
+                    std: Optional[Sequence[float]] = None, to_rgb: bool = False,
+                    quantize: bool = True, nearest: bool = False) -> Tensor:
+    """Crop, resize and pad N patches in one launch (scflow_patch_extract): frames
+    [F, H, W, 3] uint8 (interleaved) or [F, H, W, 1] uint8 / float32, frame_index [N] int32, geom
+    [N, 8] int32 and valid [N] uint8 of ``patch_boxes`` → [N, C, size, size] float32, planar:
+    cv2's INTER_LINEAR of the inclusive crop (``nearest``: the nearest source pixel), rounded to
+    integer levels with ``quantize``, ``pad`` outside the frame and around the resized crop, then
+    (v − mean[c]) / std[c] per output channel, the channel order reversed first with ``to_rgb``.
+    An invalid object's patch is ``pad`` everywhere.  Runs on the current stream; N = 0 returns an
+    empty tensor without a launch."""
+    _require_patch_size(size)
+    _require_patch(frames, "frames", (torch.uint8, torch.float32), (None, None, None, None))
+    f, h, w, c = frames.shape
+    if not (c == 1 or (c == 3 and frames.dtype == torch.uint8)):
+        raise ScflowError("frames must be [F, H, W, 3] uint8 or [F, H, W, 1] uint8 / float32, got "
+                          f"{list(frames.shape)} {frames.dtype}")
+    if f < 1 or h < 1 or w < 1:
+        raise ScflowError(f"frames must not be empty, got {list(frames.shape)}")
+    _require_patch(frame_index, "frame_index", torch.int32, (None,))
+    n = frame_index.shape[0]
+    _require_patch(geom, "geom", torch.int32, (n, 8))
+    _require_patch(valid, "valid", torch.uint8, (n,))
+    stats = []
+    for name, v, dflt in (("mean", mean, 0.0), ("std", std, 1.0)):
+        v = [dflt] * c if v is None else [float(x) for x in v]
+        if len(v) != c:
+            raise ScflowError(f"{name} must have {c} entries, got {len(v)}")
+        stats.append((ctypes.c_float * c)(*v))
+    if any(s == 0.0 for s in stats[1]):
+        raise ScflowError("std must not be zero")
+    out = torch.empty(n, c, size, size, device=frames.device, dtype=torch.float32)
+    if n:
+        flags = (_lib.PATCH_TO_RGB if to_rgb else 0) | (_lib.PATCH_QUANTIZE if quantize else 0) | \
+            (_lib.PATCH_NEAREST if nearest else 0)
+        _launch("scflow_patch_extract", frames, _p(frames), _p(frame_index), _p(geom), _p(valid),
+                _p(out), n, f, h, w, c,
+                _lib.PATCH_U8 if frames.dtype == torch.uint8 else _lib.PATCH_F32, int(size),
+                float(pad), ctypes.cast(stats[0], ctypes.c_void_p),
+                ctypes.cast(stats[1], ctypes.c_void_p), flags)
+    return out
+
+
 # ------------------------------------------------------------------------------- resampling
 def flow_downsample(flow: Tensor, out0: Chan, h: int, w: int, value_scale: float,
                     out1: Optional[Chan] = None, mask: Optional[Tensor] = None,

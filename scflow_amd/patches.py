@@ -1,0 +1,120 @@
+"""Patches from full frames on the device: crop, resize, pad and the adapted intrinsics.
+
+Reference: the test pipeline ``ComputeBbox → Crop → Resize(keep_ratio) → Pad(center) →
+RemapPose(adapt_intrinsic) → Normalize`` (``datasets/pipelines/formatting.py:42-91``,
+``geometry_transform.py:155-500``, ``configs/refine_datasets/ycbv_real.py:76-99``), which runs per
+object on the host with cv2 / mmcv.  Here it is two HIP launches for all objects of a batch
+(``ops.patch_boxes``, ``ops.extract_patches``; DESIGN.md §15 states the geometry) with no host
+synchronisation: the crop sizes stay in device memory.  Image decoding stays the caller's.
+
+In ``adapt_intrinsic`` mode the pose is unchanged by the crop (``models/utils/pose.py:275-277``):
+a pose refined on the patches under ``internel_k`` is the pose in the original camera.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Tuple, Union
+
+import torch
+
+from . import ops
+from ._lib import ScflowError
+
+Tensor = torch.Tensor
+
+# configs/refine_datasets/ycbv_real.py:12-13, :87
+IMG_NORM_CFG = dict(mean=(0.0, 0.0, 0.0), std=(255.0, 255.0, 255.0))
+
+
+def point_table(renderer) -> Tuple[Tensor, Tensor]:
+    """(points [C, P, 3] float32, counts [C] int32) from the meshes a ``Renderer`` holds, on their
+    device: class ``l`` owns ``points[l, :counts[l]]`` — ALL vertices of its mesh; a label without
+    a mesh has count 0 (its objects come out invalid).  The reference's ``ComputeBbox`` draws 1000
+    random vertices of ``models_eval`` instead (formatting.py:53-55), so its boxes are at most as
+    large as these and differ from run to run."""
+    if not renderer.meshes:
+        raise ScflowError("point_table: the renderer holds no mesh")
+    c = max(renderer.meshes) + 1
+    p = max(m[0].shape[0] for m in renderer.meshes.values())
+    dev = next(iter(renderer.meshes.values()))[0].device
+    points = torch.zeros(c, p, 3, device=dev, dtype=torch.float32)
+    counts = torch.zeros(c, dtype=torch.int32)
+    for lab, m in renderer.meshes.items():
+        points[lab, :m[0].shape[0]] = m[0]
+        counts[lab] = m[0].shape[0]
+    return points, counts.to(dev)
+
+
+def _i32(x: Tensor) -> Tensor:
+    return x.contiguous().to(torch.int32)
+
+
+def frames_to_patches(frames: Tensor, frame_index: Tensor, ref_rotations: Tensor,
+                      ref_translations: Tensor, ori_k: Tensor, labels: Tensor, points: Tensor,
+                      counts: Tensor, size: int = 256, size_ratio: Union[float, Tensor] = 1.1,
+                      pad_val: float = 128, img_norm_cfg: Optional[dict] = None,
+                      to_rgb: bool = True) -> Dict[str, Tensor]:
+    """Decoded frames [F, H, W, 3] uint8 (interleaved, as cv2 decodes them) plus N detections —
+    frame_index [N], reference poses [N, 3, 3] / [N, 3], labels [N], intrinsics ori_k [N, 3, 3] or
+    one per frame [F, 3, 3] — to what ``format_data_test`` hands the refiner:
+
+    * ``real_images`` [N, 3, size, size] float32, normalised with ``img_norm_cfg`` (``mean`` /
+      ``std`` in output channel order, mmcv ``imnormalize``; default the config's 0 / 255) after
+      ``to_rgb`` reversed the channels;
+    * ``internel_k`` [N, 3, 3] = ``transform_matrix`` · ``ori_k``, ``transform_matrix`` [N, 3, 3],
+      ``ori_k`` [N, 3, 3] (per object);
+    * ``valid`` [N] bool and ``crop_boxes`` [N, 4] int32 (x1, y1, x2, y2, inclusive); also the raw
+      ``geom`` [N, 8] int32 for ``extract_maps`` and ``bboxes`` [N, 4].
+
+    ``points`` / ``counts``: the model point table (``point_table``).  ``size_ratio``: the crop's
+    side over the box's, 1.1 at test time; a tensor [N] gives every object its own — the training
+    pipeline's ``U(1.0, 1.25)``, drawn by the caller.  An invalid object (behind the camera, off
+    the frame, …) gets a ``pad_val`` patch, the identity transform and ``internel_k = ori_k``.
+    Everything runs on the current stream without a host synchronisation."""
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
+        raise ScflowError("frames must be a [F, H, W, 3] uint8 tensor")
+    f, h, w, _ = frames.shape
+    n = labels.shape[0]
+    cfg = dict(IMG_NORM_CFG if img_norm_cfg is None else img_norm_cfg)
+    to_rgb = bool(cfg.get("to_rgb", to_rgb))
+    fidx = _i32(frame_index)
+    per_frame = ori_k.shape[0] != n
+    if per_frame and ori_k.shape[0] != f:
+        raise ScflowError(f"ori_k must be [{n}, 3, 3] or [{f}, 3, 3], got {list(ori_k.shape)}")
+    if isinstance(size_ratio, torch.Tensor):
+        ratio = size_ratio.contiguous().float()
+    else:
+        ratio = torch.full((n,), float(size_ratio), device=frames.device, dtype=torch.float32)
+    ori_k = ori_k.contiguous().float()
+    bbox, geom, T, k, valid = ops.patch_boxes(
+        points.contiguous().float(), _i32(counts), _i32(labels), ref_rotations.contiguous().float(),
+        ref_translations.contiguous().float(), ori_k, ratio, h, w, size, frame_index=fidx,
+        num_frames=f, k_per_frame=per_frame)
+    images = ops.extract_patches(frames.contiguous(), fidx, geom, valid, size, pad=float(pad_val),
+                                 mean=cfg["mean"], std=cfg["std"], to_rgb=to_rgb)
+    if per_frame:  # an index outside the frames made its object invalid; clamp it for the gather
+        ori_k = ori_k[fidx.clamp(0, f - 1).long()]
+    return dict(real_images=images, internel_k=k, transform_matrix=T, ori_k=ori_k,
+                valid=valid != 0, crop_boxes=geom[:, :4], geom=geom, bboxes=bbox)
+
+
+def extract_maps(maps: Tensor, frame_index: Tensor, geom: Tensor, valid: Optional[Tensor] = None,
+                 size: int = 256, mode: str = "bilinear") -> Tensor:
+    """Single-channel maps [F, H, W] or [F, H, W, 1] (float32 depth, uint8 masks) under the
+    geometry ``frames_to_patches`` returned (``geom`` [N, 8], ``valid`` [N] bool / uint8 or None =
+    all valid) → [N, 1, size, size] float32.  ``mode='bilinear'`` (depth): cv2's INTER_LINEAR, pad
+    0, not quantised; ``mode='nearest'`` (masks): the nearest source pixel, pad 0.
+
+    The result is DEFINED by ``transform_matrix``: pixel (u, v) of a map patch shows the frame
+    point T⁻¹(u, v), as the image patch does.  The reference's ``BitmapMasks.crop / rescale / pad``
+    are not reproduced: they take the crop box as exclusive (one column and row fewer than mmcv's
+    inclusive ``imcrop`` of the image), so its masks land up to a pixel off its own image."""
+    if mode not in ("bilinear", "nearest"):
+        raise ScflowError(f"extract_maps: mode must be 'bilinear' or 'nearest', got {mode!r}")
+    if isinstance(maps, torch.Tensor) and maps.dim() == 3:
+        maps = maps.unsqueeze(-1)
+    n = geom.shape[0]
+    if valid is None:
+        valid = torch.ones(n, device=geom.device, dtype=torch.uint8)
+    return ops.extract_patches(maps.contiguous(), _i32(frame_index), geom.contiguous(),
+                               valid.contiguous().to(torch.uint8), size, pad=0.0, quantize=False,
+                               nearest=mode == "nearest")

@@ -213,6 +213,35 @@ class SCFlowRefiner(_RefinerBase):
             self.decoder.iters = iters
         return R, t, out
 
+    def refine_frames(self, frames: Tensor, frame_index: Tensor, ref_rotations: Tensor,
+                      ref_translations: Tensor, ori_k: Tensor, labels: Tensor,
+                      cycles: Optional[int] = None, points=None):
+        """Decoded frames [F, H, W, 3] uint8 plus N detections (frame_index, reference poses,
+        ori_k per object or per frame, labels) → poses in the ORIGINAL camera:
+        ``patches.frames_to_patches`` (crop, resize, pad and the adapted intrinsics on the device,
+        at the renderer's image size) and then ``refine`` on its patches and ``internel_k`` —
+        with the intrinsics adapted the crop leaves the pose as it is (pose.py:275-277).  Returns
+        (rotations, translations, valid, data): where ``valid`` is False the pose is the input
+        pose; ``data`` is ``frames_to_patches``' dict.  ``points``: a (points, counts) table,
+        default ``patches.point_table`` of the renderer's meshes (built once)."""
+        from . import patches
+        if self.renderer is None:
+            raise RuntimeError("SCFlowRefiner was built without a renderer config")
+        if points is None:
+            if getattr(self, "_point_table", None) is None or \
+                    self._point_table[0].device != self.renderer._device:
+                self._point_table = patches.point_table(self.renderer)
+            points = self._point_table
+        data = patches.frames_to_patches(frames, frame_index, ref_rotations, ref_translations,
+                                         ori_k, labels, points[0], points[1],
+                                         size=self.renderer.image_size[0])
+        R, t, _ = self.refine(data["real_images"], ref_rotations, ref_translations,
+                              data["internel_k"], labels, cycles=cycles)
+        valid = data["valid"]
+        R = torch.where(valid.view(-1, 1, 1), R, ref_rotations)
+        t = torch.where(valid.view(-1, 1), t, ref_translations)
+        return R, t, valid, data
+
     # ------------------------------------------------------------------ reference API
     def get_pose(self, render_images: Tensor, real_images: Tensor, ref_rotation: Tensor,
                  ref_translation: Tensor, depth: Tensor, internel_k: Tensor, label: Tensor,

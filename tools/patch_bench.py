@@ -1,0 +1,143 @@
+"""Timing of the patch path: scflow_patch_boxes + scflow_patch_extract next to the
+per-object PyTorch loop, on the device, alternating in one process.
+
+usage: python tools/patch_bench.py [--frames 4] [--height 480] [--width 640] [--objects 32]
+                                   [--size 256] [--rounds 9] [--steps 50] [--json out.json]
+
+The scene: `frames` seeded random uint8 frames, `objects` ellipsoid-sized point clouds posed in
+front of a YCB-V-like camera (seeded; the crop sizes are printed), ratio 1.1.  Timed, each window
+between two device events around `steps` calls, after a warm-up of every shape:
+
+* `hip`: the two launches (`ops.patch_boxes`, `ops.extract_patches`) — and `hip_staged`, the same
+  with SCFLOW_PATCH_LDS=1 (source rows staged in LDS instead of every tap read from global memory);
+* `torch_loop`: tests/patch_restatement.py `torch_patches` on the geometry the box kernel
+  produced — pad, slice, one `interpolate` per object, after `geom.tolist()`, its host
+  synchronisation.  It does not include the projection and box arithmetic, so the ratio favours it.
+
+Prints the medians, the ratio, the bytes the extract launch has to move (from the shapes) and one
+JSON line.  No threshold: the parent has no such path.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def scene(a, dev):
+    rng = np.random.default_rng(0)
+    frames = torch.from_numpy(rng.integers(0, 256, (a.frames, a.height, a.width, 3), dtype=np.uint8))
+    points = rng.uniform(-1.0, 1.0, (21, 1000, 3)).astype(np.float32)
+    points *= rng.uniform(45.0, 135.0, (21, 1, 1)).astype(np.float32) * np.array([1.0, 0.76, 0.6], np.float32)
+    K = np.array([[1066.8, 0, 312.99], [0, 1067.5, 241.31], [0, 0, 1]], np.float32)
+    Rs, ts = [], []
+    for _ in range(a.objects):
+        q, _r = np.linalg.qr(rng.normal(size=(3, 3)))
+        Rs.append(q * np.sign(np.linalg.det(q)))
+        tz = rng.uniform(700.0, 1300.0)
+        ts.append([rng.uniform(-0.22, 0.22) * tz, rng.uniform(-0.16, 0.16) * tz, tz])
+    T = lambda x, dt=torch.float32: torch.as_tensor(np.asarray(x)).to(dt).to(dev)  # noqa: E731
+    return dict(frames=frames.to(dev), points=T(points), counts=T(np.full(21, 1000), torch.int32),
+                labels=T(rng.integers(0, 21, a.objects), torch.int32), R=T(np.stack(Rs)), t=T(ts),
+                K=T(np.repeat(K[None], a.frames, 0)),
+                fidx=T(rng.integers(0, a.frames, a.objects), torch.int32),
+                ratio=torch.full((a.objects,), 1.1, device=dev))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=4)
+    ap.add_argument("--height", type=int, default=480)
+    ap.add_argument("--width", type=int, default=640)
+    ap.add_argument("--objects", type=int, default=32)
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("patch_bench needs a GPU: a CPU run says nothing about these timings")
+    from scflow_amd import _lib, ops
+    from tests.patch_restatement import torch_patches
+    dev = torch.device("cuda")
+    s = scene(a, dev)
+    norm = dict(pad=128.0, mean=[0.0] * 3, std=[255.0] * 3, to_rgb=True)
+
+    def boxes():
+        return ops.patch_boxes(s["points"], s["counts"], s["labels"], s["R"], s["t"], s["K"],
+                               s["ratio"], a.height, a.width, a.size, frame_index=s["fidx"],
+                               num_frames=a.frames, k_per_frame=True)
+
+    def hip():
+        _, geom, _, _, valid = boxes()
+        return ops.extract_patches(s["frames"], s["fidx"], geom, valid, a.size, **norm)
+
+    _, geom, _, _, valid = boxes()
+
+    def loop():
+        return torch_patches(s["frames"], s["fidx"], geom, valid, a.size, **norm)
+
+    def set_lds(on):
+        os.environ["SCFLOW_PATCH_LDS"] = "1" if on else "0"
+        _lib.reload_switches()
+
+    run = {"hip": (False, hip), "hip_staged": (True, hip), "torch_loop": (False, loop)}
+    outs = {}
+    for k, (lds, f) in run.items():  # warm every shape (code objects, allocator)
+        set_lds(lds)
+        for _ in range(3):
+            outs[k] = f()
+    torch.cuda.synchronize()
+    times = {k: [] for k in run}
+    for _ in range(a.rounds):
+        for k, (lds, f) in run.items():
+            set_lds(lds)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.steps):
+                f()
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1) / a.steps)
+    set_lds(True)  # for the staging query below
+    g = geom.cpu().numpy()
+    cw, ch = g[:, 2] - g[:, 0] + 1, g[:, 3] - g[:, 1] + 1
+    nv = int(valid.sum())
+    staged = sum(ops.patch_staged(int(w), 3, torch.uint8, a.size) for w, v in zip(cw, valid.tolist()) if v)
+    # what the extract launch has to move: every valid crop read once (uint8 × 3), every patch written
+    bytes_in = int((cw * ch)[valid.cpu().numpy() != 0].sum()) * 3
+    bytes_out = a.objects * 3 * a.size * a.size * 4
+    del os.environ["SCFLOW_PATCH_LDS"]
+    _lib.reload_switches()
+    res = dict(frames=a.frames, height=a.height, width=a.width, objects=a.objects, size=a.size,
+               rounds=a.rounds, steps=a.steps, valid=nv, staged=staged,
+               crop_min=int(cw[valid.cpu().numpy() != 0].min()), crop_max=int(cw.max()),
+               bytes_in=bytes_in, bytes_out=bytes_out,
+               same_bits_staged_direct=bool(torch.equal(outs["hip"], outs["hip_staged"])),
+               max_diff_vs_torch_levels=float((outs["hip"] - outs["torch_loop"]).abs().max() * 255))
+    for k, v in times.items():
+        res[k] = dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v))
+        print(f"{k}: median {res[k]['median_ms']:.4f} ms/call (min {min(v):.4f}, max {max(v):.4f})")
+    res["torch_over_hip"] = res["torch_loop"]["median_ms"] / res["hip"]["median_ms"]
+    print(f"F={a.frames} frames of {a.height}×{a.width}, N={a.objects} objects ({nv} valid, crops "
+          f"{res['crop_min']}-{res['crop_max']} px, {staged} of them staged under SCFLOW_PATCH_LDS=1), S={a.size}: "
+          f"torch loop / HIP = {res['torch_over_hip']:.1f}×; the extract launch reads "
+          f"{bytes_in / 1e6:.2f} MB and writes {bytes_out / 1e6:.2f} MB; staged and direct routes "
+          f"{'equal' if res['same_bits_staged_direct'] else 'DIFFER'} bit for bit; max difference "
+          f"from the torch loop {res['max_diff_vs_torch_levels']:.3f} levels")
+    line = json.dumps(res)
+    print(line)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
