@@ -179,6 +179,19 @@ def test_decoder_512_feat64():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("B", [1, 3])
+def test_decoder_odd_batch_matches_oracle(B):
+    """Batch sizes at which the pose head's gather conv has a ragged pixel tile (B = 1: M = 16,
+    half a tile; B = 3: M = 48) and its GroupNorm reduce other slab counts than at B = 2, 4, 8."""
+    inp = decoder_inputs(B, 256, seed=33 + B)
+    dec = build_decoder(2, seed=3)
+    out = run_gpu(dec, inp)
+    sd = {k: v.detach().cpu() for k, v in dec.state_dict().items()}
+    ref = orc.decoder_forward(sd, **inp, iters=2)
+    check_against(out, ref[0][-1], ref[1][-1], torch.stack(ref[2]).numpy(), torch.stack(ref[3]).numpy())
+
+
+@pytest.mark.gpu
 def test_decoder_iters_attribute_is_reread():
     inp = decoder_inputs(1, 256, seed=2)
     dec = build_decoder(4)

@@ -798,7 +798,11 @@ def test_cpu_tensor_rejected(ops):
 
 
 # ------------------------------------------------------------------------------ a7 pose head
-@pytest.mark.parametrize("n,feat", [(16, 32), (32, 32), (3, 64)])
+@pytest.mark.parametrize("n,feat", [(16, 32), (32, 32), (3, 64),
+                                    # batch 1 (conv3's M = 16: half a pixel tile; 14 conv1 slabs),
+                                    # 2, 5 (M = 80: ragged tile), 33 (the unsplit FCs' row-block
+                                    # loop), batch 1 at 64×64
+                                    (1, 32), (2, 32), (5, 32), (33, 32), (1, 64)])
 def test_pose_head_hip_vs_oracle(ops, n, feat):
     from scflow_amd import synthetic
     from scflow_amd.modules import MultiClassPoseHead
