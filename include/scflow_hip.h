@@ -890,6 +890,81 @@ int scflow_patch_extract(const void* frames, const int* frame_index, const int* 
                          const float* std, int flags, void* stream);
 int scflow_patch_staged(int cw, int channels, int dtype, int size);
 
+/* Training patches from full frames: the reference's training formatting PoseJitter
+ * → ComputeBbox → Crop(size_range) → RandomHSV → RandomNoise → RandomSmooth → Resize → Pad →
+ * RemapPose → Normalize (configs/refine_models/scflow_ycbv_real.py:50-93, datasets/pipelines/
+ * jitter.py:51-79, geometry_transform.py:232-254, color_transform.py:78-134) as scflow_train_draw →
+ * scflow_patch_boxes → scflow_train_patch_extract on the caller's stream with no host work between.
+ *
+ * Random numbers: stateless Philox4x32-10 (scflow_philox4x32: the host's evaluation of one call,
+ *   counter[4], key[2] → out[4]).  key = (seed low, seed high); counter = (index, object, stream |
+ *   (step high 32 bits) << 8, step low 32 bits); object = the object's index in the call +
+ *   object_offset; stream = SCFLOW_RNG_*; step < 2^56.  u[0,1) = (w >> 8)·2^-24; u(0,1] =
+ *   ((w >> 8) + 0.5)·2^-24 in fp32 (the largest word rounds to 1); normals by Box–Muller with the
+ *   precise logf / sqrtf / cosf / sinf: words (w0, w1) → z0 = sqrtf(−2·logf(u(w0)))·cosf(2π·u[w1)),
+ *   z1 the same with sinf, (w2, w3) → z2 (cos).
+ * scflow_train_draw: per object, for try k = 0 .. max_tries−1 (≤ SCFLOW_TRAIN_MAX_TRIES): angles
+ *   (a, b, c) = cfg[ANGLE_MEAN] + cfg[ANGLE_STD]·z of the call (0, object, JITTER + k), degrees;
+ *   ΔR = Rx(c)·Ry(b)·Rz(a) (scipy's from_euler('zyx')); R = ΔR·R_gt; rot = acos(clip((tr(R·R_gtᵀ) −
+ *   1)/2, −1, 1)) in degrees, rejected when > cfg[ANGLE_LIMIT]; Δt = cfg[T_MEAN..] + cfg[T_STD..]·z
+ *   of the call (1, object, JITTER + k), rejected when ‖Δt‖ > cfg[TRANS_LIMIT]; add = mean over
+ *   points[label][0 .. counts[label]) of ‖(R_gt·X + t_gt) − (R·X + t_gt + Δt)‖ / diameters[label]
+ *   (0 for a label without points or diameter), rejected when > cfg[ADD_LIMIT].  A limit below 0
+ *   is off.  The first accepted try gives R_ref, t_ref, errors[i] = (add, rot, ‖Δt‖), ok = 1,
+ *   tries = k + 1; without one ok = 0, tries = max_tries, the GT pose and zero errors.  ratio[i]
+ *   = cfg[RATIO_LO] + u·(cfg[RATIO_HI] − cfg[RATIO_LO]) from word 0 of (0, object, CROP).
+ *   aug[i][8] from the words of (0, object, COLOUR): a, b, c = 1 + (2u − 1)·cfg[H_RATIO..],
+ *   sigma = u·cfg[NOISE_RATIO]; and of (1, object, COLOUR): ksize = 2·min(int(u·nk), nk − 1) + 1
+ *   with nk = (max_kernel_size + 1) div 2 (max_kernel_size ≤ 5), then stage-mask bits
+ *   SCFLOW_AUG_HSV / NOISE / BLUR, each set where u ≤ cfg[P_HSV..]; aug[i] = (a, b, c, sigma,
+ *   ksize, mask, 0, 0).  cfg: a HOST array of SCFLOW_TRAIN_CFG_LEN floats read by the call.
+ * scflow_train_patch_extract: scflow_patch_extract for uint8 × 3 BGR frames (same geometry, validity
+ *   re-check, flags TO_RGB / QUANTIZE, mean / std, output; pad an integer level) with the stages of
+ *   aug[i] applied to every crop pixel — pad pixels outside the frame included — before the
+ *   bilinear resample reads the crop as uint8: HSV (cv2's 8-bit BGR2HSV in integers, gains a, b, c
+ *   in fp32 clipped to 179 / 255 / 255 where the gain is ≥ 1, truncated, cv2's 8-bit HSV2BGR in
+ *   fp32), noise (level + (z·sigma)·255 clipped to [0, 255] and truncated; z = the three normals
+ *   of (y·cw + x, object, NOISE) for B, G, R), box blur (ksize 3 or 5, BORDER_REFLECT_101 at the
+ *   crop's edges, (2·Σ + k²) div (2·k²)).  A stage mask of 0 gives scflow_patch_extract's bits.
+ *   The augmented crop window a tile of output pixels reads is staged once in LDS where it fits;
+ *   otherwise, and with SCFLOW_PATCH_AUG_DIRECT, every tap computes its own window.  Both routes
+ *   give the same bits, and neither depends on size or geom[4..8) for the noise a crop pixel gets. */
+#define SCFLOW_TRAIN_CFG_LEN 20
+#define SCFLOW_TRAIN_ANGLE_MEAN 0
+#define SCFLOW_TRAIN_ANGLE_STD 1
+#define SCFLOW_TRAIN_T_MEAN 2  /* x, y, z */
+#define SCFLOW_TRAIN_T_STD 5   /* x, y, z */
+#define SCFLOW_TRAIN_ANGLE_LIMIT 8
+#define SCFLOW_TRAIN_TRANS_LIMIT 9
+#define SCFLOW_TRAIN_ADD_LIMIT 10
+#define SCFLOW_TRAIN_RATIO_LO 11
+#define SCFLOW_TRAIN_RATIO_HI 12
+#define SCFLOW_TRAIN_H_RATIO 13 /* h, s, v */
+#define SCFLOW_TRAIN_NOISE_RATIO 16
+#define SCFLOW_TRAIN_P_HSV 17 /* hsv, noise, blur */
+#define SCFLOW_TRAIN_MAX_TRIES 224
+#define SCFLOW_RNG_CROP 0
+#define SCFLOW_RNG_COLOUR 1
+#define SCFLOW_RNG_NOISE 2
+#define SCFLOW_RNG_JITTER 16 /* + try */
+#define SCFLOW_AUG_HSV 1
+#define SCFLOW_AUG_NOISE 2
+#define SCFLOW_AUG_BLUR 4
+#define SCFLOW_PATCH_AUG_DIRECT 8
+void scflow_philox4x32(const unsigned int* counter, const unsigned int* key, unsigned int* out);
+int scflow_train_draw(const float* points, const int* counts, const int* labels,
+                      const float* diameters, const float* R_gt, const float* t_gt, const float* cfg,
+                      float* R_ref, float* t_ref, float* errors, unsigned char* ok, int* tries,
+                      float* ratio, float* aug, int n, int num_classes, int max_points,
+                      int max_tries, int max_kernel_size, unsigned long long seed,
+                      unsigned long long step, unsigned int object_offset, void* stream);
+int scflow_train_patch_extract(const void* frames, const int* frame_index, const int* geom,
+                             const unsigned char* valid, const float* aug, float* out, int n,
+                             int num_frames, int height, int width, int size, int pad,
+                             const float* mean, const float* std, int flags,
+                             unsigned long long seed, unsigned long long step,
+                             unsigned int object_offset, void* stream);
+
 /* Profiling helper (bench.py roofline timing; no reference equivalent): a one-thread kernel
  * that stores the GPU's constant-rate wall clock (s_memrealtime) into stamps[idx].  Enqueued on
  * the stream of the kernel being timed, before and after it; as an ordinary kernel it is also a

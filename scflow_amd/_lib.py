@@ -28,6 +28,14 @@ PNP_MAX_HYPS = 256  # SCFLOW_PNP_MAX_HYPS
 PATCH_MAX_CROP = 8192  # SCFLOW_PATCH_MAX_CROP
 PATCH_U8, PATCH_F32 = 0, 1  # scflow_patch_extract's dtype
 PATCH_TO_RGB, PATCH_QUANTIZE, PATCH_NEAREST = 1, 2, 4  # scflow_patch_extract's flags
+PATCH_AUG_DIRECT = 8  # scflow_train_patch_extract's flag SCFLOW_PATCH_AUG_DIRECT
+AUG_HSV, AUG_NOISE, AUG_BLUR = 1, 2, 4  # SCFLOW_AUG_*: the stage mask in aug[:, 5]
+RNG_CROP, RNG_COLOUR, RNG_NOISE, RNG_JITTER = 0, 1, 2, 16  # SCFLOW_RNG_*
+TRAIN_MAX_TRIES = 224  # SCFLOW_TRAIN_MAX_TRIES
+# SCFLOW_TRAIN_*: where scflow_train_draw's cfg holds what
+TRAIN_CFG = ("angle_mean", "angle_std", "x_mean", "y_mean", "z_mean", "x_std", "y_std", "z_std",
+             "angle_limit", "translation_limit", "add_limit", "ratio_lo", "ratio_hi", "h_ratio",
+             "s_ratio", "v_ratio", "noise_ratio", "p_hsv", "p_noise", "p_blur")
 
 
 class ConvArgs(ctypes.Structure):
@@ -267,6 +275,11 @@ SIGNATURES = {
     "scflow_patch_boxes": (c_int, [c_vp] * 13 + [c_int] * 8 + [c_vp]),
     "scflow_patch_extract": (c_int, [c_vp] * 5 + [c_int] * 7 + [c_float, c_vp, c_vp, c_int, c_vp]),
     "scflow_patch_staged": (c_int, [c_int, c_int, c_int, c_int]),
+    "scflow_philox4x32": (None, [c_vp, c_vp, c_vp]),
+    "scflow_train_draw": (c_int, [c_vp] * 14 + [c_int] * 5 +
+                          [ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, c_vp]),
+    "scflow_train_patch_extract": (c_int, [c_vp] * 6 + [c_int] * 6 + [c_vp, c_vp, c_int,
+                                 ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, c_vp]),
     "scflow_timestamp": (c_int, [c_vp, c_int, c_vp]),
     "scflow_wallclock_khz": (c_ll, []),
 }

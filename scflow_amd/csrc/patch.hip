@@ -14,18 +14,15 @@
 //
 // Every fp32 expression here is part of the contract (tests/patch_restatement.py restates it
 // operation by operation), so contraction into FMAs is off for the whole file.
-#include "common.h"
+#include "patch_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int PB_THREADS = 256;
-constexpr int PX_THREADS = 256;
 constexpr int PX_LDS_BYTES = 32 * 1024;  // staging budget of one workgroup
 constexpr int PX_MAX_SLOTS = 64;         // two source rows per output row, ≤ 32 rows per band
-constexpr int PX_MAX_CROP = 16384;       // crop sides the extract kernel accepts from geom
-constexpr int PX_MAX_ORIGIN = 1 << 20;   // |x1|, |y1| it accepts (keeps every index in 32 bits)
 
 // 0: every tap is read from global memory (the measured-faster route at the sizes timed,
 // DESIGN.md §15); other: source rows staged in LDS where the crop row fits the budget
@@ -45,17 +42,6 @@ __host__ __device__ inline int px_row_bytes(int cw, int bpp) { return (cw * bpp 
 __host__ __device__ inline bool px_staged(int cw, int bpp, int S) {
   return cw >= 1 && cw <= PX_MAX_CROP &&
          2ll * px_rows(S) * px_row_bytes(cw, bpp) <= (long long)PX_LDS_BYTES;
-}
-
-// c = a·b, row-major 3×3, every element summed over k = 0, 1, 2 in that order
-__device__ inline void mat3_mul(const float* a, const float* b, float* c) {
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      float acc = a[3 * i] * b[j];
-      acc = acc + a[3 * i + 1] * b[3 + j];
-      acc = acc + a[3 * i + 2] * b[6 + j];
-      c[3 * i + j] = acc;
-    }
 }
 
 struct PatchBoxArgs {
@@ -176,20 +162,6 @@ struct PatchExtractArgs {
   float mean[3], std[3];
   int to_rgb, quantize, nearest, use_lds;
 };
-
-// cv2's INTER_LINEAR source coordinate of output index o on an axis of n source and no output
-// samples, the exact rational ((2o + 1)·n − no) / (2·no): its floor i0 and fraction f, clamped to
-// the first / last sample.  f is the only rounded quantity.
-__device__ inline void linear_coord(int o, int n, int no, int& i0, float& f) {
-  const int num = (2 * o + 1) * n - no, den = 2 * no;
-  if (num < 0) {
-    i0 = 0, f = 0.f;
-    return;
-  }
-  i0 = num / den;
-  f = (float)(num - i0 * den) / (float)den;
-  if (i0 >= n - 1) i0 = n - 1, f = 0.f;
-}
 
 template <typename T, int C>
 __global__ __launch_bounds__(PX_THREADS) void patch_extract_kernel(PatchExtractArgs a) {

@@ -22,6 +22,11 @@ op                             reference                                        
                                geometry, geometry_transform.py:155-500
 ``scflow::extract_patches``    mmcv imcrop, imrescale, impad, imnormalize of the       no
                                same pipeline, all objects in one launch
+``scflow::train_draw``         PoseJitter's rejection loop, Crop's size draw and the    no
+                               colour transforms' draws, jitter.py:51-79,
+                               color_transform.py:78-134
+``scflow::patch_extract_aug``  ``extract_patches`` with RandomHSV / RandomNoise /       no
+                               RandomSmooth on the crop, in the same launch
 =============================  =====================================================  =========
 
 The backward formulas are ops of their own (``scflow::corr_pyramid_backward``,
@@ -400,3 +405,54 @@ def extract_patches(frames: Tensor, frame_index: Tensor, geom: Tensor, valid: Te
 @extract_patches.register_fake
 def _(frames, frame_index, geom, valid, size, pad, mean, std, to_rgb, quantize, nearest):
     return frames.new_empty(frame_index.shape[0], frames.shape[3], size, size, dtype=torch.float32)
+
+
+@torch.library.custom_op("scflow::train_draw", mutates_args=(), device_types="cuda")
+def train_draw(points: Tensor, counts: Tensor, labels: Tensor, diameters: Tensor, R_gt: Tensor,
+               t_gt: Tensor, cfg: List[float], max_kernel_size: int, max_tries: int, seed: int,
+               step: int, object_offset: int
+               ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Pose jitter, crop ratio and colour parameters from the counter-based generator
+    (``ops.train_draw``; replaces PoseJitter's rejection loop, jitter.py:51-79, Crop's size draw,
+    geometry_transform.py:232-254, and the draws of RandomHSV / RandomNoise / RandomSmooth,
+    color_transform.py:78-134, per object on the host): ``cfg`` in the order of ``_lib.TRAIN_CFG``
+    → (R_ref, t_ref, errors [N, 3], ok [N] uint8, tries [N] int32, ratio [N], aug [N, 8]).
+    Not differentiable."""
+    from ._lib import TRAIN_CFG
+    i32 = torch.int32
+    d = dict(zip(TRAIN_CFG, cfg), max_kernel_size=max_kernel_size)
+    return ops.train_draw(points.contiguous().float(), counts.contiguous().to(i32),
+                          labels.contiguous().to(i32), diameters.contiguous().float(),
+                          R_gt.contiguous().float(), t_gt.contiguous().float(), d, seed, step,
+                          object_offset, max_tries)
+
+
+@train_draw.register_fake
+def _(points, counts, labels, diameters, R_gt, t_gt, cfg, max_kernel_size, max_tries, seed, step,
+      object_offset):
+    n, f32 = labels.shape[0], torch.float32
+    return (R_gt.new_empty(n, 3, 3, dtype=f32), R_gt.new_empty(n, 3, dtype=f32),
+            R_gt.new_empty(n, 3, dtype=f32), R_gt.new_empty(n, dtype=torch.uint8),
+            R_gt.new_empty(n, dtype=torch.int32), R_gt.new_empty(n, dtype=f32),
+            R_gt.new_empty(n, 8, dtype=f32))
+
+
+@torch.library.custom_op("scflow::patch_extract_aug", mutates_args=(), device_types="cuda")
+def patch_extract_aug(frames: Tensor, frame_index: Tensor, geom: Tensor, valid: Tensor, aug: Tensor,
+                      size: int, seed: int, step: int, object_offset: int, pad: int,
+                      mean: Optional[List[float]], std: Optional[List[float]], to_rgb: bool,
+                      quantize: bool) -> Tensor:
+    """Crop → RandomHSV → RandomNoise → RandomSmooth → Resize → Pad → Normalize of N patches in one
+    launch (``ops.extract_patches_aug``; replaces cv2 / mmcv per object on the host,
+    color_transform.py:78-134): frames [F, H, W, 3] uint8 BGR → [N, 3, size, size] float32.  Not
+    differentiable."""
+    return ops.extract_patches_aug(frames.contiguous(), frame_index.contiguous().to(torch.int32),
+                                   geom.contiguous(), valid.contiguous(), aug.contiguous().float(),
+                                   size, seed, step, object_offset, pad, mean, std, to_rgb,
+                                   quantize)
+
+
+@patch_extract_aug.register_fake
+def _(frames, frame_index, geom, valid, aug, size, seed, step, object_offset, pad, mean, std, to_rgb,
+      quantize):
+    return frames.new_empty(frame_index.shape[0], 3, size, size, dtype=torch.float32)

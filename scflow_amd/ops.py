@@ -908,6 +908,108 @@ def extract_patches(frames: Tensor, frame_index: Tensor, geom: Tensor, valid: Te
     return out
 
 
+def _require_counter(seed: int, step: int, object_offset: int) -> None:
+    if not (0 <= seed < 2 ** 64 and 0 <= step < 2 ** 56 and 0 <= object_offset < 2 ** 32):
+        raise ScflowError(f"seed must be in [0, 2^64), step in [0, 2^56) and object_offset in "
+                          f"[0, 2^32), got {seed}, {step}, {object_offset}")
+
+
+def philox4x32(counter: Sequence[int], key: Sequence[int]) -> Tuple[int, int, int, int]:
+    """One Philox4x32-10 call as the kernels make it (scflow_philox4x32: host only)."""
+    c, k, o = (ctypes.c_uint * 4)(*counter), (ctypes.c_uint * 2)(*key), (ctypes.c_uint * 4)()
+    _lib.load().scflow_philox4x32(ctypes.cast(c, ctypes.c_void_p), ctypes.cast(k, ctypes.c_void_p),
+                                  ctypes.cast(o, ctypes.c_void_p))
+    return tuple(o)
+
+
+def train_draw(points: Tensor, counts: Tensor, labels: Tensor, diameters: Tensor, R_gt: Tensor,
+               t_gt: Tensor, cfg: dict, seed: int, step: int, object_offset: int = 0,
+               max_tries: int = 32
+               ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Pose jitter, crop ratio and colour parameters of N objects in one launch (scflow_train_draw;
+    DESIGN.md §17; the reference's PoseJitter, Crop's size draw and the draws of RandomHSV /
+    RandomNoise / RandomSmooth): points [C, P, 3] with counts [C] int32 and diameters [C], labels
+    [N] int32, GT poses R_gt [N, 3, 3] / t_gt [N, 3], ``cfg`` a dict with the keys of
+    ``_lib.TRAIN_CFG`` plus ``max_kernel_size`` (``patches.TRAIN_AUG`` holds the config's) →
+    (R_ref [N, 3, 3], t_ref [N, 3], errors [N, 3] = (add, rot, trans), ok [N] uint8, tries [N]
+    int32, ratio [N], aug [N, 8]).  Everything is a function of (seed, step, object_offset + i)
+    alone.  Runs on the current stream; N = 0 returns empty tensors without a launch."""
+    _require_patch(points, "points", torch.float32, (None, None, 3))
+    c, p, _ = points.shape
+    _require_patch(counts, "counts", torch.int32, (c,))
+    _require_patch(diameters, "diameters", torch.float32, (c,))
+    _require_patch(labels, "labels", torch.int32, (None,))
+    n = labels.shape[0]
+    _require_patch(R_gt, "R_gt", torch.float32, (n, 3, 3))
+    _require_patch(t_gt, "t_gt", torch.float32, (n, 3))
+    _require_counter(seed, step, object_offset)
+    missing = [k for k in _lib.TRAIN_CFG + ("max_kernel_size",) if k not in cfg]
+    if missing:
+        raise ScflowError(f"train_draw: cfg lacks {missing}")
+    mk = int(cfg["max_kernel_size"])
+    if not (1 <= mk <= 5 and 0 <= max_tries <= _lib.TRAIN_MAX_TRIES):
+        raise ScflowError(f"train_draw: max_kernel_size must be in [1, 5] and max_tries in "
+                          f"[0, {_lib.TRAIN_MAX_TRIES}], got {mk}, {max_tries}")
+    if c < 1 or p < 1:
+        raise ScflowError(f"train_draw: empty point table {list(points.shape)}")
+    host = (ctypes.c_float * len(_lib.TRAIN_CFG))(*[float(cfg[k]) for k in _lib.TRAIN_CFG])
+    dev = labels.device
+    new = lambda *s, dt=torch.float32: torch.empty(*s, device=dev, dtype=dt)  # noqa: E731
+    R, t, err, ratio, aug = new(n, 3, 3), new(n, 3), new(n, 3), new(n), new(n, 8)
+    ok, tries = new(n, dt=torch.uint8), new(n, dt=torch.int32)
+    if n:
+        _launch("scflow_train_draw", labels, _p(points), _p(counts), _p(labels), _p(diameters),
+                _p(R_gt), _p(t_gt), ctypes.cast(host, ctypes.c_void_p), _p(R), _p(t), _p(err),
+                _p(ok), _p(tries), _p(ratio), _p(aug), n, c, p, int(max_tries), mk, int(seed),
+                int(step), int(object_offset))
+    return R, t, err, ok, tries, ratio, aug
+
+
+def extract_patches_aug(frames: Tensor, frame_index: Tensor, geom: Tensor, valid: Tensor,
+                        aug: Tensor, size: int, seed: int, step: int, object_offset: int = 0,
+                        pad: int = 128, mean: Optional[Sequence[float]] = None,
+                        std: Optional[Sequence[float]] = None, to_rgb: bool = False,
+                        quantize: bool = True, direct: bool = False) -> Tensor:
+    """``extract_patches`` for [F, H, W, 3] uint8 BGR frames with the training pipeline's colour
+    stages on the crop, before the resize, in the same launch (scflow_train_patch_extract; DESIGN.md
+    §17): aug [N, 8] float32 = (a, b, c, sigma, ksize, stage mask, 0, 0) per object, as
+    ``train_draw`` returns it or as the caller writes it — HSV gains, the noise's sigma (its
+    normals come from (seed, step, object_offset + i, crop pixel)), the box blur's side (1, 3 or
+    5) and which stages run (``_lib.AUG_*``).  ``pad`` is an integer level.  A stage mask of 0 gives
+    ``extract_patches``' bits.  ``direct`` forces the route that stages nothing in LDS (the same
+    bits).  Runs on the current stream; N = 0 returns an empty tensor without a launch."""
+    _require_patch_size(size)
+    _require_patch(frames, "frames", torch.uint8, (None, None, None, 3))
+    f, h, w, _ = frames.shape
+    if f < 1 or h < 1 or w < 1:
+        raise ScflowError(f"frames must not be empty, got {list(frames.shape)}")
+    _require_patch(frame_index, "frame_index", torch.int32, (None,))
+    n = frame_index.shape[0]
+    _require_patch(geom, "geom", torch.int32, (n, 8))
+    _require_patch(valid, "valid", torch.uint8, (n,))
+    _require_patch(aug, "aug", torch.float32, (n, 8))
+    _require_counter(seed, step, object_offset)
+    if int(pad) != pad or not 0 <= pad <= 255:
+        raise ScflowError(f"pad must be an integer level in [0, 255], got {pad}")
+    stats = []
+    for name, v, dflt in (("mean", mean, 0.0), ("std", std, 1.0)):
+        v = [dflt] * 3 if v is None else [float(x) for x in v]
+        if len(v) != 3:
+            raise ScflowError(f"{name} must have 3 entries, got {len(v)}")
+        stats.append((ctypes.c_float * 3)(*v))
+    if any(s == 0.0 for s in stats[1]):
+        raise ScflowError("std must not be zero")
+    out = torch.empty(n, 3, size, size, device=frames.device, dtype=torch.float32)
+    if n:
+        flags = (_lib.PATCH_TO_RGB if to_rgb else 0) | (_lib.PATCH_QUANTIZE if quantize else 0) | \
+            (_lib.PATCH_AUG_DIRECT if direct else 0)
+        _launch("scflow_train_patch_extract", frames, _p(frames), _p(frame_index), _p(geom),
+                _p(valid), _p(aug), _p(out), n, f, h, w, int(size), int(pad),
+                ctypes.cast(stats[0], ctypes.c_void_p), ctypes.cast(stats[1], ctypes.c_void_p),
+                flags, int(seed), int(step), int(object_offset))
+    return out
+
+
 # ------------------------------------------------------------------------------- resampling
 def flow_downsample(flow: Tensor, out0: Chan, h: int, w: int, value_scale: float,
                     out1: Optional[Chan] = None, mask: Optional[Tensor] = None,

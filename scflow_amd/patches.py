@@ -67,8 +67,9 @@ def frames_to_patches(frames: Tensor, frame_index: Tensor, ref_rotations: Tensor
 
     ``points`` / ``counts``: the model point table (``point_table``).  ``size_ratio``: the crop's
     side over the box's, 1.1 at test time; a tensor [N] gives every object its own — the training
-    pipeline's ``U(1.0, 1.25)``, drawn by the caller.  An invalid object (behind the camera, off
-    the frame, …) gets a ``pad_val`` patch, the identity transform and ``internel_k = ori_k``.
+    pipeline's ``U(1.0, 1.25)``, which ``frames_to_train_patches`` draws on the device.  An invalid
+    object (behind the camera, off the frame, …) gets a ``pad_val`` patch, the identity transform
+    and ``internel_k = ori_k``.
     Everything runs on the current stream without a host synchronisation."""
     if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
         raise ScflowError("frames must be a [F, H, W, 3] uint8 tensor")
@@ -118,3 +119,67 @@ def extract_maps(maps: Tensor, frame_index: Tensor, geom: Tensor, valid: Optiona
     return ops.extract_patches(maps.contiguous(), _i32(frame_index), geom.contiguous(),
                                valid.contiguous().to(torch.uint8), size, pad=0.0, quantize=False,
                                nearest=mode == "nearest")
+
+
+# ------------------------------------------------------------------------------ training
+# configs/refine_models/scflow_ycbv_real.py:53-75: PoseJitter, Crop(size_range), RandomHSV,
+# RandomNoise, RandomSmooth (each colour transform with its default p = 1).  A limit below 0 is
+# off; a stage with p < 0 never runs.
+TRAIN_AUG = dict(angle_mean=0.0, angle_std=15.0, x_mean=0.0, y_mean=0.0, z_mean=0.0, x_std=15.0,
+                 y_std=15.0, z_std=50.0, angle_limit=45.0, translation_limit=200.0, add_limit=1.0,
+                 ratio_lo=1.0, ratio_hi=1.25, h_ratio=0.2, s_ratio=0.5, v_ratio=0.5,
+                 noise_ratio=0.1, max_kernel_size=5, p_hsv=1.0, p_noise=1.0, p_blur=1.0)
+
+
+def frames_to_train_patches(frames: Tensor, masks: Tensor, frame_index: Tensor,
+                            gt_rotations: Tensor, gt_translations: Tensor, ori_k: Tensor,
+                            labels: Tensor, points: Tensor, counts: Tensor, diameters: Tensor,
+                            seed: int, step: int, aug: Optional[dict] = None, size: int = 256,
+                            object_offset: int = 0, max_tries: int = 32, pad_val: int = 128,
+                            img_norm_cfg: Optional[dict] = None, to_rgb: bool = True
+                            ) -> Dict[str, Tensor]:
+    """Decoded frames [F, H, W, 3] uint8 (BGR) and their instance masks [F, H, W] uint8 plus N
+    annotated objects — frame_index [N], GT poses, labels, ori_k per object or per frame — to the
+    real-image half of a training batch, as the reference's training pipeline formats it
+    (configs/refine_models/scflow_ycbv_real.py:50-93) but in four launches for all objects:
+    ``ops.train_draw`` (jittered pose, crop ratio, colour parameters), ``ops.patch_boxes`` at the
+    jittered pose with the drawn ratio, ``ops.extract_patches_aug`` and ``extract_maps`` of the
+    masks (nearest).  ``aug``: ``TRAIN_AUG`` with any key replaced; ``diameters`` [C] float32.
+
+    Returns ``real_images`` [N, 3, size, size], ``gt_masks`` [N, size, size] (0 / 1),
+    ``internel_k``, ``transform_matrix``, ``ref_rotation`` / ``ref_translation`` (jittered),
+    ``gt_rotation`` / ``gt_translation``, ``label`` (int64), ``valid`` [N] bool (the crop is one
+    AND a jitter try was accepted), ``init_add_error`` / ``init_rot_error`` / ``init_trans_error``
+    [N], ``tries``, ``ratio``, ``aug`` [N, 8] and ``geom`` [N, 8].  Every random number is a
+    function of (seed, step, object_offset + i): a data-parallel rank passes the
+    number of objects before its own as ``object_offset``.  An invalid object gets a ``pad_val``
+    patch.  Everything runs on the current stream without a host synchronisation."""
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
+        raise ScflowError("frames must be a [F, H, W, 3] uint8 tensor")
+    f, h, w, _ = frames.shape
+    n = labels.shape[0]
+    cfg = dict(TRAIN_AUG)
+    cfg.update(aug or {})
+    norm = dict(IMG_NORM_CFG if img_norm_cfg is None else img_norm_cfg)
+    to_rgb = bool(norm.get("to_rgb", to_rgb))
+    fidx, lab = _i32(frame_index), _i32(labels)
+    per_frame = ori_k.shape[0] != n
+    if per_frame and ori_k.shape[0] != f:
+        raise ScflowError(f"ori_k must be [{n}, 3, 3] or [{f}, 3, 3], got {list(ori_k.shape)}")
+    points, counts = points.contiguous().float(), _i32(counts)
+    R_gt, t_gt = gt_rotations.contiguous().float(), gt_translations.contiguous().float()
+    R, t, err, ok, tries, ratio, rows = ops.train_draw(
+        points, counts, lab, diameters.contiguous().float(), R_gt, t_gt, cfg, seed, step,
+        object_offset, max_tries)
+    _, geom, T, k, valid = ops.patch_boxes(points, counts, lab, R, t, ori_k.contiguous().float(),
+                                           ratio, h, w, size, frame_index=fidx, num_frames=f,
+                                           k_per_frame=per_frame)
+    images = ops.extract_patches_aug(frames.contiguous(), fidx, geom, valid, rows, size, seed, step,
+                                     object_offset, pad=pad_val, mean=norm["mean"],
+                                     std=norm["std"], to_rgb=to_rgb)
+    gt_masks = extract_maps(masks, fidx, geom, valid, size, mode="nearest")[:, 0]
+    return dict(real_images=images, gt_masks=(gt_masks > 0).float(), internel_k=k,
+                transform_matrix=T, ref_rotation=R, ref_translation=t, gt_rotation=R_gt,
+                gt_translation=t_gt, label=labels.long(), valid=(valid != 0) & (ok != 0),
+                init_add_error=err[:, 0], init_rot_error=err[:, 1], init_trans_error=err[:, 2],
+                tries=tries, ratio=ratio, aug=rows, geom=geom)

@@ -242,6 +242,40 @@ class SCFlowRefiner(_RefinerBase):
         t = torch.where(valid.view(-1, 1), t, ref_translations)
         return R, t, valid, data
 
+    def train_batch_from_frames(self, frames: Tensor, masks: Tensor, frame_index: Tensor,
+                                gt_rotations: Tensor, gt_translations: Tensor, ori_k: Tensor,
+                                labels: Tensor, diameters: Tensor, seed: int, step: int,
+                                aug: Optional[dict] = None, object_offset: int = 0,
+                                drop_invalid: bool = False, points=None) -> Dict[str, Tensor]:
+        """Decoded frames [F, H, W, 3] uint8, instance masks [F, H, W] uint8 and N annotated
+        objects → the batch ``train.step.TrainStep`` takes: ``patches.frames_to_train_patches``
+        (pose jitter, random crop, colour augmentation, all on the device, at the renderer's image
+        size) plus ``render_images`` and ``depth`` rendered at the jittered pose under
+        ``internel_k`` — format_data_train_sup (base_refiner.py:154-225).  ``diameters`` [C]
+        float32; ``points`` as in ``refine_frames``.  The default keeps all N objects and
+        synchronises nothing (``valid`` says which are usable); ``drop_invalid=True`` compacts
+        every per-object entry by ``valid``, which costs ONE host synchronisation (the number of
+        valid objects sizes the result)."""
+        from . import patches
+        if self.renderer is None:
+            raise RuntimeError("SCFlowRefiner was built without a renderer config")
+        if points is None:
+            if getattr(self, "_point_table", None) is None or \
+                    self._point_table[0].device != self.renderer._device:
+                self._point_table = patches.point_table(self.renderer)
+            points = self._point_table
+        data = patches.frames_to_train_patches(
+            frames, masks, frame_index, gt_rotations, gt_translations, ori_k, labels, points[0],
+            points[1], diameters, seed, step, aug=aug, size=self.renderer.image_size[0],
+            object_offset=object_offset)
+        if drop_invalid:
+            keep = data["valid"].nonzero()[:, 0]  # the synchronisation
+            data = {k: v[keep] for k, v in data.items()}
+        img, depth, _ = self.render(data["ref_rotation"], data["ref_translation"],
+                                    data["internel_k"], data["label"])
+        data["render_images"], data["depth"] = img, depth
+        return data
+
     # ------------------------------------------------------------------ reference API
     def get_pose(self, render_images: Tensor, real_images: Tensor, ref_rotation: Tensor,
                  ref_translation: Tensor, depth: Tensor, internel_k: Tensor, label: Tensor,

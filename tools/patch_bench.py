@@ -16,6 +16,16 @@ between two device events around `steps` calls, after a warm-up of every shape:
 
 Prints the medians, the ratio, the bytes the extract launch has to move (from the shapes) and one
 JSON line.  No threshold: the parent has no such path.
+
+`--train` times the training front end instead, alternating in the same way:
+
+* `plain`: the two launches above at the GT pose (what inference runs);
+* `train`: `ops.train_draw` + `ops.patch_boxes` at the jittered pose with the drawn ratio +
+  `ops.extract_patches_aug` with the config's augmentation (`patches.TRAIN_AUG`: every stage on);
+* `train_direct`: the same with the extract's direct route forced (every tap computes its own
+  window; the same bits);
+* `train_mask0`: the same three launches with every stage probability below 0 (stage mask 0: the
+  extract does `plain`'s work).
 """
 import argparse
 import json
@@ -50,6 +60,68 @@ def scene(a, dev):
                 ratio=torch.full((a.objects,), 1.1, device=dev))
 
 
+def train_bench(a, s):
+    """The `--train` mode: see the module docstring."""
+    from scflow_amd import ops, patches
+    dev = s["frames"].device
+    norm = dict(mean=[0.0] * 3, std=[255.0] * 3, to_rgb=True)
+    diam = torch.full((21,), 180.0, device=dev)
+    off = dict(patches.TRAIN_AUG, p_hsv=-1.0, p_noise=-1.0, p_blur=-1.0)
+    seed = 2024
+
+    def boxes(R, t, ratio):
+        return ops.patch_boxes(s["points"], s["counts"], s["labels"], R, t, s["K"], ratio, a.height,
+                               a.width, a.size, frame_index=s["fidx"], num_frames=a.frames,
+                               k_per_frame=True)
+
+    def plain():
+        _, geom, _, _, valid = boxes(s["R"], s["t"], s["ratio"])
+        return ops.extract_patches(s["frames"], s["fidx"], geom, valid, a.size, pad=128.0, **norm)
+
+    def train(cfg=patches.TRAIN_AUG, direct=False, step=0):
+        R, t, _, ok, tries, ratio, rows = ops.train_draw(s["points"], s["counts"], s["labels"], diam,
+                                                         s["R"], s["t"], cfg, seed, step)
+        _, geom, _, _, valid = boxes(R, t, ratio)
+        img = ops.extract_patches_aug(s["frames"], s["fidx"], geom, valid, rows, a.size, seed, step,
+                                      direct=direct, **norm)
+        return img, ok, tries, rows, geom, valid
+
+    run = {"plain": plain, "train": train, "train_direct": lambda: train(direct=True),
+           "train_mask0": lambda: train(cfg=off)}
+    outs = {}
+    for k, f in run.items():
+        for _ in range(3):
+            outs[k] = f()
+    torch.cuda.synchronize()
+    times = {k: [] for k in run}
+    for _ in range(a.rounds):
+        for k, f in run.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.steps):
+                f()
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1) / a.steps)
+    img, ok, tries, rows, geom, valid = outs["train"]
+    g = geom.cpu().numpy()
+    cw = (g[:, 2] - g[:, 0] + 1)[valid.cpu().numpy() != 0]
+    res = dict(mode="train", frames=a.frames, height=a.height, width=a.width, objects=a.objects,
+               size=a.size, rounds=a.rounds, steps=a.steps, valid=int(valid.sum()),
+               accepted=int(ok.sum()), max_tries=int(tries.max()), crop_min=int(cw.min()),
+               crop_max=int(cw.max()), ksizes=sorted(set(rows[:, 4].tolist())),
+               same_bits_tiled_direct=bool(torch.equal(img, outs["train_direct"][0])))
+    for k, v in times.items():
+        res[k] = dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v))
+        print(f"{k}: median {res[k]['median_ms']:.4f} ms/call (min {min(v):.4f}, max {max(v):.4f})")
+    res["train_over_plain"] = res["train"]["median_ms"] / res["plain"]["median_ms"]
+    print(f"F={a.frames} frames of {a.height}×{a.width}, N={a.objects} objects ({res['valid']} valid, "
+          f"{res['accepted']} jittered within {res['max_tries']} tries, crops {res['crop_min']}-"
+          f"{res['crop_max']} px), S={a.size}: train / plain = {res['train_over_plain']:.2f}×; tiled "
+          f"and direct routes {'equal' if res['same_bits_tiled_direct'] else 'DIFFER'} bit for bit")
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4)
@@ -60,6 +132,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--train", action="store_true", help="time the training front end (§17)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("patch_bench needs a GPU: a CPU run says nothing about these timings")
@@ -67,6 +140,9 @@ def main():
     from tests.patch_restatement import torch_patches
     dev = torch.device("cuda")
     s = scene(a, dev)
+    if a.train:
+        write_json(a, train_bench(a, s))
+        return
     norm = dict(pad=128.0, mean=[0.0] * 3, std=[255.0] * 3, to_rgb=True)
 
     def boxes():
@@ -131,6 +207,10 @@ def main():
           f"{bytes_in / 1e6:.2f} MB and writes {bytes_out / 1e6:.2f} MB; staged and direct routes "
           f"{'equal' if res['same_bits_staged_direct'] else 'DIFFER'} bit for bit; max difference "
           f"from the torch loop {res['max_diff_vs_torch_levels']:.3f} levels")
+    write_json(a, res)
+
+
+def write_json(a, res):
     line = json.dumps(res)
     print(line)
     if a.json:
