@@ -928,7 +928,25 @@ int scflow_patch_staged(int cw, int channels, int dtype, int size);
  *   crop's edges, (2·Σ + k²) div (2·k²)).  A stage mask of 0 gives scflow_patch_extract's bits.
  *   The augmented crop window a tile of output pixels reads is staged once in LDS where it fits;
  *   otherwise, and with SCFLOW_PATCH_AUG_DIRECT, every tap computes its own window.  Both routes
- *   give the same bits, and neither depends on size or geom[4..8) for the noise a crop pixel gets. */
+ *   give the same bits, and neither depends on size or geom[4..8) for the noise a crop pixel gets.
+ * scflow_train_patch_extract_bg: the same with the reference's RandomBackground
+ *   (color_transform.py:177-244) between the crop and the stages.  pool [num_slots]
+ *   [pool_height][pool_width][3] uint8 BGR; pool_sizes (may be NULL: every slot used in full)
+ *   [num_slots][2] = the used (height, width) of a slot, top-left aligned, 1 ≤ h ≤ pool_height, 1 ≤ w
+ *   ≤ pool_width; masks [num_frames][height][width] uint8, foreground where != 0.  Object i takes a
+ *   background where u[0,1) of word 0 of (0, object, SCFLOW_RNG_BACKGROUND) ≤ p, from slot
+ *   min(int(u(word 1)·num_slots), num_slots − 1); choice (may be NULL) [n] replaces the draw: −1
+ *   none, 0 .. num_slots−1 that slot, anything else none.  chosen[i] = the slot, −1 for none (also
+ *   where the slot's pool_sizes row is not a used size).  Under slot b of used size h_b × w_b,
+ *   crop pixel (x, y) keeps the frame's level where it lies inside the frame and masks[frame][y1+y]
+ *   [x1+x] != 0; every other crop pixel, pad pixels included, is the level of the slot's used
+ *   region resampled to the crop's cw × ch as scflow_patch_extract resamples (source coordinates
+ *   of x on w_b → cw and of y on h_b → ch, (1−fx)·a + fx·b per row, then the row blend, rintf).
+ *   The stages then run on the composite: noise keys and the blur's fold at the crop's edges are
+ *   unchanged.  An invalid object draws (chosen is set) but stays a pad patch.  A background with
+ *   stage mask 0 is staged like any other window.  p outside [0, 1] (a NaN too), num_slots ≤ 0,
+ *   NULL masks / pool / chosen: SCFLOW_EINVAL; pool_height or pool_width above 2^20:
+ *   SCFLOW_EUNSUPPORTED.  Without a background an object's bits are scflow_train_patch_extract's. */
 #define SCFLOW_TRAIN_CFG_LEN 20
 #define SCFLOW_TRAIN_ANGLE_MEAN 0
 #define SCFLOW_TRAIN_ANGLE_STD 1
@@ -946,6 +964,7 @@ int scflow_patch_staged(int cw, int channels, int dtype, int size);
 #define SCFLOW_RNG_CROP 0
 #define SCFLOW_RNG_COLOUR 1
 #define SCFLOW_RNG_NOISE 2
+#define SCFLOW_RNG_BACKGROUND 3
 #define SCFLOW_RNG_JITTER 16 /* + try */
 #define SCFLOW_AUG_HSV 1
 #define SCFLOW_AUG_NOISE 2
@@ -964,6 +983,15 @@ int scflow_train_patch_extract(const void* frames, const int* frame_index, const
                              const float* mean, const float* std, int flags,
                              unsigned long long seed, unsigned long long step,
                              unsigned int object_offset, void* stream);
+int scflow_train_patch_extract_bg(const void* frames, const int* frame_index, const int* geom,
+                                  const unsigned char* valid, const float* aug, float* out,
+                                  const unsigned char* masks, const unsigned char* pool,
+                                  const int* pool_sizes, const int* choice, int* chosen, int n,
+                                  int num_frames, int height, int width, int size, int pad,
+                                  const float* mean, const float* std, int flags, int num_slots,
+                                  int pool_height, int pool_width, float p,
+                                  unsigned long long seed, unsigned long long step,
+                                  unsigned int object_offset, void* stream);
 
 /* Profiling helper (bench.py roofline timing; no reference equivalent): a one-thread kernel
  * that stores the GPU's constant-rate wall clock (s_memrealtime) into stamps[idx].  Enqueued on

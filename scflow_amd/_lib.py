@@ -31,6 +31,7 @@ PATCH_TO_RGB, PATCH_QUANTIZE, PATCH_NEAREST = 1, 2, 4  # scflow_patch_extract's 
 PATCH_AUG_DIRECT = 8  # scflow_train_patch_extract's flag SCFLOW_PATCH_AUG_DIRECT
 AUG_HSV, AUG_NOISE, AUG_BLUR = 1, 2, 4  # SCFLOW_AUG_*: the stage mask in aug[:, 5]
 RNG_CROP, RNG_COLOUR, RNG_NOISE, RNG_JITTER = 0, 1, 2, 16  # SCFLOW_RNG_*
+RNG_BACKGROUND = 3  # SCFLOW_RNG_BACKGROUND: scflow_train_patch_extract_bg's draw
 TRAIN_MAX_TRIES = 224  # SCFLOW_TRAIN_MAX_TRIES
 # SCFLOW_TRAIN_*: where scflow_train_draw's cfg holds what
 TRAIN_CFG = ("angle_mean", "angle_std", "x_mean", "y_mean", "z_mean", "x_std", "y_std", "z_std",
@@ -280,6 +281,9 @@ SIGNATURES = {
                           [ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, c_vp]),
     "scflow_train_patch_extract": (c_int, [c_vp] * 6 + [c_int] * 6 + [c_vp, c_vp, c_int,
                                  ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, c_vp]),
+    "scflow_train_patch_extract_bg": (c_int, [c_vp] * 11 + [c_int] * 6 + [c_vp, c_vp] + [c_int] * 4 +
+                                      [c_float, ctypes.c_ulonglong, ctypes.c_ulonglong,
+                                       ctypes.c_uint, c_vp]),
     "scflow_timestamp": (c_int, [c_vp, c_int, c_vp]),
     "scflow_wallclock_khz": (c_ll, []),
 }

@@ -14,6 +14,10 @@
 //                             window from there.  Where that window exceeds the LDS budget, and for objects
 //                             whose stage mask is 0, each tap computes its own window from the
 //                             frame (the direct route).  Both routes sum the same integers.
+//                             The <true> instantiation (scflow_train_patch_extract_bg, DESIGN.md
+//                             §18) draws a background slot per object and replaces every crop
+//                             pixel that the instance mask calls background, before the stages;
+//                             <false> is the kernel without any of that.
 //
 // Every fp32 expression here is part of the contract (tests/train_patch_restatement.py restates it
 // operation by operation), so contraction into FMAs is off for the whole file.
@@ -268,19 +272,80 @@ struct PatchAugArgs {
   Rng rng;
 };
 
+// RandomBackground (color_transform.py:177-244): what the <true> instantiation takes on top
+struct BgArgs {
+  const unsigned char* masks;  // [F][H][W], foreground where != 0
+  const unsigned char* pool;   // [B][Hb][Wb][3] BGR
+  const int* sizes;            // [B][2] used (height, width), top-left aligned; NULL: whole slots
+  const int* choice;           // [n] −1 none, 0 .. B−1 that slot; NULL: drawn
+  int* chosen;                 // [n] the slot applied, −1 for none
+  int B, Hb, Wb;
+  float p;
+};
+
 // what a workgroup knows of its object
 struct Crop {
   const unsigned char* frame;
   int x1, y1, cw, ch, H, W, pad, mask;
   float ga, gb, gc, sigma;
   uint32_t obj;
+  // the background's used region and the frame's mask; bg == nullptr: no background
+  const unsigned char* bg;
+  const unsigned char* fmask;
+  int bw, bh, bstride;
 };
 
-// crop pixel (x, y), 0 ≤ x < cw, 0 ≤ y < ch, after HSV and noise
+// linear_coord for a background axis: (2o + 1)·n reaches 2^35 at the accepted limits (a crop side
+// of PX_MAX_CROP on a slot side of PX_MAX_ORIGIN), so the wide case divides in 64 bits.  Which
+// case runs is the same for a whole object.
+__device__ inline void bg_coord(int o, int n, int no, int& i0, float& f) {
+  if ((long long)(2 * no) * n < (1ll << 31)) return linear_coord(o, n, no, i0, f);
+  const long long num = (long long)(2 * o + 1) * n - no, den = 2 * no;
+  if (num < 0) {
+    i0 = 0, f = 0.f;
+    return;
+  }
+  const long long q = num / den;
+  i0 = (int)q;
+  f = (float)(num - q * den) / (float)den;
+  if (i0 >= n - 1) i0 = n - 1, f = 0.f;
+}
+
+// crop pixel (x, y) of the background resized to the crop's cw × ch: the resample of DESIGN.md §15
+// (cv2's INTER_LINEAR, aspect ratio not kept) on the used region, rounded to a level
+__device__ __forceinline__ Px bg_pixel(const Crop& c, int x, int y) {
+  int xa, ya;
+  float fx, fy;
+  bg_coord(x, c.bw, c.cw, xa, fx);
+  bg_coord(y, c.bh, c.ch, ya, fy);
+  const int xb = xa + 1 < c.bw - 1 ? xa + 1 : c.bw - 1, yb = ya + 1 < c.bh - 1 ? ya + 1 : c.bh - 1;
+  const unsigned char* r0 = c.bg + (size_t)ya * c.bstride;
+  const unsigned char* r1 = c.bg + (size_t)yb * c.bstride;
+  const float gx = 1.f - fx, gy = 1.f - fy;
+  int v[3];
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const float up = gx * (float)r0[3 * xa + ch] + fx * (float)r0[3 * xb + ch];
+    const float dn = gx * (float)r1[3 * xa + ch] + fx * (float)r1[3 * xb + ch];
+    v[ch] = (int)rintf(gy * up + fy * dn);
+  }
+  return Px{v[0], v[1], v[2]};
+}
+
+// crop pixel (x, y), 0 ≤ x < cw, 0 ≤ y < ch, after HSV and noise.  BG: under a background, a
+// pixel outside the frame or with a zero mask byte is the background's instead (a select)
+template <bool BG>
 __device__ __forceinline__ Px aug_pixel(const Crop& c, const Rng& rng, int x, int y) {
   const int fx = c.x1 + x, fy = c.y1 + y;
   Px p{c.pad, c.pad, c.pad};
-  if (fx >= 0 && fx < c.W && fy >= 0 && fy < c.H) {
+  bool in = fx >= 0 && fx < c.W && fy >= 0 && fy < c.H;
+  if constexpr (BG) {
+    if (c.bg) {
+      in = in && c.fmask[(size_t)fy * c.W + fx] != 0;
+      if (!in) p = bg_pixel(c, x, y);
+    }
+  }
+  if (in) {
     const unsigned char* s = c.frame + ((size_t)fy * c.W + fx) * 3;
     p.b = s[0], p.g = s[1], p.r = s[2];
   }
@@ -320,7 +385,8 @@ __host__ __device__ inline int pa_rows(int S) {
   return r > S ? S : r;
 }
 
-__global__ __launch_bounds__(PX_THREADS) void patch_extract_aug_kernel(PatchAugArgs a) {
+template <bool BG>
+__global__ __launch_bounds__(PX_THREADS) void patch_extract_aug_kernel(PatchAugArgs a, BgArgs g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char win[];  // PA_LDS_BYTES
   const int S = a.S, rows = pa_rows(S), cols = pa_cols(S);
   const int bands = (S + rows - 1) / rows, ctiles = (S + cols - 1) / cols;
@@ -350,6 +416,32 @@ __global__ __launch_bounds__(PX_THREADS) void patch_extract_aug_kernel(PatchAugA
   int k = 1;
   if (c.mask & SCFLOW_AUG_BLUR) k = row[4] == 3.f ? 3 : (row[4] == 5.f ? 5 : 1);
   const int halo = k >> 1;
+  c.bg = nullptr;
+  if constexpr (BG) {
+    // every workgroup of the object derives the same slot from the counter; the first stores it
+    int slot = -1;
+    if (g.choice) {
+      const int v = g.choice[obj];
+      slot = v >= 0 && v < g.B ? v : -1;
+    } else {
+      const Words q = a.rng.draw(0, c.obj, SCFLOW_RNG_BACKGROUND);
+      if (u01(q.w[0]) <= g.p) {
+        slot = (int)(u01(q.w[1]) * (float)g.B);
+        slot = slot < g.B - 1 ? slot : g.B - 1;
+      }
+    }
+    if (slot >= 0) {
+      c.bh = g.sizes ? g.sizes[2 * slot] : g.Hb, c.bw = g.sizes ? g.sizes[2 * slot + 1] : g.Wb;
+      // a used size that is none refuses the background instead of reading past the slot
+      if (c.bh < 1 || c.bh > g.Hb || c.bw < 1 || c.bw > g.Wb) slot = -1;
+    }
+    if (tile == 0 && tid == 0) g.chosen[obj] = slot;
+    if (ok && slot >= 0) {
+      c.bstride = 3 * g.Wb;
+      c.bg = g.pool + (size_t)slot * g.Hb * c.bstride;
+      c.fmask = g.masks + (size_t)fi * a.H * a.W;
+    }
+  }
 
   // the tile's rows and columns of the resized crop and the crop window their taps read
   int oya = row0 - top, oyb = row0 + nrows - 1 - top;
@@ -371,12 +463,13 @@ __global__ __launch_bounds__(PX_THREADS) void patch_extract_aug_kernel(PatchAugA
   const int wx0 = xlo - halo, wcols = xhi - xlo + 1 + 2 * halo;
   const int wstride = 3 * wcols;
   // block-uniform; a stage mask of 0 leaves nothing to share between taps but the frame itself
-  const bool tiled = any && !a.direct && c.mask != 0 &&
+  // (under a background: its resampled pixels, so such a window is staged too)
+  const bool tiled = any && !a.direct && (c.mask != 0 || (BG && c.bg)) &&
                      (long long)wrows * wstride <= (long long)PA_LDS_BYTES;
   if (tiled) {
     for (int idx = tid; idx < wrows * wcols; idx += PX_THREADS) {
       const int r = idx / wcols, col = idx - r * wcols;
-      const Px p = aug_pixel(c, a.rng, fold101(wx0 + col, c.cw), fold101(wy0 + r, c.ch));
+      const Px p = aug_pixel<BG>(c, a.rng, fold101(wx0 + col, c.cw), fold101(wy0 + r, c.ch));
       unsigned char* d = win + r * wstride + 3 * col;
       d[0] = (unsigned char)p.b, d[1] = (unsigned char)p.g, d[2] = (unsigned char)p.r;
     }
@@ -387,7 +480,7 @@ __global__ __launch_bounds__(PX_THREADS) void patch_extract_aug_kernel(PatchAugA
     return Px{s[0], s[1], s[2]};
   };
   const auto from_frame = [&](int xu, int yu) {
-    return aug_pixel(c, a.rng, fold101(xu, c.cw), fold101(yu, c.ch));
+    return aug_pixel<BG>(c, a.rng, fold101(xu, c.cw), fold101(yu, c.ch));
   };
 
   const int quads = ncols / 4;
@@ -482,19 +575,25 @@ SCFLOW_API int scflow_train_draw(const float* points, const int* counts, const i
   return scflow_launch_status();
 }
 
-SCFLOW_API int scflow_train_patch_extract(const void* frames, const int* frame_index, const int* geom,
-                                        const unsigned char* valid, const float* aug, float* out,
-                                        int n, int num_frames, int height, int width, int size,
-                                        int pad, const float* mean, const float* std, int flags,
-                                        unsigned long long seed, unsigned long long step,
-                                        unsigned int object_offset, void* stream) {
+// the checks and the launch both extract entries share; bg == nullptr: the kernel without a background
+static int train_extract(const void* frames, const int* frame_index, const int* geom,
+                         const unsigned char* valid, const float* aug, float* out, int n,
+                         int num_frames, int height, int width, int size, int pad, const float* mean,
+                         const float* std, int flags, unsigned long long seed,
+                         unsigned long long step, unsigned int object_offset, const BgArgs* bg,
+                         void* stream) {
   if (!frames || !frame_index || !geom || !valid || !aug || !out || n <= 0 || num_frames <= 0 ||
       height <= 0 || width <= 0 || pad < 0 || pad > 255 ||
       (flags & ~(SCFLOW_PATCH_TO_RGB | SCFLOW_PATCH_QUANTIZE | SCFLOW_PATCH_AUG_DIRECT)))
     return SCFLOW_EINVAL;
+  // !(p >= 0 && p <= 1) refuses a NaN too
+  if (bg && (!bg->masks || !bg->pool || !bg->chosen || bg->B <= 0 || bg->Hb <= 0 || bg->Wb <= 0 ||
+             !(bg->p >= 0.f && bg->p <= 1.f)))
+    return SCFLOW_EINVAL;
   if (size < 4 || size > 4096 || size % 4 || height > PX_MAX_ORIGIN || width > PX_MAX_ORIGIN ||
       (step >> 56))
     return SCFLOW_EUNSUPPORTED;
+  if (bg && (bg->Hb > PX_MAX_ORIGIN || bg->Wb > PX_MAX_ORIGIN)) return SCFLOW_EUNSUPPORTED;
   const int rows = pa_rows(size), cols = pa_cols(size);
   const long long tiles = (long long)((size + rows - 1) / rows) * ((size + cols - 1) / cols);
   if (n * tiles >= (1ll << 31)) return SCFLOW_EUNSUPPORTED;
@@ -507,7 +606,34 @@ SCFLOW_API int scflow_train_patch_extract(const void* frames, const int* frame_i
   a.to_rgb = (flags & SCFLOW_PATCH_TO_RGB) != 0, a.quantize = (flags & SCFLOW_PATCH_QUANTIZE) != 0;
   a.direct = (flags & SCFLOW_PATCH_AUG_DIRECT) != 0;
   a.object_offset = object_offset, a.rng = Rng{seed, step};
-  hipLaunchKernelGGL(patch_extract_aug_kernel, dim3((unsigned)(n * tiles)), dim3(PX_THREADS), PA_LDS_BYTES,
-                     (hipStream_t)stream, a);
+  const dim3 grid((unsigned)(n * tiles));
+  if (bg)
+    hipLaunchKernelGGL(patch_extract_aug_kernel<true>, grid, dim3(PX_THREADS), PA_LDS_BYTES,
+                       (hipStream_t)stream, a, *bg);
+  else
+    hipLaunchKernelGGL(patch_extract_aug_kernel<false>, grid, dim3(PX_THREADS), PA_LDS_BYTES,
+                       (hipStream_t)stream, a, BgArgs{});
   return scflow_launch_status();
+}
+
+SCFLOW_API int scflow_train_patch_extract(const void* frames, const int* frame_index, const int* geom,
+                                        const unsigned char* valid, const float* aug, float* out,
+                                        int n, int num_frames, int height, int width, int size,
+                                        int pad, const float* mean, const float* std, int flags,
+                                        unsigned long long seed, unsigned long long step,
+                                        unsigned int object_offset, void* stream) {
+  return train_extract(frames, frame_index, geom, valid, aug, out, n, num_frames, height, width,
+                       size, pad, mean, std, flags, seed, step, object_offset, nullptr, stream);
+}
+
+SCFLOW_API int scflow_train_patch_extract_bg(
+    const void* frames, const int* frame_index, const int* geom, const unsigned char* valid,
+    const float* aug, float* out, const unsigned char* masks, const unsigned char* pool,
+    const int* pool_sizes, const int* choice, int* chosen, int n, int num_frames, int height,
+    int width, int size, int pad, const float* mean, const float* std, int flags, int num_slots,
+    int pool_height, int pool_width, float p, unsigned long long seed, unsigned long long step,
+    unsigned int object_offset, void* stream) {
+  const BgArgs bg{masks, pool, pool_sizes, choice, chosen, num_slots, pool_height, pool_width, p};
+  return train_extract(frames, frame_index, geom, valid, aug, out, n, num_frames, height, width,
+                       size, pad, mean, std, flags, seed, step, object_offset, &bg, stream);
 }

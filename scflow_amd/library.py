@@ -27,6 +27,8 @@ op                             reference                                        
                                color_transform.py:78-134
 ``scflow::patch_extract_aug``  ``extract_patches`` with RandomHSV / RandomNoise /       no
                                RandomSmooth on the crop, in the same launch
+``scflow::patch_extract_aug_   the same with RandomBackground before the stages,       no
+bg``                           color_transform.py:177-244
 =============================  =====================================================  =========
 
 The backward formulas are ops of their own (``scflow::corr_pyramid_backward``,
@@ -456,3 +458,32 @@ def patch_extract_aug(frames: Tensor, frame_index: Tensor, geom: Tensor, valid: 
 def _(frames, frame_index, geom, valid, aug, size, seed, step, object_offset, pad, mean, std, to_rgb,
       quantize):
     return frames.new_empty(frame_index.shape[0], 3, size, size, dtype=torch.float32)
+
+
+@torch.library.custom_op("scflow::patch_extract_aug_bg", mutates_args=(), device_types="cuda")
+def patch_extract_aug_bg(frames: Tensor, masks: Tensor, frame_index: Tensor, geom: Tensor,
+                         valid: Tensor, aug: Tensor, backgrounds: Tensor,
+                         background_sizes: Optional[Tensor], background_index: Optional[Tensor],
+                         p: float, size: int, seed: int, step: int, object_offset: int, pad: int,
+                         mean: Optional[List[float]], std: Optional[List[float]], to_rgb: bool,
+                         quantize: bool) -> Tuple[Tensor, Tensor]:
+    """``patch_extract_aug`` with RandomBackground between the crop and the colour stages, in the
+    same launch (``ops.extract_patches_aug_bg``; replaces cv2.resize + a masked copy per object on
+    the host, color_transform.py:177-244): → (patches [N, 3, size, size] float32, the slot every
+    object got [N] int32, −1 for none).  Not differentiable."""
+    i32 = torch.int32
+    sizes = None if background_sizes is None else background_sizes.contiguous().to(i32)
+    index = None if background_index is None else background_index.contiguous().to(i32)
+    return ops.extract_patches_aug_bg(frames.contiguous(), masks.contiguous(),
+                                      frame_index.contiguous().to(i32), geom.contiguous(),
+                                      valid.contiguous(), aug.contiguous().float(),
+                                      backgrounds.contiguous(), size, seed, step, object_offset, p,
+                                      sizes, index, pad, mean, std, to_rgb, quantize)
+
+
+@patch_extract_aug_bg.register_fake
+def _(frames, masks, frame_index, geom, valid, aug, backgrounds, background_sizes, background_index,
+      p, size, seed, step, object_offset, pad, mean, std, to_rgb, quantize):
+    n = frame_index.shape[0]
+    return (frames.new_empty(n, 3, size, size, dtype=torch.float32),
+            frames.new_empty(n, dtype=torch.int32))

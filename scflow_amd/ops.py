@@ -965,19 +965,10 @@ def train_draw(points: Tensor, counts: Tensor, labels: Tensor, diameters: Tensor
     return R, t, err, ok, tries, ratio, aug
 
 
-def extract_patches_aug(frames: Tensor, frame_index: Tensor, geom: Tensor, valid: Tensor,
-                        aug: Tensor, size: int, seed: int, step: int, object_offset: int = 0,
-                        pad: int = 128, mean: Optional[Sequence[float]] = None,
-                        std: Optional[Sequence[float]] = None, to_rgb: bool = False,
-                        quantize: bool = True, direct: bool = False) -> Tensor:
-    """``extract_patches`` for [F, H, W, 3] uint8 BGR frames with the training pipeline's colour
-    stages on the crop, before the resize, in the same launch (scflow_train_patch_extract; DESIGN.md
-    §17): aug [N, 8] float32 = (a, b, c, sigma, ksize, stage mask, 0, 0) per object, as
-    ``train_draw`` returns it or as the caller writes it — HSV gains, the noise's sigma (its
-    normals come from (seed, step, object_offset + i, crop pixel)), the box blur's side (1, 3 or
-    5) and which stages run (``_lib.AUG_*``).  ``pad`` is an integer level.  A stage mask of 0 gives
-    ``extract_patches``' bits.  ``direct`` forces the route that stages nothing in LDS (the same
-    bits).  Runs on the current stream; N = 0 returns an empty tensor without a launch."""
+def _require_aug_extract(frames, frame_index, geom, valid, aug, size, seed, step, object_offset,
+                         pad, mean, std):
+    """The argument checks ``extract_patches_aug`` and ``extract_patches_aug_bg`` share → (n, f, h,
+    w, (mean, std) as host arrays)."""
     _require_patch_size(size)
     _require_patch(frames, "frames", torch.uint8, (None, None, None, 3))
     f, h, w, _ = frames.shape
@@ -999,6 +990,24 @@ def extract_patches_aug(frames: Tensor, frame_index: Tensor, geom: Tensor, valid
         stats.append((ctypes.c_float * 3)(*v))
     if any(s == 0.0 for s in stats[1]):
         raise ScflowError("std must not be zero")
+    return n, f, h, w, stats
+
+
+def extract_patches_aug(frames: Tensor, frame_index: Tensor, geom: Tensor, valid: Tensor,
+                        aug: Tensor, size: int, seed: int, step: int, object_offset: int = 0,
+                        pad: int = 128, mean: Optional[Sequence[float]] = None,
+                        std: Optional[Sequence[float]] = None, to_rgb: bool = False,
+                        quantize: bool = True, direct: bool = False) -> Tensor:
+    """``extract_patches`` for [F, H, W, 3] uint8 BGR frames with the training pipeline's colour
+    stages on the crop, before the resize, in the same launch (scflow_train_patch_extract; DESIGN.md
+    §17): aug [N, 8] float32 = (a, b, c, sigma, ksize, stage mask, 0, 0) per object, as
+    ``train_draw`` returns it or as the caller writes it — HSV gains, the noise's sigma (its
+    normals come from (seed, step, object_offset + i, crop pixel)), the box blur's side (1, 3 or
+    5) and which stages run (``_lib.AUG_*``).  ``pad`` is an integer level.  A stage mask of 0 gives
+    ``extract_patches``' bits.  ``direct`` forces the route that stages nothing in LDS (the same
+    bits).  Runs on the current stream; N = 0 returns an empty tensor without a launch."""
+    n, f, h, w, stats = _require_aug_extract(frames, frame_index, geom, valid, aug, size, seed, step,
+                                             object_offset, pad, mean, std)
     out = torch.empty(n, 3, size, size, device=frames.device, dtype=torch.float32)
     if n:
         flags = (_lib.PATCH_TO_RGB if to_rgb else 0) | (_lib.PATCH_QUANTIZE if quantize else 0) | \
@@ -1008,6 +1017,71 @@ def extract_patches_aug(frames: Tensor, frame_index: Tensor, geom: Tensor, valid
                 ctypes.cast(stats[0], ctypes.c_void_p), ctypes.cast(stats[1], ctypes.c_void_p),
                 flags, int(seed), int(step), int(object_offset))
     return out
+
+
+def extract_patches_aug_bg(frames: Tensor, masks: Tensor, frame_index: Tensor, geom: Tensor,
+                           valid: Tensor, aug: Tensor, backgrounds: Tensor, size: int, seed: int,
+                           step: int, object_offset: int = 0, p: float = 0.3,
+                           background_sizes: Optional[Tensor] = None,
+                           background_index: Optional[Tensor] = None, pad: int = 128,
+                           mean: Optional[Sequence[float]] = None,
+                           std: Optional[Sequence[float]] = None, to_rgb: bool = False,
+                           quantize: bool = True, direct: bool = False) -> Tuple[Tensor, Tensor]:
+    """``extract_patches_aug`` with the reference's RandomBackground between the crop and the
+    colour stages, in the same launch (scflow_train_patch_extract_bg): ``masks``
+    [F, H, W] uint8 (foreground where != 0), ``backgrounds`` [B, Hb, Wb, 3] uint8 BGR with
+    ``background_sizes`` [B, 2] int32 = the used (height, width) of every slot, top-left aligned
+    (None: the whole slot).  With probability ``p`` an object takes one slot, drawn uniformly from
+    (seed, step, object_offset + i); every crop pixel outside the frame or with a zero mask byte
+    then becomes the slot's used region resampled bilinearly to the crop's own size, and the stages
+    run on the composite.  ``background_index`` [N] int32 replaces the draw: −1 none, 0 … B−1 that
+    slot, anything else none.  Returns (patches [N, 3, size, size], chosen [N] int32: the slot
+    applied, −1 for none).
+
+    ``background_sizes`` on the host (a CPU tensor) is checked here, row by row, and copied to the
+    pool's device; a device tensor is used as it is, without a synchronisation, and a row that is
+    no used size of its slot leaves the objects that draw it without a background (chosen −1).
+    Runs on the current stream; N = 0 returns empty tensors without a launch."""
+    if not isinstance(backgrounds, torch.Tensor) or backgrounds.dtype != torch.uint8 or \
+            backgrounds.dim() != 4 or backgrounds.shape[3] != 3 or 0 in backgrounds.shape:
+        got = f"{list(backgrounds.shape)} {backgrounds.dtype}" \
+            if isinstance(backgrounds, torch.Tensor) else type(backgrounds).__name__
+        raise ScflowError(f"backgrounds must be a non-empty [B, Hb, Wb, 3] uint8 tensor, got {got}")
+    b, hb, wb, _ = backgrounds.shape
+    sizes = background_sizes
+    if sizes is not None:
+        if not isinstance(sizes, torch.Tensor) or sizes.dtype != torch.int32 or \
+                tuple(sizes.shape) != (b, 2):
+            raise ScflowError(f"background_sizes must be a [{b}, 2] int32 tensor")
+        if sizes.device.type == "cpu":
+            bad = ((sizes < 1) | (sizes > torch.tensor([hb, wb], dtype=torch.int32))).any(1)
+            if bad.any():
+                i = int(bad.nonzero()[0])
+                raise ScflowError(f"background_sizes[{i}] = {sizes[i].tolist()} is no used size of a "
+                                  f"{hb} × {wb} slot")
+    if not 0.0 <= float(p) <= 1.0:  # a NaN fails both comparisons
+        raise ScflowError(f"p must be a probability in [0, 1], got {p}")
+    n, f, h, w, stats = _require_aug_extract(frames, frame_index, geom, valid, aug, size, seed, step,
+                                             object_offset, pad, mean, std)
+    _require_patch(masks, "masks", torch.uint8, (f, h, w))
+    _require_patch(backgrounds, "backgrounds", torch.uint8)
+    if sizes is not None:
+        if sizes.device.type == "cpu":
+            sizes = sizes.to(backgrounds.device)
+        _require_patch(sizes, "background_sizes", torch.int32)
+    if background_index is not None:
+        _require_patch(background_index, "background_index", torch.int32, (n,))
+    out = torch.empty(n, 3, size, size, device=frames.device, dtype=torch.float32)
+    chosen = torch.empty(n, device=frames.device, dtype=torch.int32)
+    if n:
+        flags = (_lib.PATCH_TO_RGB if to_rgb else 0) | (_lib.PATCH_QUANTIZE if quantize else 0) | \
+            (_lib.PATCH_AUG_DIRECT if direct else 0)
+        _launch("scflow_train_patch_extract_bg", frames, _p(frames), _p(frame_index), _p(geom),
+                _p(valid), _p(aug), _p(out), _p(masks), _p(backgrounds), _p(sizes),
+                _p(background_index), _p(chosen), n, f, h, w, int(size), int(pad),
+                ctypes.cast(stats[0], ctypes.c_void_p), ctypes.cast(stats[1], ctypes.c_void_p),
+                flags, b, hb, wb, float(p), int(seed), int(step), int(object_offset))
+    return out, chosen
 
 
 # ------------------------------------------------------------------------------- resampling

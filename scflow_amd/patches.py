@@ -136,8 +136,10 @@ def frames_to_train_patches(frames: Tensor, masks: Tensor, frame_index: Tensor,
                             labels: Tensor, points: Tensor, counts: Tensor, diameters: Tensor,
                             seed: int, step: int, aug: Optional[dict] = None, size: int = 256,
                             object_offset: int = 0, max_tries: int = 32, pad_val: int = 128,
-                            img_norm_cfg: Optional[dict] = None, to_rgb: bool = True
-                            ) -> Dict[str, Tensor]:
+                            img_norm_cfg: Optional[dict] = None, to_rgb: bool = True, *,
+                            backgrounds: Optional[Tensor] = None,
+                            background_sizes: Optional[Tensor] = None, background_p: float = 0.3,
+                            background_index: Optional[Tensor] = None) -> Dict[str, Tensor]:
     """Decoded frames [F, H, W, 3] uint8 (BGR) and their instance masks [F, H, W] uint8 plus N
     annotated objects — frame_index [N], GT poses, labels, ori_k per object or per frame — to the
     real-image half of a training batch, as the reference's training pipeline formats it
@@ -153,7 +155,15 @@ def frames_to_train_patches(frames: Tensor, masks: Tensor, frame_index: Tensor,
     [N], ``tries``, ``ratio``, ``aug`` [N, 8] and ``geom`` [N, 8].  Every random number is a
     function of (seed, step, object_offset + i): a data-parallel rank passes the
     number of objects before its own as ``object_offset``.  An invalid object gets a ``pad_val``
-    patch.  Everything runs on the current stream without a host synchronisation."""
+    patch.  Everything runs on the current stream without a host synchronisation.
+
+    ``backgrounds`` [B, Hb, Wb, 3] uint8 BGR adds the reference's ``RandomBackground(p=
+    background_p)`` between the crop and the colour stages (configs/refine_datasets/
+    ycbv_mixpbr.py:49) in the same launch (``ops.extract_patches_aug_bg`` with
+    ``masks`` as the foreground): ``background_sizes`` [B, 2] int32 gives the used (height, width)
+    of each slot, ``background_index`` [N] replaces the draw (−1: none), and the result gains
+    ``background_index`` [N] int32, the slot every object got (−1: none).  Loading a directory of
+    images into the pool is the caller's."""
     if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
         raise ScflowError("frames must be a [F, H, W, 3] uint8 tensor")
     f, h, w, _ = frames.shape
@@ -174,11 +184,20 @@ def frames_to_train_patches(frames: Tensor, masks: Tensor, frame_index: Tensor,
     _, geom, T, k, valid = ops.patch_boxes(points, counts, lab, R, t, ori_k.contiguous().float(),
                                            ratio, h, w, size, frame_index=fidx, num_frames=f,
                                            k_per_frame=per_frame)
-    images = ops.extract_patches_aug(frames.contiguous(), fidx, geom, valid, rows, size, seed, step,
-                                     object_offset, pad=pad_val, mean=norm["mean"],
-                                     std=norm["std"], to_rgb=to_rgb)
+    extra = {}
+    if backgrounds is None:
+        images = ops.extract_patches_aug(frames.contiguous(), fidx, geom, valid, rows, size, seed,
+                                         step, object_offset, pad=pad_val, mean=norm["mean"],
+                                         std=norm["std"], to_rgb=to_rgb)
+    else:
+        flat = masks[..., 0] if isinstance(masks, torch.Tensor) and masks.dim() == 4 else masks
+        index = None if background_index is None else _i32(background_index)
+        images, extra["background_index"] = ops.extract_patches_aug_bg(
+            frames.contiguous(), flat.contiguous(), fidx, geom, valid, rows, backgrounds, size,
+            seed, step, object_offset, p=background_p, background_sizes=background_sizes,
+            background_index=index, pad=pad_val, mean=norm["mean"], std=norm["std"], to_rgb=to_rgb)
     gt_masks = extract_maps(masks, fidx, geom, valid, size, mode="nearest")[:, 0]
-    return dict(real_images=images, gt_masks=(gt_masks > 0).float(), internel_k=k,
+    return dict(extra, real_images=images, gt_masks=(gt_masks > 0).float(), internel_k=k,
                 transform_matrix=T, ref_rotation=R, ref_translation=t, gt_rotation=R_gt,
                 gt_translation=t_gt, label=labels.long(), valid=(valid != 0) & (ok != 0),
                 init_add_error=err[:, 0], init_rot_error=err[:, 1], init_trans_error=err[:, 2],

@@ -246,7 +246,11 @@ class SCFlowRefiner(_RefinerBase):
                                 gt_rotations: Tensor, gt_translations: Tensor, ori_k: Tensor,
                                 labels: Tensor, diameters: Tensor, seed: int, step: int,
                                 aug: Optional[dict] = None, object_offset: int = 0,
-                                drop_invalid: bool = False, points=None) -> Dict[str, Tensor]:
+                                drop_invalid: bool = False, points=None, *,
+                                backgrounds: Optional[Tensor] = None,
+                                background_sizes: Optional[Tensor] = None,
+                                background_p: float = 0.3,
+                                background_index: Optional[Tensor] = None) -> Dict[str, Tensor]:
         """Decoded frames [F, H, W, 3] uint8, instance masks [F, H, W] uint8 and N annotated
         objects → the batch ``train.step.TrainStep`` takes: ``patches.frames_to_train_patches``
         (pose jitter, random crop, colour augmentation, all on the device, at the renderer's image
@@ -255,7 +259,9 @@ class SCFlowRefiner(_RefinerBase):
         float32; ``points`` as in ``refine_frames``.  The default keeps all N objects and
         synchronises nothing (``valid`` says which are usable); ``drop_invalid=True`` compacts
         every per-object entry by ``valid``, which costs ONE host synchronisation (the number of
-        valid objects sizes the result)."""
+        valid objects sizes the result).  ``backgrounds`` and the other ``background_*``
+        keywords: ``frames_to_train_patches``' (RandomBackground; the batch gains
+        ``background_index``)."""
         from . import patches
         if self.renderer is None:
             raise RuntimeError("SCFlowRefiner was built without a renderer config")
@@ -267,7 +273,9 @@ class SCFlowRefiner(_RefinerBase):
         data = patches.frames_to_train_patches(
             frames, masks, frame_index, gt_rotations, gt_translations, ori_k, labels, points[0],
             points[1], diameters, seed, step, aug=aug, size=self.renderer.image_size[0],
-            object_offset=object_offset)
+            object_offset=object_offset, backgrounds=backgrounds,
+            background_sizes=background_sizes, background_p=background_p,
+            background_index=background_index)
         if drop_invalid:
             keep = data["valid"].nonzero()[:, 0]  # the synchronisation
             data = {k: v[keep] for k, v in data.items()}

@@ -262,3 +262,25 @@ def ellipsoid_mesh(semi_axes, n_lat: int = 24, n_lon: int = 48) -> Tuple[np.ndar
     u = verts / a
     colors = 0.5 + 0.4 * np.stack([u[:, 0], u[:, 1] * u[:, 2], np.cos(3 * u[:, 0])], 1)
     return verts.astype(np.float32), np.asarray(faces, np.int64), colors.astype(np.float32)
+
+
+def make_background_pool(slots: int, height: int, width: int, seed: int = 0,
+                         full: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """A stand-in for the reference's ``background_dir`` (data/coco is absent and no image decoder
+    exists here): (pool [slots, height, width, 3] uint8 BGR, sizes [slots, 2] int32).  Slot i is a
+    smooth colour gradient plus seeded noise on its used region — sizes[i] = (h, w), top-left
+    aligned, between half and all of the slot's sides, all of them with ``full`` — and 0
+    elsewhere."""
+    rng = np.random.default_rng(seed + 104729)
+    pool = np.zeros((slots, height, width, 3), np.uint8)
+    sizes = np.empty((slots, 2), np.int32)
+    for i in range(slots):
+        h = height if full else int(rng.integers((height + 1) // 2, height + 1))
+        w = width if full else int(rng.integers((width + 1) // 2, width + 1))
+        y, x = np.mgrid[0:h, 0:w].astype(np.float64)
+        phase = rng.uniform(0.0, 2 * math.pi, 3)
+        wave = np.stack([np.sin(phase[c] + 3.0 * (c + 1) * (x / w + y / h)) for c in range(3)], -1)
+        img = 127.5 + 90.0 * wave + rng.normal(0.0, 12.0, (h, w, 3))
+        pool[i, :h, :w] = np.clip(np.rint(img), 0, 255).astype(np.uint8)
+        sizes[i] = (h, w)
+    return pool, sizes

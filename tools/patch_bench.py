@@ -26,6 +26,14 @@ JSON line.  No threshold: the parent has no such path.
   window; the same bits);
 * `train_mask0`: the same three launches with every stage probability below 0 (stage mask 0: the
   extract does `plain`'s work).
+
+`--train --background` adds the background stage to the same alternation:
+
+* `train_bg_p03`, `train_bg_p1`: `train` with `ops.extract_patches_aug_bg` in place of the extract,
+  a pool of `--slots` (64) seeded slots of `--pool-height` × `--pool-width` (480 × 640) used in
+  full, at p = 0.3 and p = 1.  The instance masks are the ellipses inscribed in the objects' boxes
+  at the GT pose.  Also printed: the bytes the stage adds at p = 1, from the shapes — one mask byte
+  per crop pixel inside the frame and 12 pool bytes per background pixel of a crop.
 """
 import argparse
 import json
@@ -88,6 +96,21 @@ def train_bench(a, s):
 
     run = {"plain": plain, "train": train, "train_direct": lambda: train(direct=True),
            "train_mask0": lambda: train(cfg=off)}
+    if a.background:
+        from scflow_amd import synthetic
+        pool = torch.from_numpy(synthetic.make_background_pool(a.slots, a.pool_height, a.pool_width,
+                                                               full=True)[0]).to(dev)
+        masks = ellipse_masks(a, s, boxes(s["R"], s["t"], torch.ones_like(s["ratio"]))[0])
+
+        def train_bg(p, step=0):
+            R, t, _, ok, tries, ratio, rows = ops.train_draw(s["points"], s["counts"], s["labels"],
+                                                             diam, s["R"], s["t"],
+                                                             patches.TRAIN_AUG, seed, step)
+            _, geom, _, _, valid = boxes(R, t, ratio)
+            return ops.extract_patches_aug_bg(s["frames"], masks, s["fidx"], geom, valid, rows, pool,
+                                              a.size, seed, step, p=p, **norm) + (geom, valid)
+
+        run["train_bg_p03"], run["train_bg_p1"] = (lambda: train_bg(0.3)), (lambda: train_bg(1.0))
     outs = {}
     for k, f in run.items():
         for _ in range(3):
@@ -115,11 +138,54 @@ def train_bench(a, s):
         res[k] = dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v))
         print(f"{k}: median {res[k]['median_ms']:.4f} ms/call (min {min(v):.4f}, max {max(v):.4f})")
     res["train_over_plain"] = res["train"]["median_ms"] / res["plain"]["median_ms"]
+    if a.background:
+        _, c03, _, _ = outs["train_bg_p03"]
+        _, c1, geom1, valid1 = outs["train_bg_p1"]
+        inside, bgpx = background_bytes(a, s, masks, geom1, valid1)
+        res.update(slots=a.slots, pool_height=a.pool_height, pool_width=a.pool_width,
+                   replaced_p03=int((c03 >= 0).sum()), replaced_p1=int((c1 >= 0).sum()),
+                   mask_bytes_p1=inside, pool_bytes_p1=12 * bgpx,
+                   same_bits_p0_train=bool(torch.equal(
+                       img, ops.extract_patches_aug_bg(s["frames"], masks, s["fidx"], geom, valid,
+                                                       rows, pool, a.size, seed, 0, p=0.0, **norm)[0])))
+        print(f"background: {a.slots} slots of {a.pool_height}×{a.pool_width}; p = 0.3 replaces "
+              f"{res['replaced_p03']} of {a.objects} objects, p = 1 {res['replaced_p1']}; at p = 1 the "
+              f"stage reads {inside / 1e6:.2f} MB of mask (one byte per crop pixel inside the frame) "
+              f"and up to {12 * bgpx / 1e6:.2f} MB of pool (12 B per background pixel of a crop), "
+              f"before the halo and the overlap of neighbouring tiles' windows; p = 0 "
+              f"{'equals' if res['same_bits_p0_train'] else 'DIFFERS FROM'} `train` bit for bit")
     print(f"F={a.frames} frames of {a.height}×{a.width}, N={a.objects} objects ({res['valid']} valid, "
           f"{res['accepted']} jittered within {res['max_tries']} tries, crops {res['crop_min']}-"
           f"{res['crop_max']} px), S={a.size}: train / plain = {res['train_over_plain']:.2f}×; tiled "
           f"and direct routes {'equal' if res['same_bits_tiled_direct'] else 'DIFFER'} bit for bit")
     return res
+
+
+def ellipse_masks(a, s, bbox):
+    """[F, H, W] uint8 instance masks: the ellipse inscribed in every object's box (l, t, r, b)."""
+    yy, xx = np.mgrid[0:a.height, 0:a.width]
+    masks = np.zeros((a.frames, a.height, a.width), np.uint8)
+    for (l, t, r, b), f in zip(bbox.cpu().numpy().tolist(), s["fidx"].cpu().numpy().tolist()):
+        if not np.isfinite([l, t, r, b]).all() or r <= l or b <= t:
+            continue
+        inside = ((xx - (l + r) / 2) / ((r - l) / 2)) ** 2 + ((yy - (t + b) / 2) / ((b - t) / 2)) ** 2 <= 1
+        masks[f][inside] = 255
+    return torch.from_numpy(masks).to(s["frames"].device)
+
+
+def background_bytes(a, s, masks, geom, valid):
+    """(crop pixels inside the frame, background pixels of the crops) over the valid objects."""
+    m = masks.cpu().numpy()
+    inside = bgpx = 0
+    for (x1, y1, x2, y2, *_), f, v in zip(geom.cpu().numpy().tolist(), s["fidx"].cpu().numpy().tolist(),
+                                          valid.cpu().numpy().tolist()):
+        if not v:
+            continue
+        xa, xb, ya, yb = max(x1, 0), min(x2, a.width - 1), max(y1, 0), min(y2, a.height - 1)
+        win = m[f][ya:yb + 1, xa:xb + 1]
+        inside += win.size
+        bgpx += (x2 - x1 + 1) * (y2 - y1 + 1) - int((win != 0).sum())
+    return inside, bgpx
 
 
 def main():
@@ -133,7 +199,14 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--json", default=None)
     ap.add_argument("--train", action="store_true", help="time the training front end (§17)")
+    ap.add_argument("--background", action="store_true",
+                    help="with --train: add the background stage at p = 0.3 and p = 1 (§18)")
+    ap.add_argument("--slots", type=int, default=64)
+    ap.add_argument("--pool-height", type=int, default=480)
+    ap.add_argument("--pool-width", type=int, default=640)
     a = ap.parse_args()
+    if a.background and not a.train:
+        raise SystemExit("--background times the training front end: pass --train with it")
     if not torch.cuda.is_available():
         raise SystemExit("patch_bench needs a GPU: a CPU run says nothing about these timings")
     from scflow_amd import _lib, ops
