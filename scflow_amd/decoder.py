@@ -1,34 +1,35 @@
 """SCFlowDecoder — drop-in replacement for the reference decoder, running on gfx950 HIP kernels.
 
-Reference: ``/root/reference/models/decoder/scflow_decoder.py:19-252``.  Same constructor
-kwargs (:48-68), same submodules and state-dict keys (so reference checkpoints load), same
-``forward`` signature (:151-156) and the same 7-list return (:252).  ``iters`` is re-read on
-every call (the refiner overwrites it temporarily, ``scflow_refiner.py:150-158``).
+Reference: ``models/decoder/scflow_decoder.py:19-252``.  Same constructor kwargs (:48-68), same
+submodules and state-dict keys (so reference checkpoints load), same ``forward`` signature
+(:151-156) and the same 7-list return (:252).  ``iters`` is re-read on every call (the refiner
+overwrites it temporarily, ``scflow_refiner.py:150-158``).
 
-Forward, per call (B pairs, features h×w = image/8, M = B·h·w):
+A forward (B pairs, features h×w = image/8, M = B·h·w) is one ``_DecoderRun``: its constructor
+launches what happens once — the correlation pyramid (a1), the dense object-frame points (a9, no
+``nonzero``, no host sync), the channels-last working set ``HX = [h | cxt | motion | flow]`` — and
+plans the schedule; then, ``iters`` times, two phases:
 
-* a1  ``scflow_corr_pyramid``: correlation GEMM (fp32 MFMA) + pooled levels, once;
-* a9  ``scflow_lift_points``: dense per-pixel object-frame points, once (no ``nonzero``, no
-  host sync);
-* then ``iters`` times, with every activation channels-last in a handful of buffers
-  (``HX = [h | cxt | motion | flow]`` is exactly the GRU's ``cat[h, x]``):
-  a11↓ downsample → a2 lookup → a3 motion encoder (5 convs) → a4 GRU (4 launches: z/r fused,
-  q with the state update fused) → a5 heads (hidden convs of both heads in one launch, thin
-  predictors) → a6 Δflow/mask encoders → a7 pose head (PyTorch-ROCm) → a11↑ upsample →
-  a8+a10 pose update + reprojection (one launch).
+* ``heavy(it)``: the ↓8 flow (a11↓, first iteration only under the fused tail), the flow branch on
+  the side stream beside lookup + corr_net (a2, a3), out_net, the GRU (a4) and the heads' hidden
+  convs with their predictors (a5) — the convolutions that fill the chip; the previous iteration's
+  deferred full-resolution outputs are queued on the side stream behind the join;
+* ``tail(it)``: flow predictor + Δflow encoder ‖ mask predictor + mask encoder (a5, a6; paired
+  launches, or two streams), the pose head's trunk (a7, HIP) and the fused pose step (a8 + a10 +
+  a11↑ + the next iteration's a11↓; its rotation / translation heads inside the same launch).
 
 No host synchronisation happens inside ``forward``; the whole call can be captured into a
 HIP graph (``graph.py``).  There is no CPU path: inputs must be on a ROCm device.
 
 The constructor's common part and the iteration up to the GRU (pyramid, ``HX``, a2–a4, the
 recorded segments, the tiled / fused-lookup planning) live in ``recurrent.py``, shared with the
-RAFT decoders; this file holds what follows the GRU (a5–a11), the streams, events, ping-pong and
-kernel-timer hooks.
+RAFT decoders; this file holds what follows the GRU (a5–a11), the streams and events
+(``_Streams``), ping-pong and the kernel-timer hooks.
 """
 from __future__ import annotations
 
 import os
-from typing import Dict, Optional, Sequence, Tuple, Union
+from typing import Dict, Optional, Sequence, Union
 
 import torch
 import torch.nn as nn
@@ -57,6 +58,77 @@ def _record_on(out, stream) -> None:
                     t.record_stream(stream)
 
 
+def _alloc_outputs(iters: int, N: int, H: int, W: int, rot_channels: int, dev) -> Dict[str, Tensor]:
+    """The seven stacked output tensors of a forward (the lists returned are views)."""
+    def e(*shape):
+        return torch.empty(iters, N, *shape, device=dev, dtype=torch.float32)
+    return dict(flow_pose=e(2, H, W), flow_pred=e(2, H, W), mask=e(1, H, W), R=e(3, 3), t=e(3),
+                drot=e(rot_channels), dt=e(3))
+
+
+def _lists(outs: Dict[str, Tensor]):
+    """The reference's 7-list return: per-iteration views of the stacked outputs."""
+    return tuple(list(outs[k].unbind(0))
+                 for k in ("flow_pose", "flow_pred", "R", "t", "mask", "drot", "dt"))
+
+
+def _at(bufs, i: int) -> Tensor:
+    """Buffer ``i`` of a list that holds two buffers where the plan double-buffers them (indexed
+    by parity) and one where it does not."""
+    return bufs[i % len(bufs)]
+
+
+class _Streams:
+    """A forward's (main, side) streams, their raw handles and the orderings the forward uses.
+
+    ``events`` = (fork, join, mark), each with ``record(s)`` / ``wait(s)``: ``ops.SyncEvent``
+    (device scope: no system-scope cache writeback per record) on the raw handles (``raw``), or
+    ``torch.cuda.Event`` on the stream objects.  They are reused every iteration (a wait captures
+    the event's state when issued).  Without events, or with ``side is main``, everything runs on
+    the main stream and every method is a no-op."""
+
+    def __init__(self, main, side, events=None, raw: bool = True) -> None:
+        self.main, self.side = main, (main if events is None else side)
+        self.h_main, self.h_side = main.cuda_stream, self.side.cuda_stream
+        self.two = self.side is not main
+        self._m, self._s = (self.h_main, self.h_side) if raw else (main, self.side)
+        self._fork, self._join, self._mark = events if self.two else (None, None, None)
+
+    @classmethod
+    def of(cls, dec: "SCFlowDecoder", dev, slot=0) -> "_Streams":
+        """The current stream + ``dec``'s side stream of this slot, with ``dec``'s event flavour."""
+        main = torch.cuda.current_stream(dev)
+        if not dec.side_stream:
+            return cls(main, main)
+        side = dec._side_stream(dev, slot)
+        if dec.device_scope_events:
+            evs = dec._sync_events(dev, slot) + dec._sync_events(dev, (slot, "full"))[:1]
+            return cls(main, side, evs)
+        return cls(main, side, tuple(torch.cuda.Event() for _ in range(3)), raw=False)
+
+    def fork(self) -> None:
+        """The side stream waits for what the main stream holds now."""
+        if self.two:
+            self._fork.record(self._m)
+            self._fork.wait(self._s)
+
+    def join(self) -> None:
+        """The main stream waits for what the side stream holds now."""
+        if self.two:
+            self._join.record(self._s)
+            self._join.wait(self._m)
+
+    def mark_side(self) -> None:
+        """Mark the side stream's position (after a deferred launch) …"""
+        if self.two:
+            self._mark.record(self._s)
+
+    def wait_side_mark(self) -> None:
+        """… and have the main stream wait for the last mark (see ``_DecoderRun.tail``)."""
+        if self.two:
+            self._mark.wait(self._m)
+
+
 @MODELS.register_module()
 class SCFlowDecoder(_RecurrentDecoder):
     def __init__(self, net_type: str, num_levels: int, radius: int, iters: int, detach_flow: bool,
@@ -82,7 +154,6 @@ class SCFlowDecoder(_RecurrentDecoder):
             ConvModule(2, 128, 7, padding=3, **mk), ConvModule(128, 64, 3, padding=1, **mk))
         self.mask_encoder = nn.Sequential(
             ConvModule(1, 64, 3, padding=1, **mk), ConvModule(64, 32, 3, padding=1, **mk))
-        # optional per-kernel timing hooks (bench.py): name -> callable(start: bool)
         # name -> callable(start: bool) bracketing one launch (bench.py's live kernel timing):
         # gru_zr, gru_q, corr_pyramid, corr_lookup, pose_flow
         self.kernel_hooks: Dict[str, object] = {}
@@ -99,7 +170,6 @@ class SCFlowDecoder(_RecurrentDecoder):
         # the XHeads' predictors contracted in the hidden conv's epilogue (scflow_xhead_pred:
         # the 512-channel hidden output is never written; round 6) where the shapes allow it
         self.fuse_xhead_pred = os.environ.get("SCFLOW_XHEAD_PRED", "1") != "0"
-        self.dbg_skip_fullres = False  # measurement only (tools/ab_bench.py)
         # fork / join with device-scope events (no system-scope cache writeback per record)
         self.device_scope_events = True
         # the iteration's tail (pose update, pose flow, ×8 prediction, next ↓8 flow) as one
@@ -124,11 +194,10 @@ class SCFlowDecoder(_RecurrentDecoder):
         self.fullres_given = os.environ.get("SCFLOW_FULLRES_GIVEN", "1") != "0"
         # 0: every stream at the default priority; 1: the forward's critical stream is a
         # high-priority stream of the decoder's own (the side branches at the default), so the
-        # CP dispatches its workgroups first when both queues hold work; 2: the side branches'
-        # stream at high priority instead; -1 (default): 1 for feature maps above 32×32, else 0.
-        # Measured (round 5, tools/sess_r5ag.sh, in-process A/B): configs[4] 44.64 / 44.90 /
-        # 44.99 ms per forward for 1 / 0 / 2; configs[1] 4.926 / 4.841 / 4.909 ms — at 32² the
-        # side branches are nearly as long as the critical ones and must not be held back
+        # CP dispatches its workgroups first when both queues hold work; -1 (default): 1 for
+        # feature maps above 32×32, else 0.  Measured (round 5, in-process A/B): configs[4]
+        # 44.64 / 44.90 ms per forward for 1 / 0; configs[1] 4.926 / 4.841 ms — at 32² the side
+        # branches are nearly as long as the critical ones and must not be held back
         self.main_priority = -1
         self._hooks_on = True
         self.hook_batch = 0
@@ -180,16 +249,15 @@ class SCFlowDecoder(_RecurrentDecoder):
 
     def _side_stream(self, dev, slot=0) -> torch.cuda.Stream:
         """An extra HIP stream (created once per device and slot): slot 0 / 1 the side branches
-        of each ping-pong half, "main1" the second half's main stream."""
+        of each ping-pong half, "main1" the second half's main stream, "priority" (main_priority
+        1) the critical stream at the highest priority the device allows (a lower number is a
+        higher priority)."""
         ss = getattr(self, "_streams", None)
         if ss is None:
             ss = self._streams = {}
-        # "priority" (main_priority 1) and the side branches under main_priority 2: the highest
-        # priority the device allows (a lower number is a higher priority)
-        prio = -8 if slot == "priority" or (self.main_priority == 2 and slot in (0, 1)) else 0
-        if (dev, slot, prio) not in ss:
-            ss[(dev, slot, prio)] = torch.cuda.Stream(device=dev, priority=prio)
-        return ss[(dev, slot, prio)]
+        if (dev, slot) not in ss:
+            ss[(dev, slot)] = torch.cuda.Stream(device=dev, priority=-8 if slot == "priority" else 0)
+        return ss[(dev, slot)]
 
     def _hook(self, name: str, start: bool) -> None:
         if not self._hooks_on:
@@ -231,10 +299,9 @@ class SCFlowDecoder(_RecurrentDecoder):
 
         With ``self.pingpong`` and a batch of ≥ 2·``pingpong_min`` pairs the batch runs as two
         halves interleaved on two stream pairs (``_forward_pingpong``); else as one."""
-        N = feat_render.shape[0]
-        if self.pingpong and hx is None and N >= 2 * self.pingpong_min:
-            return self._forward_pingpong(feat_render, feat_real, h_feat, cxt_feat, R0, t0, depth, K,
-                                          label, init_flow, invalid, head_label)
+        args = (feat_render, feat_real, h_feat, cxt_feat, R0, t0, depth, K, label, init_flow, invalid)
+        if self.pingpong and hx is None and feat_render.shape[0] >= 2 * self.pingpong_min:
+            return self._forward_pingpong(*args, head_label)
         mp = self.main_priority
         if mp < 0:
             mp = 1 if feat_render.shape[-2] * feat_render.shape[-1] > 32 * 32 else 0
@@ -244,27 +311,24 @@ class SCFlowDecoder(_RecurrentDecoder):
             hp = self._side_stream(dev, "priority")
             hp.wait_stream(cur)  # inputs produced on the caller's stream
             with torch.cuda.stream(hp):
-                out = self._run_steps(feat_render, feat_real, h_feat, cxt_feat, R0, t0, depth, K,
-                                      label, init_flow, invalid, hx, head_label)
+                out = self._forward_single(*args, hx, head_label)
             cur.wait_stream(hp)
             _record_on(out, cur)
             return out
-        return self._run_steps(feat_render, feat_real, h_feat, cxt_feat, R0, t0, depth, K, label,
-                               init_flow, invalid, hx, head_label)
+        return self._forward_single(*args, hx, head_label)
 
-    def _run_steps(self, feat_render, feat_real, h_feat, cxt_feat, R0, t0, depth, K, label,
-                   init_flow, invalid, hx, head_label):
-        gen = self._forward_steps(feat_render, feat_real, h_feat, cxt_feat, R0, t0, depth, K, label,
-                                  init_flow, invalid, hx=hx, head_label=head_label)
-        while True:
-            try:
-                next(gen)
-            except StopIteration as e:
-                return e.value
+    def _forward_single(self, *args):
+        """The whole batch as one run on the current stream (+ slot 0's side stream)."""
+        run = _DecoderRun(self, *args)
+        for it in range(run.iters):
+            run.heavy(it)
+            run.tail(it)
+        run.finish()
+        return run.lists()
 
     def _forward_pingpong(self, feat_render, feat_real, h_feat, cxt_feat, R0, t0, depth, K, label,
                           init_flow, invalid, head_label):
-        """The batch as two halves A | B, each a complete forward on its own (main, side) stream
+        """The batch as two halves A | B, each a complete run on its own (main, side) stream
         pair, with their iterations interleaved so that one half's latency-bound iteration tail
         (Δflow / mask encoders, pose head, pose update: many small launches that leave most CUs
         idle) runs while the other half's convolutions fill the chip.  Two device-scope events
@@ -276,25 +340,14 @@ class SCFlowDecoder(_RecurrentDecoder):
         tensors (per-half views)."""
         dev = feat_render.device
         N = feat_render.shape[0]
-        n0 = N // 2
         iters = int(self.iters)
-        _, H, W = depth.shape
-        f32 = torch.float32
-        outs = dict(flow_pose=torch.empty(iters, N, 2, H, W, device=dev, dtype=f32),
-                    flow_pred=torch.empty(iters, N, 2, H, W, device=dev, dtype=f32),
-                    mask=torch.empty(iters, N, 1, H, W, device=dev, dtype=f32),
-                    R=torch.empty(iters, N, 3, 3, device=dev, dtype=f32),
-                    t=torch.empty(iters, N, 3, device=dev, dtype=f32),
-                    drot=torch.empty(iters, N, self.pose_pred.rotation_out_channels, device=dev,
-                                     dtype=f32),
-                    dt=torch.empty(iters, N, 3, device=dev, dtype=f32))
+        outs = _alloc_outputs(iters, N, *depth.shape[1:], self.pose_pred.rotation_out_channels, dev)
         gl = (label if head_label is None else head_label).to(dev).long()[:1]
         cur = torch.cuda.current_stream(dev)
         mains = [cur, self._side_stream(dev, "main1")]
         ev = self._pp_events(dev)  # (A heavy done, B heavy done)
         h_main = [m.cuda_stream for m in mains]
         mains[1].wait_stream(cur)  # inputs produced on the caller's stream
-        halves = [slice(0, n0), slice(n0, N)]
 
         def pp(k):
             def before(it):
@@ -307,387 +360,326 @@ class SCFlowDecoder(_RecurrentDecoder):
                 ev[k].record(h_main[k])
             return before, after
 
-        gens = []
-        for k, sl in enumerate(halves):
-            sub = dict(flow_pose=outs["flow_pose"][:, sl], flow_pred=outs["flow_pred"][:, sl],
-                       mask=outs["mask"][:, sl], R=outs["R"][:, sl], t=outs["t"][:, sl],
-                       drot=outs["drot"][:, sl], dt=outs["dt"][:, sl])
+        runs = []
+        for k, sl in enumerate((slice(0, N // 2), slice(N // 2, N))):
             with torch.cuda.stream(mains[k]):
-                gens.append(self._forward_steps(
-                    feat_render[sl], feat_real[sl], h_feat[sl], cxt_feat[sl], R0[sl], t0[sl],
-                    depth[sl], K[sl], label[sl], init_flow[sl], invalid, head_label=gl, outs=sub,
-                    slot=k, pp=pp(k), hooks=k == 0))
-        # host issue order: A.heavy(i), B.heavy(i), A.tail(i), B.tail(i), … (each generator step
-        # runs up to its next yield on its own main stream)
-        live = [True, True]
-        while any(live):
-            for k in (0, 1):
-                if live[k]:
+                runs.append(_DecoderRun(
+                    self, feat_render[sl], feat_real[sl], h_feat[sl], cxt_feat[sl], R0[sl], t0[sl],
+                    depth[sl], K[sl], label[sl], init_flow[sl], invalid, head_label=gl,
+                    outs={n: o[:, sl] for n, o in outs.items()}, slot=k, pp=pp(k), hooks=k == 0))
+        # host issue order: A.heavy(i), B.heavy(i), A.tail(i), B.tail(i), …, each on its half's
+        # main stream
+        for it in range(iters):
+            for phase in (_DecoderRun.heavy, _DecoderRun.tail):
+                for k in (0, 1):
                     with torch.cuda.stream(mains[k]):
-                        try:
-                            next(gens[k])
-                        except StopIteration:
-                            live[k] = False
+                        phase(runs[k], it)
+        for k in (0, 1):
+            with torch.cuda.stream(mains[k]):
+                runs[k].finish()
         cur.wait_stream(mains[1])
-        return (list(outs["flow_pose"].unbind(0)), list(outs["flow_pred"].unbind(0)),
-                list(outs["R"].unbind(0)), list(outs["t"].unbind(0)), list(outs["mask"].unbind(0)),
-                list(outs["drot"].unbind(0)), list(outs["dt"].unbind(0)))
+        return _lists(outs)
 
-    def _forward_steps(self, feat_render, feat_real, h_feat, cxt_feat, R0, t0, depth, K, label,
-                       init_flow, invalid, hx: Optional[Tensor] = None,
-                       head_label: Optional[Tensor] = None, outs: Optional[dict] = None,
-                       slot: int = 0, pp=None, hooks: bool = True):
-        """The forward as a generator on the CURRENT stream (+ this slot's side stream): yields
-        after each iteration's heavy phase (through the heads) and after its tail; returns the
-        7 lists.  ``outs``: preallocated output tensors (``_forward_pingpong``'s views);
-        ``pp``: (before_heavy(it), after_heavy(it)) callables ordering this half against the
-        other; ``hooks``: whether the bench's kernel timers bracket this forward's launches."""
+
+class _DecoderRun:
+    """One forward (or one ping-pong half) on the stream that is current when it is built, plus
+    ``slot``'s side stream: the shared ``RecurrentCore``, the buffers of what follows the GRU, the
+    plan, the ``_Streams`` and the stacked outputs.  The caller drives ``heavy(it)`` and
+    ``tail(it)`` for every iteration, then ``finish()``; ``lists()`` is the 7-list return.
+
+    ``outs``: preallocated stacked outputs (``_forward_pingpong``'s per-half views); ``pp``:
+    (before(it), after(it)) callables that order this half's heavy phase against the other's;
+    ``hooks``: whether the bench's kernel timers bracket this run's launches.
+
+    Host path: the launches that read and write the same persistent buffers in every iteration
+    are recorded on the first iteration (``core.segment`` / ``ops.binding``: argument structs built
+    once) and replayed afterwards as one ctypes call each; the launches whose pointers change per
+    iteration (poses, outputs) have their calls for every iteration built once
+    (``build_tail_calls``).  This keeps the host well ahead of the GPU (a Python wrapper costs
+    more than several of the pose head's kernels take to run).
+
+    Every buffer is allocated on the main stream and outlives the forward, and the main stream
+    always waits for the side stream before they are reused.  Buffers written in one iteration
+    and read during the next come in pairs indexed by the iteration's parity (``_at``): the ↓8
+    flow F2 under the fused tail (its launch writes the next iteration's), Δflow and the mask when
+    the full-resolution outputs are deferred.  Under occlusion masking (mask_corr / mask_flow,
+    scflow_decoder.py:189-207) the mask the previous iteration predicted (all ones before the
+    first) scales the correlation samples inside the lookup kernels (mask_corr) and the ↓8 flow
+    inside the launch that produces it (mask_flow: the tail, or the downsample): F2 stays the
+    unmasked flow (the lookup's centroids), FLM = F2 · mask feeds the flow branch and the motion
+    features' flow channels, buffered like F2."""
+
+    def __init__(self, dec: SCFlowDecoder, feat_render, feat_real, h_feat, cxt_feat, R0, t0, depth,
+                 K, label, init_flow, invalid, hx: Optional[Tensor] = None,
+                 head_label: Optional[Tensor] = None, outs: Optional[dict] = None, slot=0, pp=None,
+                 hooks: bool = True) -> None:
+        self.dec, self.pp, self.hooks, self.invalid = dec, pp, hooks, invalid
         dev = feat_render.device
-        self._hooks_on = hooks
-        self.hook_batch = feat_render.shape[0]  # pairs per bracketed launch (bench roofline)
-        f32 = torch.float32
+        dec._hooks_on = hooks
+        dec.hook_batch = feat_render.shape[0]  # pairs per bracketed launch (bench roofline)
         feat_render = feat_render.contiguous().float()
         feat_real = feat_real.contiguous().float()
-        N, C, h, w = feat_render.shape
-        _, H, W = depth.shape
-        scale = 2 ** (self.num_levels - 1)
-        M = N * h * w
-        iters = int(self.iters)
-
+        N, _, h, w = feat_render.shape
+        self.N, self.h, self.w = N, h, w
+        self.H, self.W = depth.shape[1:]
+        self.scale = 2 ** (dec.num_levels - 1)
+        self.iters = iters = int(dec.iters)
         # a1 + a9 (once per forward), then the channels-last working set; the motion encoder's
         # and the GRU's buffers and launches are the shared core's (recurrent.py)
-        core = RecurrentCore(self, feat_render, feat_real, self._hook, self._hooks_for)
-        depth = depth.contiguous().float()
-        K = K.contiguous().float()
-        R_prev = R0.contiguous().float()
-        t_prev = t0.contiguous().float()
-        points = ops.lift_points(depth, K, R_prev, t_prev)
+        self.core = core = RecurrentCore(dec, feat_render, feat_real, dec._hook, dec._hooks_for)
+        self.K = K.contiguous().float()
+        self.R_prev, self.t_prev = R0.contiguous().float(), t0.contiguous().float()
+        self.points = ops.lift_points(depth.contiguous().float(), self.K, self.R_prev, self.t_prev)
         core.bind_state(h_feat, cxt_feat, hx)
-        segment, scratch = core.segment, core.scratch
-        hx_flow, hid = core.hx_flow, core.hid
-        F2 = torch.empty(M, 2, device=dev, dtype=f32)
-        fh = self.flow_pred.layers[-1].conv.out_channels
-        mh = self.mask_pred.layers[-1].conv.out_channels
-        HEAD = torch.empty(M, fh + mh, device=dev, dtype=f32)
-        D2 = torch.empty(M, 2, device=dev, dtype=f32)
-        MASK = torch.empty(M, 1, device=dev, dtype=f32)
-        dfc = self.delta_flow_encoder[-1].conv.out_channels
-        mfc = self.mask_encoder[-1].conv.out_channels
-        FM = torch.empty(M, dfc + mfc, device=dev, dtype=f32)  # [Δflow feat | mask feat]
-        s_dfe = scratch(self.delta_flow_encoder)
-        s_me = scratch(self.mask_encoder)
+        self.label = (label if head_label is None else head_label).to(dev).long()
+        self.flow_full = init_flow.contiguous().float()
+        self.out = outs if outs is not None else _alloc_outputs(
+            iters, N, self.H, self.W, dec.pose_pred.rotation_out_channels, dev)
+        self.st = _Streams.of(dec, dev, slot)
 
-        # outputs (stacked; the lists returned are views)
-        if outs is not None:
-            o_flow_pose, o_flow_pred, o_mask = outs["flow_pose"], outs["flow_pred"], outs["mask"]
-            o_R, o_t = outs["R"], outs["t"]
-        else:
-            o_flow_pose = torch.empty(iters, N, 2, H, W, device=dev, dtype=f32)
-            o_flow_pred = torch.empty(iters, N, 2, H, W, device=dev, dtype=f32)
-            o_mask = torch.empty(iters, N, 1, H, W, device=dev, dtype=f32)
-            o_R = torch.empty(iters, N, 3, 3, device=dev, dtype=f32)
-            o_t = torch.empty(iters, N, 3, device=dev, dtype=f32)
-        drots, dts = [], []
+        # the plan (last_plan's keys; the mask flags do not change it)
+        self.masked = bool(dec.mask_corr or dec.mask_flow)
+        self.fuse_tail = fuse_tail = bool(dec.fuse_tail)
+        self.defer = defer = bool(fuse_tail and dec.defer_full_res and iters > 1)
+        pt = dec.pair_tail if dec.pair_tail >= 0 else int(h * w <= 32 * 32)
+        self.pair_tail = bool(pt) and len(dec.delta_flow_encoder) == len(dec.mask_encoder)
+        self.mark = defer and self.pair_tail  # the mark / wait pair of the deferred launches (tail)
+        dec._last_plan = dict(fuse_tail=fuse_tail, defer=defer, pair_tail=self.pair_tail,
+                              fuse_lc=core.fuse_lc, tiled=core.tiled, side_stream=self.st.two)
 
-        head_runner = self._hidden_heads()
-        flow_pred_r = ConvRunner.of(self.flow_pred.predict_layer, None)
-        mask_pred_r = ConvRunner.of(self.mask_pred.predict_layer, "Sigmoid")
-        label = (label if head_label is None else head_label).to(dev).long()
-        masked = bool(self.mask_corr or self.mask_flow)
-        flow_full = init_flow.contiguous().float()
-        # independent branches run concurrently on a second stream, joined with events:
-        # flow_net ‖ (lookup, corr_net); mask predictor + mask encoder ‖ flow predictor +
-        # Δflow encoder.  Every buffer is allocated above on the main stream and outlives the
-        # forward, and the main stream always waits for the side branch before reusing them.
-        main = torch.cuda.current_stream(dev)
-        two = self.side_stream
-        side = self._side_stream(dev, slot) if two else main
+        def bufs(channels, two):
+            return [torch.empty(core.M, channels, device=dev, dtype=torch.float32)
+                    for _ in range(2 if two else 1)]
+        self.fh = fh = dec.flow_pred.layers[-1].conv.out_channels
+        self.mh = mh = dec.mask_pred.layers[-1].conv.out_channels
+        self.dfc = dfc = dec.delta_flow_encoder[-1].conv.out_channels
+        self.mfc = mfc = dec.mask_encoder[-1].conv.out_channels
+        self.HEAD = bufs(fh + mh, False)[0]
+        self.FM = bufs(dfc + mfc, False)[0]  # [Δflow feat | mask feat]
+        self.s_dfe = core.scratch(dec.delta_flow_encoder)
+        self.s_me = core.scratch(dec.mask_encoder)
+        self.F2s = bufs(2, fuse_tail)
+        self.FLMs = bufs(2, fuse_tail) if dec.mask_flow else self.F2s
+        self.D2s, self.MASKs = bufs(2, defer), bufs(1, defer)
+        if self.masked:  # before the first prediction: interpolate(ones, 1/8) == ones
+            _at(self.MASKs, -1).fill_(1.0)
+        if defer:  # the deferred launches' pose outputs (duplicates of the outputs: not read)
+            self.R_scr = torch.empty(N, 3, 3, device=dev, dtype=torch.float32)
+            self.t_scr = torch.empty(N, 3, device=dev, dtype=torch.float32)
+        self.head_runner = dec._hidden_heads()
+        self.flow_pred_r = ConvRunner.of(dec.flow_pred.predict_layer, None)
+        self.mask_pred_r = ConvRunner.of(dec.mask_pred.predict_layer, "Sigmoid")
+        self.xpred = dec._xhead_pred_plan(self.head_runner, core.hid, self.HEAD, N, h, w, dev)
+        self.keep = []  # buffers the recorded pose-head launches write (alive for the forward)
+        self.pose_x = None  # the pose trunk's output (set when its launches are recorded)
+        self.tail_calls = None  # fused tail: per-iteration (heads, pose step, deferred) launches
+        self.pending = []  # the previous iteration's deferred full-resolution launches
+        self.par = 0
 
-        # two events reused every iteration (a wait captures the event's state when issued);
-        # device-scope ones (ops.SyncEvent) unless self.device_scope_events is False
-        if two and self.device_scope_events:
-            ev_fork, ev_join = self._sync_events(dev, slot)
-            h_main, h_side = main.cuda_stream, side.cuda_stream
-
-            def fork():
-                ev_fork.record(h_main)
-                ev_fork.wait(h_side)
-
-            def join():
-                ev_join.record(h_side)
-                ev_join.wait(h_main)
-        else:
-            ev_fork, ev_join = (torch.cuda.Event(), torch.cuda.Event()) if two else (None, None)
-
-            def fork():
-                if two:
-                    ev_fork.record(main)
-                    side.wait_event(ev_fork)
-
-            def join():
-                if two:
-                    ev_join.record(side)
-                    main.wait_event(ev_join)
-
-        # Host path: the launches that read and write the same persistent buffers in every
-        # iteration are recorded on the first iteration (ops.binding: argument structs built
-        # once) and replayed afterwards as one ctypes call each; only the launches whose
-        # arguments change per iteration (flow in / out, poses, Δpose) go through the wrappers.
-        # This keeps the host well ahead of the GPU (a Python wrapper costs more than several of
-        # the pose head's kernels take to run).
-        keep = []  # buffers the recorded pose-head launches write (alive for the forward)
-        if outs is not None:
-            o_drot, o_dt = outs["drot"], outs["dt"]
-        else:
-            o_drot = torch.empty(iters, N, self.pose_pred.rotation_out_channels, device=dev,
-                                 dtype=f32)
-            o_dt = torch.empty(iters, N, 3, device=dev, dtype=f32)
-        # Fused iteration tail: one launch does the pose update, the pose flow, this
-        # iteration's ×8 prediction (from F2) and the next iteration's ↓8 flow (into the other
-        # F2 buffer, computed from the new pose).  F2 alternates between two buffers, so the
-        # recorded launches that read it (lookup, flow branch) are recorded once per parity.
-        # Occlusion masking (mask_corr / mask_flow, scflow_decoder.py:189-207) runs the same plan:
-        # the mask the previous iteration predicted (mask_prev: all ones before the first) scales
-        # the correlation samples inside the lookup kernels (mask_corr) and the ↓8 flow inside the
-        # launch that produces it (mask_flow: the tail, or the downsample) — F2 stays the unmasked
-        # flow (the lookup's centroids), FLM = F2 · mask feeds the flow branch and the motion
-        # features' flow channels, double-buffered per parity like F2.
-        fuse_tail = self.fuse_tail
-        F2s = [F2, torch.empty_like(F2)] if fuse_tail else [F2, F2]
-        if self.mask_flow:
-            FLMs = [torch.empty_like(F2), torch.empty_like(F2)] if fuse_tail else \
-                [torch.empty_like(F2)] * 2
-        else:
-            FLMs = F2s
-        mask_prev = None  # the mask buffer this iteration's masked launches read
-
-        xpred = self._xhead_pred_plan(head_runner, hid, HEAD, N, h, w, dev)
-
-        def seg_heads():
-            if xpred is not None:  # hidden conv + both predictors → Δflow, mask
-                hargs, pw, xws, fb, mb, fh_ = xpred
-                ops.xhead_pred(hargs, fh_, pw, xws, fb, mb, None, "Sigmoid",
-                               Chan.whole(D2s[cur_par[0]]), Chan.whole(MASKs[cur_par[0]]))
-            elif head_runner is not None:
-                head_runner.run(hid, Chan.whole(HEAD), N, h, w)
-            else:
-                run_chain(self.flow_pred.layers, hid, Chan(HEAD, 0, fh), N, h, w)
-                run_chain(self.mask_pred.layers, hid, Chan(HEAD, fh, mh), N, h, w)
-
-        def seg_mask_branch():
-            MK = MASKs[cur_par[0]]
-            if xpred is None:
-                mask_pred_r.run(Chan(HEAD, fh, mh), Chan.whole(MK), N, h, w)
-            run_chain(self.mask_encoder, Chan.whole(MK), Chan(FM, dfc, mfc), N, h, w, s_me,
-                      hooks=self._hooks_for(None, "mask_enc1"))
-
-        def seg_tail_pair():
-            # the flow-predictor and mask-predictor branches on the main stream, their k-th
-            # launches paired into one grid each (scflow_conv2d_pair): no fork / join events
-            D2, MK = D2s[cur_par[0]], MASKs[cur_par[0]]
-            if xpred is None:
-                ops.conv2d_pair(flow_pred_r.args(Chan(HEAD, 0, fh), Chan.whole(D2), N, h, w),
-                                mask_pred_r.args(Chan(HEAD, fh, mh), Chan.whole(MK), N, h, w), HEAD)
-            run_chain_pair(self.delta_flow_encoder, Chan.whole(D2), Chan(FM, 0, dfc),
-                           self.mask_encoder, Chan.whole(MK), Chan(FM, dfc, mfc), N, h, w, s_dfe,
-                           s_me)
-
-        def seg_flow_pred():
-            D2 = D2s[cur_par[0]]
-            if xpred is None:
-                flow_pred_r.run(Chan(HEAD, 0, fh), Chan.whole(D2), N, h, w)
-            run_chain(self.delta_flow_encoder, Chan.whole(D2), Chan(FM, 0, dfc), N, h, w, s_dfe,
-                      hooks=self._hooks_for(None, "dflow1"))
-
-        pose_x = []
-        tail_calls = None  # fused tail: per-iteration (heads, pose_step) launches, built once
-        defer = fuse_tail and self.defer_full_res and iters > 1
-        # Δflow alternates between two buffers when the full-resolution outputs are deferred: the
-        # previous iteration's deferred launch reads its Δflow on the side stream while this
-        # iteration's flow predictor writes the other one on the main stream
-        D2s = [D2, torch.empty_like(D2)] if defer else [D2, D2]
-        # the mask likewise (read by the previous iteration's deferred launch on the side stream
-        # while this iteration's mask predictor writes the other one — on the main stream when
-        # the tail is paired)
-        MASKs = [MASK, torch.empty_like(MASK)] if defer else [MASK, MASK]
-        pt = self.pair_tail if self.pair_tail >= 0 else int(h * w <= 32 * 32)
-        pair_tail = bool(pt) and len(self.delta_flow_encoder) == len(self.mask_encoder)
-        # last_plan's keys (the mask flags do not change it)
-        self._last_plan = dict(fuse_tail=bool(fuse_tail), defer=bool(defer),
-                               pair_tail=bool(pair_tail), fuse_lc=core.fuse_lc, tiled=core.tiled,
-                               side_stream=bool(two))
-        if masked:
-            MASKs[1].fill_(1.0)  # before the first prediction: interpolate(ones, 1/8) == ones
-        # Masked plan, paired tail + deferred outputs: nothing on the main stream orders the tail
-        # of iteration i (which writes F2s[(i+1)%2]) after the side stream's deferred launch of
-        # iteration i−1 (which reads that buffer as its ↓8 flow) — no join sits between them when
-        # the tail is paired.  The masked plan orders the two with an event of its own.
-        ev_full = None
-        if masked and defer and pair_tail and two:
-            if self.device_scope_events:
-                ev_full = self._sync_events(dev, (slot, "full"))[0]
-                h_main, h_side = main.cuda_stream, side.cuda_stream
-            else:
-                ev_full = torch.cuda.Event()
-        cur_par = [0]
-        pending = []  # the previous iteration's deferred full-resolution launches
-        if defer:  # the deferred launches' pose outputs (duplicates of o_R / o_t: not read)
-            R_scr = torch.empty(N, 3, 3, device=dev, dtype=f32)
-            t_scr = torch.empty(N, 3, device=dev, dtype=f32)
-
-        def seg_pose_trunk():
-            pose_x.append(self.pose_pred.trunk_hip(hid, Chan.whole(FM), N, h, w, ws=keep))
-
-        for it in range(iters):
-            par = f"{it % 2}" if fuse_tail else ""
-            F2 = F2s[it % 2]
-            flow_in = FLMs[it % 2]
-            if masked:  # the mask iteration it−1 predicted (ones before the first)
-                mask_prev = MASKs[(it - 1) % 2]
-            # a11 ↓: flow at feature resolution → F2 (and the motion-feature flow channels, times
-            # the mask under mask_flow); the fused tail of the previous iteration already wrote it
-            if not fuse_tail or it == 0:
-                if self.mask_flow:
-                    ops.flow_downsample(flow_full, Chan.whole(F2), h, w, 1.0 / scale, out1=hx_flow,
-                                        mask=mask_prev, outm=Chan.whole(flow_in))
-                else:
-                    ops.flow_downsample(flow_full, Chan.whole(F2), h, w, 1.0 / scale, out1=hx_flow)
-            if pp is not None:
-                pp[0](it)
-            # a3 (flow branch) on the side stream
-            fork()
-            with torch.cuda.stream(side):
-                core.flow_branch(par, flow_in)
-            # a2 + a3 (correlation branch)
-            core.correlation(par, F2, mask_prev if self.mask_corr else None)
-            join()
-            if pending:
-                # the previous iteration's full-resolution outputs on the side stream AFTER the
-                # join's record: they overlap out_net and the GRU (MFMA-bound) instead of
-                # lengthening a joined branch; the mask branch queued behind them reads MASK after
-                # they do, and Δflow / F2 are double-buffered against this iteration's writes
-                with torch.cuda.stream(side):
-                    self._hook("pose_flow", True)
-                    for c in pending:
-                        c()
-                    self._hook("pose_flow", False)
-                    if ev_full is not None:
-                        if self.device_scope_events:
-                            ev_full.record(h_side)
-                        else:
-                            ev_full.record(side)
-                pending = []
-            core.motion_out()
-            # a4 GRU (in place on HX[:, :hc])
-            core.gru(self.kernel_hooks)
-            # a5 heads (with xpred: the predictors too, into this iteration's Δflow / mask)
-            cur_par[0] = it % 2 if defer else 0
-            self._hook("heads", True)
-            segment("heads" + (par if xpred is not None and defer else ""), seg_heads)
-            self._hook("heads", False)
-            if pp is not None:
-                pp[1](it)
-            yield "heavy"
-            if pair_tail:
-                # flow predictor + Δflow encoder ‖ mask predictor + mask encoder (a5, a6) as
-                # paired launches on this stream
-                segment("tail_pair" + (par if defer else ""), seg_tail_pair)
-            else:
-                # mask predictor + mask encoder (a5, a6) on the side stream, after the previous
-                # iteration's deferred full-resolution outputs (they read its MASK; the side
-                # branch is the shorter one here)
-                fork()
-                with torch.cuda.stream(side):
-                    segment("mask_branch" + (par if defer else ""), seg_mask_branch)
-                # flow predictor + Δflow encoder (into this iteration's Δflow buffer)
-                segment("flow_pred" + (par if defer else ""), seg_flow_pred)
-                join()
-            # a7 pose head on cat[h, Δflow feat, mask feat] (two channel sources, no concat)
-            segment("pose_trunk", seg_pose_trunk)
-            drot, dtr = o_drot[it], o_dt[it]
-            if fuse_tail:
-                # a8 + a10 + a11 ↑ (+ the next iteration's a11 ↓): one launch.  The heads and
-                # this launch take per-iteration pointers; their argument lists for every
-                # iteration are built once (after the trunk's first pass) and replayed as one
-                # ctypes call each, like the recorded segments
-                if tail_calls is None:
-                    tail_calls = []
-                    Rp, tp = R_prev, t_prev
-                    for j in range(iters):
-                        last = j == iters - 1
-                        hc, pc, fc = [], [], []
-                        step = (o_drot[j], o_dt[j], Rp, tp, K, points, o_R[j], o_t[j],
-                                o_flow_pose[j], invalid, F2s[j % 2], D2s[j % 2], MASKs[j % 2], o_flow_pred[j],
-                                o_mask[j], h, w, float(scale))
-                        nxt = dict(lr_next=None if last else Chan.whole(F2s[(j + 1) % 2]),
-                                   hx_next=None if last else hx_flow,
-                                   depth_transform=self.depth_transform)
-                        if self.mask_flow and not last:  # the next iteration's masked ↓8 flow
-                            nxt.update(mask_next=MASKs[j % 2],
-                                       lrm_next=Chan.whole(FLMs[(j + 1) % 2]))
-                        # the rotation / translation heads inside the pose step's launch
-                        # (scflow_pose_step_heads), or as their own launch before it
-                        ha = self.pose_pred.heads_args(pose_x[0], label) if self.fuse_heads else None
-                        if ha is None:
-                            with ops.binding(hc, run=False):
-                                self.pose_pred.heads_hip(pose_x[0], label, o_drot[j], o_dt[j])
-                        else:
-                            nxt["heads"] = ha
-                        if defer and not last:
-                            with ops.binding(pc, run=False):
-                                ops.pose_step(*step, **nxt, parts=2)
-                            with ops.binding(fc, run=False):
-                                if self.fullres_given:
-                                    ops.pose_step_given(o_R[j], o_t[j], *step[4:6], *step[8:])
-                                else:  # (reads the deltas the ↓8 launch wrote)
-                                    fstep = step[:6] + (R_scr, t_scr) + step[8:]
-                                    ops.pose_step(*fstep, parts=1,
-                                                  **{k: v for k, v in nxt.items()
-                                                     if k not in ("heads", "mask_next", "lrm_next")})
-                        else:
-                            with ops.binding(pc, run=False):
-                                ops.pose_step(*step, **nxt)
-                        tail_calls.append((hc, pc, fc))
-                        Rp, tp = o_R[j], o_t[j]
-                hc, pc, fc = tail_calls[it]
-                for c in hc:
+    # ------------------------------------------------------------------ the two phases
+    def heavy(self, it: int) -> None:
+        """The ↓8 flow through the heads: the phase whose convolutions fill the chip."""
+        dec, core, st = self.dec, self.core, self.st
+        dec._hooks_on = self.hooks
+        self.par = it % 2
+        sfx = str(self.par) if self.fuse_tail else ""  # recorded once per F2 buffer
+        F2, flow_in = _at(self.F2s, it), _at(self.FLMs, it)
+        # the mask iteration it−1 predicted (ones before the first)
+        mask_prev = _at(self.MASKs, it - 1) if self.masked else None
+        # a11 ↓: flow at feature resolution → F2 (and the motion-feature flow channels, times
+        # the mask under mask_flow); the fused tail of the previous iteration already wrote it
+        if not self.fuse_tail or it == 0:
+            masked = dict(mask=mask_prev, outm=Chan.whole(flow_in)) if dec.mask_flow else {}
+            ops.flow_downsample(self.flow_full, Chan.whole(F2), self.h, self.w, 1.0 / self.scale,
+                                out1=core.hx_flow, **masked)
+        if self.pp is not None:
+            self.pp[0](it)
+        # a3 (flow branch) on the side stream ‖ a2 + a3 (correlation branch)
+        st.fork()
+        with torch.cuda.stream(st.side):
+            core.flow_branch(sfx, flow_in)
+        core.correlation(sfx, F2, mask_prev if dec.mask_corr else None)
+        st.join()
+        if self.pending:
+            # the previous iteration's full-resolution outputs on the side stream AFTER the
+            # join's record: they overlap out_net and the GRU (MFMA-bound) instead of
+            # lengthening a joined branch (what orders their inputs: see tail)
+            with torch.cuda.stream(st.side):
+                dec._hook("pose_flow", True)
+                for c in self.pending:
                     c()
-                if ev_full is not None and it > 0:  # after iteration it−1's deferred launch
-                    if self.device_scope_events:
-                        ev_full.wait(h_main)
-                    else:
-                        main.wait_event(ev_full)
-                # deferred: this is the critical-path ↓8 launch (its own timer); otherwise the
-                # whole pose step
-                hook = "pose_step_crit" if fc else "pose_flow"
-                self._hook(hook, True)
-                for c in pc:
-                    c()
-                self._hook(hook, False)
-                if self.kernel_hooks:  # measurement only: bench.py times a launch alone
-                    self._tail_calls = tail_calls
-                # (dbg_skip_fullres: measurement only — drops the deferred full-resolution
-                # outputs to price their side-stream contention; outputs are then incomplete)
-                pending = [] if self.dbg_skip_fullres else fc
-            else:
-                self.pose_pred.heads_hip(pose_x[0], label, drot, dtr)
-                # a11 ↑: flow_pred = 8·up(flow + Δflow), mask ↑
-                ops.flow_upsample(F2, D2s[0], MASKs[0], N, h, w, H, W, float(scale), o_flow_pred[it],
-                                  o_mask[it])
-                # a8 + a10: pose update + pose-induced flow (one launch)
-                self._hook("pose_flow", True)
-                ops.pose_update_flow(drot, dtr, R_prev, t_prev, K, points, o_R[it], o_t[it],
-                                     o_flow_pose[it], invalid, depth_transform=self.depth_transform)
-                self._hook("pose_flow", False)
-            R_prev, t_prev = o_R[it], o_t[it]
-            flow_full = o_flow_pose[it]
-            drots.append(drot)
-            dts.append(dtr)
-            yield "tail"
-        if pair_tail:
-            # with the tail paired on the main stream the side stream's last work (the deferred
-            # full-resolution outputs queued in the last iteration) is not joined inside the loop
-            join()
+                dec._hook("pose_flow", False)
+                if self.mark:
+                    st.mark_side()
+            self.pending = []
+        core.motion_out()
+        core.gru(dec.kernel_hooks)  # a4, in place on HX[:, :hc]
+        # a5 heads (with xpred: the predictors too, into this iteration's Δflow / mask)
+        dec._hook("heads", True)
+        core.segment("heads" + (sfx if self.xpred is not None and self.defer else ""), self.seg_heads)
+        dec._hook("heads", False)
+        if self.pp is not None:
+            self.pp[1](it)
 
-        return (list(o_flow_pose.unbind(0)), list(o_flow_pred.unbind(0)), list(o_R.unbind(0)),
-                list(o_t.unbind(0)), list(o_mask.unbind(0)), drots, dts)
+    def tail(self, it: int) -> None:
+        """The tail branches through the pose step: many small, latency-bound launches.
+
+        Deferred outputs: iteration j's deferred launch is queued on the side stream in
+        heavy(j+1), behind its join, and reads F2s[j % 2], D2s[j % 2] and MASKs[j % 2] (the flow
+        branch, earlier on that stream, read FLMs[j % 2]).  Each one's next writer is ordered
+        after it.  F2s / FLMs[j % 2]: iteration j+1's pose step on the main stream (its
+        lr_next / lrm_next) — the unpaired tail's join precedes it; under the paired tail no join
+        does, so heavy(j+1) marks the side stream after the deferred launch and the pose step
+        waits for that mark.  D2s / MASKs[j % 2]: iteration j+2's predictors, on the main stream
+        after heavy(j+2)'s join, or (unpaired mask branch) on the side stream itself."""
+        dec, core, st, out = self.dec, self.core, self.st, self.out
+        dec._hooks_on = self.hooks
+        sfx = str(self.par) if self.defer else ""  # recorded once per Δflow / mask buffer
+        if self.pair_tail:
+            # flow predictor + Δflow encoder ‖ mask predictor + mask encoder (a5, a6) as paired
+            # launches on this stream
+            core.segment("tail_pair" + sfx, self.seg_tail_pair)
+        else:
+            # mask predictor + mask encoder on the side stream (the shorter branch), flow
+            # predictor + Δflow encoder on this one
+            st.fork()
+            with torch.cuda.stream(st.side):
+                core.segment("mask_branch" + sfx, self.seg_mask_branch)
+            core.segment("flow_pred" + sfx, self.seg_flow_pred)
+            st.join()
+        # a7 pose head on cat[h, Δflow feat, mask feat] (two channel sources, no concat)
+        core.segment("pose_trunk", self.seg_pose_trunk)
+        if self.fuse_tail:
+            # a8 + a10 + a11 ↑ (+ the next iteration's a11 ↓): one launch, replayed from the
+            # calls built after the trunk's first pass
+            if self.tail_calls is None:
+                self.tail_calls = self.build_tail_calls()
+            hc, pc, fc = self.tail_calls[it]
+            for c in hc:
+                c()
+            if self.mark and it > 0:  # after iteration it−1's deferred launch
+                st.wait_side_mark()
+            # deferred: this is the critical-path ↓8 launch (its own timer); otherwise the
+            # whole pose step
+            hook = "pose_step_crit" if fc else "pose_flow"
+            dec._hook(hook, True)
+            for c in pc:
+                c()
+            dec._hook(hook, False)
+            if dec.kernel_hooks:  # measurement only: bench.py times a launch alone
+                dec._tail_calls = self.tail_calls
+            self.pending = fc
+        else:
+            dec.pose_pred.heads_hip(self.pose_x, self.label, out["drot"][it], out["dt"][it])
+            # a11 ↑: flow_pred = 8·up(flow + Δflow), mask ↑
+            ops.flow_upsample(_at(self.F2s, it), self.D2s[0], self.MASKs[0], self.N, self.h, self.w,
+                              self.H, self.W, float(self.scale), out["flow_pred"][it], out["mask"][it])
+            # a8 + a10: pose update + pose-induced flow (one launch)
+            dec._hook("pose_flow", True)
+            ops.pose_update_flow(out["drot"][it], out["dt"][it], self.R_prev, self.t_prev, self.K,
+                                 self.points, out["R"][it], out["t"][it], out["flow_pose"][it],
+                                 self.invalid, depth_transform=dec.depth_transform)
+            dec._hook("pose_flow", False)
+            # (the fused tail's launches hold every iteration's pointers already)
+            self.R_prev, self.t_prev = out["R"][it], out["t"][it]
+            self.flow_full = out["flow_pose"][it]
+
+    def finish(self) -> None:
+        """With the tail paired on the main stream the side stream's last work (the deferred
+        full-resolution outputs queued in the last iteration) is not joined inside the loop."""
+        if self.pair_tail:
+            self.st.join()
+
+    def lists(self):
+        return _lists(self.out)
+
+    # ------------------------------------------------------------------ the recorded segments
+    def seg_heads(self):
+        dec, core = self.dec, self.core
+        if self.xpred is not None:  # hidden conv + both predictors → Δflow, mask
+            hargs, pw, xws, fb, mb, fh_ = self.xpred
+            ops.xhead_pred(hargs, fh_, pw, xws, fb, mb, None, "Sigmoid",
+                           Chan.whole(_at(self.D2s, self.par)), Chan.whole(_at(self.MASKs, self.par)))
+        elif self.head_runner is not None:
+            self.head_runner.run(core.hid, Chan.whole(self.HEAD), self.N, self.h, self.w)
+        else:
+            run_chain(dec.flow_pred.layers, core.hid, Chan(self.HEAD, 0, self.fh), self.N, self.h, self.w)
+            run_chain(dec.mask_pred.layers, core.hid, Chan(self.HEAD, self.fh, self.mh), self.N,
+                      self.h, self.w)
+
+    def seg_mask_branch(self):
+        N, h, w, MK = self.N, self.h, self.w, _at(self.MASKs, self.par)
+        if self.xpred is None:
+            self.mask_pred_r.run(Chan(self.HEAD, self.fh, self.mh), Chan.whole(MK), N, h, w)
+        run_chain(self.dec.mask_encoder, Chan.whole(MK), Chan(self.FM, self.dfc, self.mfc), N, h, w,
+                  self.s_me, hooks=self.dec._hooks_for(None, "mask_enc1"))
+
+    def seg_tail_pair(self):
+        # the flow-predictor and mask-predictor branches on the main stream, their k-th
+        # launches paired into one grid each (scflow_conv2d_pair): no fork / join events
+        N, h, w, HEAD, FM = self.N, self.h, self.w, self.HEAD, self.FM
+        D2, MK = _at(self.D2s, self.par), _at(self.MASKs, self.par)
+        if self.xpred is None:
+            ops.conv2d_pair(
+                self.flow_pred_r.args(Chan(HEAD, 0, self.fh), Chan.whole(D2), N, h, w),
+                self.mask_pred_r.args(Chan(HEAD, self.fh, self.mh), Chan.whole(MK), N, h, w), HEAD)
+        run_chain_pair(self.dec.delta_flow_encoder, Chan.whole(D2), Chan(FM, 0, self.dfc),
+                       self.dec.mask_encoder, Chan.whole(MK), Chan(FM, self.dfc, self.mfc), N, h, w,
+                       self.s_dfe, self.s_me)
+
+    def seg_flow_pred(self):
+        N, h, w, D2 = self.N, self.h, self.w, _at(self.D2s, self.par)
+        if self.xpred is None:
+            self.flow_pred_r.run(Chan(self.HEAD, 0, self.fh), Chan.whole(D2), N, h, w)
+        run_chain(self.dec.delta_flow_encoder, Chan.whole(D2), Chan(self.FM, 0, self.dfc), N, h, w,
+                  self.s_dfe, hooks=self.dec._hooks_for(None, "dflow1"))
+
+    def seg_pose_trunk(self):
+        self.pose_x = self.dec.pose_pred.trunk_hip(self.core.hid, Chan.whole(self.FM), self.N,
+                                                   self.h, self.w, ws=self.keep)
+
+    def build_tail_calls(self):
+        """The fused tail's launches for every iteration, one (heads, pose step, deferred
+        full-resolution) tuple of call lists each: they take per-iteration pointers, so their
+        argument structs are built once (after the trunk's first pass) and replayed."""
+        dec, out, iters = self.dec, self.out, self.iters
+        F2s, FLMs, D2s, MASKs = self.F2s, self.FLMs, self.D2s, self.MASKs
+        calls = []
+        Rp, tp = self.R_prev, self.t_prev
+        for j in range(iters):
+            last = j == iters - 1
+            hc, pc, fc = [], [], []
+            step = (out["drot"][j], out["dt"][j], Rp, tp, self.K, self.points, out["R"][j],
+                    out["t"][j], out["flow_pose"][j], self.invalid, _at(F2s, j), _at(D2s, j),
+                    _at(MASKs, j), out["flow_pred"][j], out["mask"][j], self.h, self.w,
+                    float(self.scale))
+            nxt = dict(lr_next=None if last else Chan.whole(_at(F2s, j + 1)),
+                       hx_next=None if last else self.core.hx_flow,
+                       depth_transform=dec.depth_transform)
+            if dec.mask_flow and not last:  # the next iteration's masked ↓8 flow
+                nxt.update(mask_next=_at(MASKs, j), lrm_next=Chan.whole(_at(FLMs, j + 1)))
+            # the rotation / translation heads inside the pose step's launch
+            # (scflow_pose_step_heads), or as their own launch before it
+            ha = dec.pose_pred.heads_args(self.pose_x, self.label) if dec.fuse_heads else None
+            if ha is None:
+                with ops.binding(hc, run=False):
+                    dec.pose_pred.heads_hip(self.pose_x, self.label, out["drot"][j], out["dt"][j])
+            else:
+                nxt["heads"] = ha
+            if self.defer and not last:
+                with ops.binding(pc, run=False):
+                    ops.pose_step(*step, **nxt, parts=2)
+                with ops.binding(fc, run=False):
+                    if dec.fullres_given:
+                        ops.pose_step_given(out["R"][j], out["t"][j], *step[4:6], *step[8:])
+                    else:  # (reads the deltas the ↓8 launch wrote)
+                        fstep = step[:6] + (self.R_scr, self.t_scr) + step[8:]
+                        ops.pose_step(*fstep, parts=1,
+                                      **{k: v for k, v in nxt.items()
+                                         if k not in ("heads", "mask_next", "lrm_next")})
+            else:
+                with ops.binding(pc, run=False):
+                    ops.pose_step(*step, **nxt)
+            calls.append((hc, pc, fc))
+            Rp, tp = out["R"][j], out["t"][j]
+        return calls

@@ -124,13 +124,19 @@ def test_masked_decoder_schedules_bit_identical():
     assert not torch.equal(plain[0][-1], base[0][-1])
 
 
-def test_masked_decoder_side_stream_delay():
-    """The masked default plan with the side stream held back by ordinary work queued first on it
-    (a large correlation pyramid on scratch inputs): the same bits as the undelayed run — every
-    buffer the masked plan adds is ordered by an event or is a buffer of its own."""
+@pytest.mark.parametrize("flags", [(False, False), (True, True)])
+def test_masked_decoder_side_stream_delay(flags):
+    """The default plan, unmasked and with both mask flags, with every deferred full-resolution
+    launch held back on the side stream by ordinary work queued right before it (the "pose_flow"
+    hook fires there: two large correlation pyramids on scratch inputs, milliseconds) while the
+    main stream runs on into the next pose step: the same bits as the undelayed run — every
+    buffer a deferred launch reads is ordered against its next writer by an event or is a buffer
+    of its own.  (The unmasked case also passed before the unmasked plan had its mark / wait:
+    the delaying GEMMs fill every CU, so the main stream does not get far ahead of them either.
+    That ordering rests on the code and tests/test_decoder_streams.py.)"""
     from scflow_amd import ops
     inp = decoder_inputs(2, 256, seed=13)
-    dec = masked_decoder(4, seed=4).cuda()
+    dec = masked_decoder(4, flags, seed=4).cuda()
     base = run_gpu(dec, inp)
     assert dec.last_plan["side_stream"] and dec.last_plan["defer"] and dec.last_plan["pair_tail"]
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -139,8 +145,21 @@ def test_masked_decoder_side_stream_delay():
     f1 = torch.randn(8, 256, 64, 64, generator=g).cuda()
     f2 = torch.randn(8, 256, 64, 64, generator=g).cuda()
     torch.cuda.synchronize()
-    with torch.cuda.stream(side):
-        for _ in range(4):
-            ops.corr_pyramid(f1, f2, 4)
-    out = run_gpu(dec, inp)
-    _equal_lists(base, out, "delayed side stream")
+    fired = []
+
+    def delay(start):
+        if start:
+            fired.append(torch.cuda.current_stream(dev) == side)
+            for _ in range(2):
+                ops.corr_pyramid(f1, f2, 4)
+
+    dec.kernel_hooks["pose_flow"] = delay
+    try:
+        out = run_gpu(dec, inp)
+    finally:
+        dec.kernel_hooks.clear()
+    # on the side stream before each deferred launch (iterations 0-2); the last iteration's whole
+    # pose step carries the same hook on the main stream
+    assert fired == [True] * 3 + [False]
+    assert dec.last_plan["side_stream"] and dec.last_plan["defer"] and dec.last_plan["pair_tail"]
+    _equal_lists(base, out, f"delayed side stream, flags {flags}")
