@@ -256,6 +256,31 @@ int scflow_conv_pack_weights(const float* w_oihw, float* packed, int cout, int c
  * 8 when the grid needs more resident workgroups than 16-deep stages' LDS allows, else 16. */
 int scflow_conv_pick_bk(const scflow_conv_args* args);
 int scflow_conv2d(const scflow_conv_args* args, void* stream);
+/* Host-only query of the launch plan (no launch, no device access, src / weight / out are never
+ * dereferenced).  b NULL: *kind = the kernel family scflow_conv2d launches for a (SCFLOW_PLAN_*,
+ * SCFLOW_PLAN_NONE if refused); returns the status scflow_conv2d answers before launching.
+ * b non-NULL: *kind = the grouped kernel scflow_conv2d_pair launches for the two in either order
+ * (SCFLOW_PAIR_*, SCFLOW_PAIR_NONE: two launches); returns the status scflow_conv2d_pair answers
+ * before launching (an invalid half refuses the pair). */
+int scflow_conv_plan_kind(const scflow_conv_args* a, const scflow_conv_args* b, int* kind);
+#define SCFLOW_PLAN_NONE 0
+#define SCFLOW_PLAN_MFMA 1              /* direct implicit-GEMM conv (conv_mfma_kernel)          */
+#define SCFLOW_PLAN_1X1 2               /* conv1x1_kernel: 1×1 on 128-pixel tiles                */
+#define SCFLOW_PLAN_1X1W 3              /* wide 1×1 (SCFLOW_CONV_1X1W)                           */
+#define SCFLOW_PLAN_WINO 4              /* Winograd F(2×2,3×3)                                   */
+#define SCFLOW_PLAN_WINO5 5             /* Winograd F(4,5), 1×5 / 5×1                            */
+#define SCFLOW_PLAN_WINO4 6             /* Winograd F(4×4,3×3): transform + GEMM launches        */
+#define SCFLOW_PLAN_SMALLCIN_MFMA 7     /* cin ≤ 2 on MFMA, whole rows of 32 / 64 pixels         */
+#define SCFLOW_PLAN_SMALLCIN_TILED 8    /* cin ≤ 2, one lane per output channel, 32-pixel tiles  */
+#define SCFLOW_PLAN_SMALLCIN_GENERIC 9  /* cin ≤ 4, any shape                                    */
+#define SCFLOW_PLAN_THINZ 10            /* cout ≤ 2: 3×3 256-channel contraction on MFMA         */
+#define SCFLOW_PLAN_THIN_FULL 11        /* cout ≤ 2: 3×3, the whole halo in LDS                  */
+#define SCFLOW_PLAN_THIN_CHUNKED 12     /* cout ≤ 2: halo in 32-channel chunks                   */
+#define SCFLOW_PLAN_THIN_GENERIC 13     /* cout ≤ 4, any shape                                   */
+#define SCFLOW_PAIR_NONE 0
+#define SCFLOW_PAIR_THIN 1              /* THINZ (cout 2) beside THIN_CHUNKED 1×1 (cout 1)       */
+#define SCFLOW_PAIR_SMALLCIN 2          /* SMALLCIN_MFMA 7×7 2→128 beside 3×3 1→64               */
+#define SCFLOW_PAIR_WINO 3              /* two WINO convs of one width (32 or 64)                */
 
 /* a8: R_dst = R(ortho6d Δ)·R_src; t_z' = t_z/exp(Δt_z) (depth_transform 0) or t_z·(Δt_z+1) (1);
  * t_xy' = t_z'·(Δt_xy/weight + t_xy/t_z).  drot6 [n][6], dt [n][3], R [n][3][3], t [n][3]. */

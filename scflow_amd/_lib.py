@@ -22,6 +22,11 @@ EPI_PLAIN, EPI_GRU_ZR, EPI_GRU_Q = 0, 1, 2
 CONV_WINO = 2  # scflow_conv_args.bk: Winograd F(2x2,3x3) packing/kernel (SCFLOW_CONV_WINO)
 CONV_1X1W = 3  # scflow_conv_args.bk: wide 1x1 packing/kernel (SCFLOW_CONV_1X1W)
 CONV_WINO4 = 4  # scflow_conv_args.bk: Winograd F(4x4,3x3) packing/kernel (SCFLOW_CONV_WINO4)
+# scflow_conv_plan_kind: SCFLOW_PLAN_* (one conv's kernel family) and SCFLOW_PAIR_* (grouped kernel)
+(PLAN_NONE, PLAN_MFMA, PLAN_1X1, PLAN_1X1W, PLAN_WINO, PLAN_WINO5, PLAN_WINO4, PLAN_SMALLCIN_MFMA,
+ PLAN_SMALLCIN_TILED, PLAN_SMALLCIN_GENERIC, PLAN_THINZ, PLAN_THIN_FULL, PLAN_THIN_CHUNKED,
+ PLAN_THIN_GENERIC) = range(14)
+PAIR_NONE, PAIR_THIN, PAIR_SMALLCIN, PAIR_WINO = range(4)
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 ABI_VERSION = 4  # SCFLOW_ABI_VERSION of include/scflow_hip.h this binding mirrors
 PNP_MAX_HYPS = 256  # SCFLOW_PNP_MAX_HYPS
@@ -156,6 +161,8 @@ SIGNATURES = {
     "scflow_conv_workspace_bytes": (ctypes.c_longlong, [ctypes.POINTER(ConvArgs)]),
     "scflow_conv2d": (c_int, [ctypes.POINTER(ConvArgs), c_vp]),
     "scflow_conv2d_pair": (c_int, [ctypes.POINTER(ConvArgs), ctypes.POINTER(ConvArgs), c_vp]),
+    "scflow_conv_plan_kind": (c_int, [ctypes.POINTER(ConvArgs), ctypes.POINTER(ConvArgs),
+                                      ctypes.POINTER(c_int)]),
     "scflow_xhead_pred_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int, c_int]),
     "scflow_xhead_pred": (c_int, [ctypes.POINTER(ConvArgs), c_int, c_vp, c_vp, c_ll, c_vp, c_vp, c_int,
                                   c_int, c_vp, c_int, c_vp, c_int, c_vp]),

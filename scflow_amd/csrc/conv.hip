@@ -1046,8 +1046,6 @@ int wino_swz(int R, int C) {
   return c;
 }
 
-// profiling: where the next F(2×2,3×3) Winograd launches write their per-workgroup stamps
-
 #include "conv_wino4.h"
 
 // F(4×4,3×3) (conv_wino4.h) for the 3×3 convs it covers with at least WINO4_MIN_COUT output
@@ -1080,72 +1078,60 @@ bool wino4_pick(const scflow_conv_args& a) {
   return a.cout >= WINO4_MIN_COUT_MULTI && wgs > 2LL * device_cus();
 }
 
+// What scflow_conv2d does with one argument struct: decided once by plan_conv, carried out by
+// launch_plan, and paired by scflow_conv2d_pair (conv_pair.h).  The instantiation's key is tm /
+// bks / nbw here plus a's own kh, kw, c0, cout, epilogue and the width ow, all of which the kind
+// restricts to instantiated values.  lds is the launch's dynamic LDS where that depends on the
+// arguments; the Winograd and wide 1×1 kernels' is a constant of the instantiation.
+struct ConvPlan {
+  int status, kind;  // the error scflow_conv2d answers before launching (or SCFLOW_OK); SCFLOW_PLAN_*
+  int tm, bks, nbw;  // pixel tile and stage depth (direct conv); 32-channel blocks per workgroup
+  unsigned gx, gy;
+  size_t lds;
+  int oh, ow, tr, hr, hc, cp0, nst, npad, ntiles;  // what the kernel's parameters need
+};
 
+// one launch of Kernel on the plan's grid
+template <auto Kernel, int THREADS = 256, class... Args>
+int launch_k(const ConvPlan& c, size_t lds, hipStream_t st, const Args&... args) {
+  allow_big_lds<Kernel>(lds);
+  Kernel<<<dim3(c.gx, c.gy), THREADS, lds, st>>>(args...);
+  return scflow_launch_status();
+}
+
+// The Winograd and wide 1×1 plans' instantiations (launch_plan's cases for them).  They stand
+// ahead of conv_pair.h and xhead_pred.h because device code is emitted in the order of first use
+// and the library's code object is kept byte-identical across host-side changes.
 template <int W, int NBW>
-int launch_wino_w(WinoParams p, hipStream_t st) {
-  using G = WinoGeom<W>;
-  const size_t lds = wino_lds_bytes<W, NBW>();
-  allow_big_lds<conv_wino_kernel<W, NBW>>(lds);
-  dim3 grid(p.a.n * (p.a.h / G::OROWS) * G::XB, round_up(p.a.cout, 32 * NBW) / (32 * NBW));
-  p.swz_c = wino_swz(grid.x, grid.y);
-  p.stamps = g_wino_stamps;
-  conv_wino_kernel<W, NBW><<<grid, 256, lds, st>>>(p);
-  return scflow_launch_status();
+int launch_wino_k(const ConvPlan& c, const WinoParams& p, hipStream_t st) {
+  return launch_k<conv_wino_kernel<W, NBW>>(c, wino_lds_bytes<W, NBW>(), st, p);
 }
-
-template <int DIR, int W, int NBW, int EPI>
-int launch_wino5_k(Wino5Params p, hipStream_t st) {
-  using G = Wino5Geom<DIR, W>;
-  const size_t lds = wino5_lds_bytes<DIR, W, NBW>();
-  allow_big_lds<conv_wino5_kernel<DIR, W, NBW, EPI>>(lds);
-  dim3 grid(p.a.n * (p.a.h / G::OROWS) * (W / G::OCOLS), round_up(p.a.cout, 32 * NBW) / (32 * NBW));
-  p.swz_c = wino_swz(grid.x, grid.y);
-  p.stamps = g_wino_stamps;
-  conv_wino5_kernel<DIR, W, NBW, EPI><<<grid, 256, lds, st>>>(p);
-  return scflow_launch_status();
+template <int EPI, int DIR, int W>
+int launch_wino5_k(const ConvPlan& c, const Wino5Params& p, hipStream_t st) {
+  return c.nbw == 2
+             ? launch_k<conv_wino5_kernel<DIR, W, 2, EPI>>(c, wino5_lds_bytes<DIR, W, 2>(), st, p)
+             : launch_k<conv_wino5_kernel<DIR, W, 1, EPI>>(c, wino5_lds_bytes<DIR, W, 1>(), st, p);
 }
-
 template <int EPI>
-int launch_wino5_epi(const Wino5Params& p, int nbw, hipStream_t st) {
-  const bool x = p.a.kh == 1;
-  if (p.a.w == 32) {
-    if (x) return nbw == 2 ? launch_wino5_k<0, 32, 2, EPI>(p, st) : launch_wino5_k<0, 32, 1, EPI>(p, st);
-    return nbw == 2 ? launch_wino5_k<1, 32, 2, EPI>(p, st) : launch_wino5_k<1, 32, 1, EPI>(p, st);
-  }
-  if (x) return nbw == 2 ? launch_wino5_k<0, 64, 2, EPI>(p, st) : launch_wino5_k<0, 64, 1, EPI>(p, st);
-  return nbw == 2 ? launch_wino5_k<1, 64, 2, EPI>(p, st) : launch_wino5_k<1, 64, 1, EPI>(p, st);
+int launch_wino5(const ConvPlan& c, const Wino5Params& p, hipStream_t st) {
+  if (c.ow == 32)
+    return p.a.kh == 1 ? launch_wino5_k<EPI, 0, 32>(c, p, st) : launch_wino5_k<EPI, 1, 32>(c, p, st);
+  return p.a.kh == 1 ? launch_wino5_k<EPI, 0, 64>(c, p, st) : launch_wino5_k<EPI, 1, 64>(c, p, st);
 }
-
-int launch_wino(const scflow_conv_args& a, hipStream_t st) {
-  if (!wino_launchable(a)) return SCFLOW_EUNSUPPORTED;
-  if (!aligned16(a.src0) || (a.s0 & 3) || (a.c1 > 0 && (!aligned16(a.src1) || (a.s1 & 3))) ||
-      !aligned16(a.weight))
-    return SCFLOW_EALIGN;
-  if (a.kh != 3) {
-    Wino5Params p;
-    p.a = a;
-    p.cp0 = round_up(a.c0, W5SC);
-    p.nst = (p.cp0 + round_up(a.c1, W5SC)) / W5SC;
-    const int nbw = wino_nbw(a, device_cus());
-    switch (a.epilogue) {
-      case SCFLOW_EPI_GRU_ZR: return launch_wino5_epi<SCFLOW_EPI_GRU_ZR>(p, nbw, st);
-      case SCFLOW_EPI_GRU_Q: return launch_wino5_epi<SCFLOW_EPI_GRU_Q>(p, nbw, st);
-      default: return launch_wino5_epi<SCFLOW_EPI_PLAIN>(p, nbw, st);
-    }
+int launch_wino(const scflow_conv_args& a, const ConvPlan& c, hipStream_t st) {
+  if (c.kind == SCFLOW_PLAN_WINO5) {
+    const Wino5Params p{a, c.cp0, c.nst, wino_swz(c.gx, c.gy), g_wino_stamps};
+    if (a.epilogue == SCFLOW_EPI_GRU_ZR) return launch_wino5<SCFLOW_EPI_GRU_ZR>(c, p, st);
+    if (a.epilogue == SCFLOW_EPI_GRU_Q) return launch_wino5<SCFLOW_EPI_GRU_Q>(c, p, st);
+    return launch_wino5<SCFLOW_EPI_PLAIN>(c, p, st);
   }
-  WinoParams p;
-  p.a = a;
-  p.cp0 = round_up(a.c0, WSC);
-  p.nst = (p.cp0 + round_up(a.c1, WSC)) / WSC;
-  const int nbw = wino_nbw(a, device_cus());
-  if (a.w == 32) {
-    return nbw == 3 ? launch_wino_w<32, 3>(p, st)
-                    : nbw == 2 ? launch_wino_w<32, 2>(p, st) : launch_wino_w<32, 1>(p, st);
-  }
-  if (a.w == 128) return nbw == 2 ? launch_wino_w<128, 2>(p, st) : launch_wino_w<128, 1>(p, st);
-  return nbw == 2 ? launch_wino_w<64, 2>(p, st) : launch_wino_w<64, 1>(p, st);
+  const WinoParams p{a, c.cp0, c.nst, wino_swz(c.gx, c.gy), g_wino_stamps};
+  if (c.ow == 32)
+    return c.nbw == 3 ? launch_wino_k<32, 3>(c, p, st)
+                      : c.nbw == 2 ? launch_wino_k<32, 2>(c, p, st) : launch_wino_k<32, 1>(c, p, st);
+  if (c.ow == 128) return c.nbw == 2 ? launch_wino_k<128, 2>(c, p, st) : launch_wino_k<128, 1>(c, p, st);
+  return c.nbw == 2 ? launch_wino_k<64, 2>(c, p, st) : launch_wino_k<64, 1>(c, p, st);
 }
-
 // Workgroup-count heuristic (measured on MI355X, tools/conv_bench.py): 128-pixel tiles when
 // that still gives ≥ 2 workgroups per CU (≥ 512), else 64-pixel tiles (GRU q: 103 vs 94 TF,
 // N=64 convs: 85 vs 54 TF, N=192: 94 vs 91 TF; z|r and the 512-wide heads prefer 128).
@@ -1197,51 +1183,13 @@ bool conv1x1_enabled() {
   return conv1x1_sw.get() != 0;
 }
 
-// tile rows / halo rows / tile size for a launch (shared by the launcher and scflow_conv_pick_bk)
+// tile rows / halo rows / tile size of a direct-conv launch (plan_conv and scflow_conv_pick_bk)
 int launch_tile(const scflow_conv_args& a, const Geometry& g, int* tr, int* hr) {
   const long long m = (long long)a.n * g.oh * g.ow;
   const int tm = (pick_tile_m(m, g.npad / BN) == 64 && g.ow <= 64) ? 64 : 128;
   *tr = tm / g.ow;
   *hr = *tr + a.kh - 1;
   return tm;
-}
-
-template <int EPI, int KH, int KW, int TM, int BKS>
-int launch_mfma_bk(MfmaParams p, Geometry g, hipStream_t st) {
-  p.nst = (g.cp0 + g.cp1) / BKS;
-  const size_t lds = mfma_lds(g.hr, g.hc, g.taps, BKS);
-  allow_big_lds<conv_mfma_kernel<EPI, KH, KW, TM, BKS>>(lds);
-  dim3 grid(p.a.n * (g.oh / g.tr), g.npad / BN);
-  conv_mfma_kernel<EPI, KH, KW, TM, BKS><<<grid, 256, lds, st>>>(p);
-  return scflow_launch_status();
-}
-
-template <int EPI, int KH, int KW, int TM>
-int launch_mfma_tm(MfmaParams p, Geometry g, hipStream_t st) {
-  g.tr = TM / g.ow;
-  if (g.tr < 1 || g.oh % g.tr) return SCFLOW_EUNSUPPORTED;
-  g.hr = g.tr + KH - 1;
-  p.tr = g.tr;
-  p.hr = g.hr;
-  if (p.a.bk == 8) return launch_mfma_bk<EPI, KH, KW, TM, 8>(p, g, st);
-  return launch_mfma_bk<EPI, KH, KW, TM, 16>(p, g, st);
-}
-
-template <int EPI, int KH, int KW>
-int launch_mfma(const MfmaParams& p, const Geometry& g, hipStream_t st) {
-  int tr, hr;
-  if (launch_tile(p.a, g, &tr, &hr) == 64) return launch_mfma_tm<EPI, KH, KW, 64>(p, g, st);
-  return launch_mfma_tm<EPI, KH, KW, 128>(p, g, st);
-}
-
-template <int EPI>
-int dispatch_mfma(const MfmaParams& p, const Geometry& g, hipStream_t st) {
-  const int kh = p.a.kh, kw = p.a.kw;
-  if (kh == 1 && kw == 1) return launch_mfma<EPI, 1, 1>(p, g, st);
-  if (kh == 3 && kw == 3) return launch_mfma<EPI, 3, 3>(p, g, st);
-  if (kh == 1 && kw == 5) return launch_mfma<EPI, 1, 5>(p, g, st);
-  if (kh == 5 && kw == 1) return launch_mfma<EPI, 5, 1>(p, g, st);
-  return SCFLOW_EUNSUPPORTED;
 }
 
 }  // namespace
@@ -1265,22 +1213,11 @@ bool conv1x1w_launchable(const scflow_conv_args& a) {
 long long conv1x1w_packed_size(int cout, int c0) {
   return (long long)(round_up(cout, 64) / 32) * conv1x1w_kb(c0) * 256;
 }
-template <int KB>
-int launch_conv1x1w_kb(const scflow_conv_args& a, hipStream_t st) {
-  const size_t lds = conv1x1w_lds_bytes<KB>();
-  allow_big_lds<conv1x1w_kernel<KB>>(lds);
-  const long long M = (long long)a.n * a.h * a.w;
-  conv1x1w_kernel<KB><<<(unsigned)((M + W1_PX - 1) / W1_PX), 256, lds, st>>>(a);
-  return scflow_launch_status();
-}
-int launch_conv1x1w(const scflow_conv_args& a, hipStream_t st) {
-  if (!conv1x1w_launchable(a)) return SCFLOW_EUNSUPPORTED;
-  if (!aligned16(a.src0) || (a.s0 & 3) || !aligned16(a.weight)) return SCFLOW_EALIGN;
+int launch_conv1x1w(const scflow_conv_args& a, const ConvPlan& c, hipStream_t st) {
   switch (conv1x1w_kb(a.c0)) {
-    case 41: return launch_conv1x1w_kb<41>(a, st);
-    case 32: return launch_conv1x1w_kb<32>(a, st);
-    case 16: return launch_conv1x1w_kb<16>(a, st);
-    default: return SCFLOW_EUNSUPPORTED;
+    case 41: return launch_k<conv1x1w_kernel<41>>(c, conv1x1w_lds_bytes<41>(), st, a);
+    case 32: return launch_k<conv1x1w_kernel<32>>(c, conv1x1w_lds_bytes<32>(), st, a);
+    default: return launch_k<conv1x1w_kernel<16>>(c, conv1x1w_lds_bytes<16>(), st, a);
   }
 }
 
@@ -1313,6 +1250,11 @@ SCFLOW_API long long scflow_conv_packed_size_bk(int cout, int c0, int c1, int kh
   return scflow_conv_packed_size(cout, c0, c1, kh, kw, stride, w);
 }
 
+// workgroups of a packing launch: one thread per packed float, at most 4096 (grid-stride beyond)
+static int pack_blocks(long long total) {
+  return (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+}
+
 SCFLOW_API int scflow_conv_pack_weights(const float* w_oihw, float* packed, int cout, int c0,
                                         int c1, int kh, int kw, int stride, int w, int bk,
                                         void* stream) {
@@ -1320,7 +1262,7 @@ SCFLOW_API int scflow_conv_pack_weights(const float* w_oihw, float* packed, int 
   if (bk == SCFLOW_CONV_1X1W) {
     const long long total = scflow_conv_packed_size_bk(cout, c0, c1, kh, kw, stride, w, bk);
     if (total < 0) return (int)total;
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    const int blocks = pack_blocks(total);
     conv1x1w_pack_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(w_oihw, packed, cout, c0,
                                                                    conv1x1w_kb(c0), total);
     return scflow_launch_status();
@@ -1330,7 +1272,7 @@ SCFLOW_API int scflow_conv_pack_weights(const float* w_oihw, float* packed, int 
     if (total < 0) return (int)total;
     const int cp0 = round_up(c0, W4KC);
     const int nsub = (cp0 + round_up(c1, W4KC)) / W4KC;
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    const int blocks = pack_blocks(total);
     wino4_pack_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(w_oihw, packed, cout, c0, c1, cp0,
                                                                 nsub, total);
     return scflow_launch_status();
@@ -1342,7 +1284,7 @@ SCFLOW_API int scflow_conv_pack_weights(const float* w_oihw, float* packed, int 
     const int kc = kh == 3 ? WKC : W5KC, sc = kh == 3 ? WSC : W5SC;
     const int cp0 = round_up(c0, sc);
     const int nst = (cp0 + round_up(c1, sc)) / kc;
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    const int blocks = pack_blocks(total);
     if (kh == 3)
       wino_pack_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(w_oihw, packed, cout, c0, c1, cp0,
                                                                  nst, total);
@@ -1357,7 +1299,7 @@ SCFLOW_API int scflow_conv_pack_weights(const float* w_oihw, float* packed, int 
                               (kw - 1) / 2);
   if (g.variant == V_NONE) return SCFLOW_EUNSUPPORTED;
   const long long total = (long long)g.npad * g.ktot;
-  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  const int blocks = pack_blocks(total);
   pack_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(w_oihw, packed, g.variant, cout, c0, c1, kh,
                                                        kw, g.cp0, (g.cp0 + g.cp1) / bk, g.npad, bk,
                                                        total);
@@ -1392,7 +1334,7 @@ SCFLOW_API long long scflow_conv_workspace_bytes(const scflow_conv_args* args) {
   return wino4_workspace_bytes(*args);
 }
 
-// the thin 3×3 contraction's preconditions (conv_thinz.h; shared with conv_pair.h)
+// the thin 3×3 contraction's preconditions (conv_thinz.h)
 bool thinz_ok(const scflow_conv_args& a, const Geometry& g, bool tiled) {
   static EnvSwitch thinz_sw("SCFLOW_THINZ", 1);
   return tiled && thinz_sw.get() && a.c1 == 0 && a.c0 == 256 && a.kh == 3 && a.kw == 3 &&
@@ -1410,11 +1352,6 @@ long long smallcin_blocks(int ntiles) {
   return ntiles < cap ? ntiles : cap;
 }
 
-namespace {  // the grouped-launch and XHead kernels: internal linkage like the rest
-#include "conv_pair.h"
-#include "xhead_pred.h"
-}  // namespace
-
 bool conv_args_valid(const scflow_conv_args& a) {
   if (!a.src0 || !a.weight || a.n <= 0 || a.h <= 0 || a.w <= 0 || a.cout <= 0 || a.c0 <= 0 ||
       a.c1 < 0 || (a.c1 > 0 && !a.src1) || a.kh <= 0 || a.kw <= 0 || a.ph < 0 || a.pw < 0)
@@ -1425,193 +1362,241 @@ bool conv_args_valid(const scflow_conv_args& a) {
   return false;
 }
 
-// The whole-halo thin conv (conv_thin_full_kernel) of a tiled, single-source launch when `a` is
-// a KH×KW conv to CO channels whose halo, weights and staging fit: true after launching.
-template <int CO, int KH, int KW>
-static bool try_thin_full(const scflow_conv_args& a, const Geometry& g, hipStream_t st) {
-  if (a.cout != CO || a.kh != KH || a.kw != KW) return false;
-  const int tr = 64 / g.ow;
-  const size_t nh4 = (size_t)(tr + KH - 1) * (g.ow + KW - 1) * (a.c0 / 4);
-  size_t lds = sizeof(float) * (size_t)(tr + KH - 1) * (g.ow + KW - 1) * thinf_ld(a.c0);
-  if (lds < sizeof(float) * THINF_WAVES * CO * 64) lds = sizeof(float) * THINF_WAVES * CO * 64;
-  const size_t nw4 = (size_t)KH * KW * a.c0 * CO / 4;
-  lds += 16 * nw4;  // the weights behind the halo
-  if (lds > 160 * 1024 || nh4 > (size_t)12 * THINF_WAVES * 64 || nw4 > (size_t)2 * THINF_WAVES * 64 ||
-      !aligned16(a.weight))
-    return false;
-  allow_big_lds<conv_thin_full_kernel<CO, KH, KW>>(lds);
-  const unsigned blocks = (unsigned)(a.n * (g.oh / tr));
-  conv_thin_full_kernel<CO, KH, KW><<<blocks, THINF_WAVES * 64, lds, st>>>(a, g.oh, g.ow, g_wino_stamps);
-  return true;
+// SCFLOW_CONV_PAIR=0: scflow_conv2d_pair always launches separately (A/B)
+bool pair_enabled() {
+  static EnvSwitch pair_sw("SCFLOW_CONV_PAIR", 1);
+  return pair_sw.get() != 0;
 }
 
-SCFLOW_API int scflow_conv2d(const scflow_conv_args* args, void* stream) {
-  if (!args) return SCFLOW_EINVAL;
-  const scflow_conv_args& a = *args;
-  if (!conv_args_valid(a)) return SCFLOW_EINVAL;
-  if (a.bk == SCFLOW_CONV_WINO) return launch_wino(a, (hipStream_t)stream);
-  if (a.bk == SCFLOW_CONV_WINO4) return launch_wino4(a, (hipStream_t)stream);
-  if (a.bk == SCFLOW_CONV_1X1W) return launch_conv1x1w(a, (hipStream_t)stream);
-  if (has_fused_norm(a)) return SCFLOW_EUNSUPPORTED;  // Winograd 3×3 only
-  if (a.bk != 0 && a.bk != 8 && a.bk != 16) return SCFLOW_EINVAL;
-  Geometry g = select_variant(a.cout, a.c0, a.c1, a.kh, a.kw, a.stride, a.h, a.w, a.ph, a.pw);
-  if (g.variant == V_NONE) return SCFLOW_EUNSUPPORTED;
-  if (g.oh <= 0 || g.ow <= 0) return SCFLOW_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  if (g.variant == V_MFMA) {
-    if (!aligned16(a.src0) || (a.s0 & 3) || (a.c1 > 0 && (!aligned16(a.src1) || (a.s1 & 3))) ||
-        !aligned16(a.weight))
-      return SCFLOW_EALIGN;
-    MfmaParams p;
-    p.a = a;
-    p.oh = g.oh;
-    p.ow = g.ow;
-    p.tr = g.tr;
-    p.hr = g.hr;
-    p.hc = g.hc;
-    p.cp0 = g.cp0;
-    p.nst = g.nst;
-    if (a.kh == 1 && a.kw == 1 && a.epilogue == SCFLOW_EPI_PLAIN && a.bk != 8 && conv1x1_enabled()) {
-      int tr, hr;
-      if (launch_tile(a, g, &tr, &hr) == 128) {
-        const long long M = (long long)a.n * g.oh * g.ow;
-        p.nst = (g.cp0 + g.cp1) / BK;
-        conv1x1_kernel<<<dim3((unsigned)((M + 127) / 128), g.npad / BN), 256, 0, st>>>(p);
-        return scflow_launch_status();
-      }
-    }
-    switch (a.epilogue) {
-      case SCFLOW_EPI_GRU_ZR: return dispatch_mfma<SCFLOW_EPI_GRU_ZR>(p, g, st);
-      case SCFLOW_EPI_GRU_Q: return dispatch_mfma<SCFLOW_EPI_GRU_Q>(p, g, st);
-      default: return dispatch_mfma<SCFLOW_EPI_PLAIN>(p, g, st);
-    }
+namespace {  // the launch plan, the grouped-launch and XHead kernels: internal linkage like the rest
+
+static_assert(WSC == W5SC, "plan_conv pads both Winograd families' channels alike");
+
+ConvPlan plan_conv(const scflow_conv_args& a) {
+  ConvPlan p{};
+  const auto fail = [&p](int status) { p.status = status; return p; };
+  const auto is = [&p](int kind, long long gx, int gy = 1, size_t lds = 0) {
+    p.kind = kind, p.gx = (unsigned)gx, p.gy = gy, p.lds = lds;
+    return p;
+  };
+  if (!conv_args_valid(a)) return fail(SCFLOW_EINVAL);
+  const bool src_aligned = aligned16(a.src0) && !(a.s0 & 3) &&
+                           (a.c1 == 0 || (aligned16(a.src1) && !(a.s1 & 3)));
+  p.oh = a.h, p.ow = a.w;
+  if (a.bk == SCFLOW_CONV_WINO) {  // F(2×2,3×3) or F(4,5)
+    if (!wino_launchable(a)) return fail(SCFLOW_EUNSUPPORTED);
+    if (!src_aligned || !aligned16(a.weight)) return fail(SCFLOW_EALIGN);
+    p.cp0 = round_up(a.c0, WSC);
+    p.nst = (p.cp0 + round_up(a.c1, WSC)) / WSC;
+    p.nbw = wino_nbw(a, device_cus());
+    return is(a.kh == 3 ? SCFLOW_PLAN_WINO : SCFLOW_PLAN_WINO5, wino_blocks(a),
+              round_up(a.cout, 32 * p.nbw) / (32 * p.nbw));
   }
-  if (a.epilogue != SCFLOW_EPI_PLAIN || a.bias_map) return SCFLOW_EUNSUPPORTED;
+  if (a.bk == SCFLOW_CONV_WINO4) {  // launch_wino4 derives its own grids (shared with the XHead)
+    p.status = wino4_status(a);
+    return p.status ? p : is(SCFLOW_PLAN_WINO4, 0);
+  }
+  if (a.bk == SCFLOW_CONV_1X1W) {
+    if (!conv1x1w_launchable(a)) return fail(SCFLOW_EUNSUPPORTED);
+    if (!aligned16(a.src0) || (a.s0 & 3) || !aligned16(a.weight)) return fail(SCFLOW_EALIGN);
+    return is(SCFLOW_PLAN_1X1W, ((long long)a.n * a.h * a.w + W1_PX - 1) / W1_PX);
+  }
+  if (has_fused_norm(a)) return fail(SCFLOW_EUNSUPPORTED);  // Winograd 3×3 only
+  if (a.bk != 0 && a.bk != 8 && a.bk != 16) return fail(SCFLOW_EINVAL);
+  const Geometry g = select_variant(a.cout, a.c0, a.c1, a.kh, a.kw, a.stride, a.h, a.w, a.ph, a.pw);
+  if (g.variant == V_NONE) return fail(SCFLOW_EUNSUPPORTED);
+  if (g.oh <= 0 || g.ow <= 0) return fail(SCFLOW_EINVAL);
+  p.oh = g.oh, p.ow = g.ow, p.npad = g.npad;
   const long long M = (long long)a.n * g.oh * g.ow;
-  if (g.variant == V_SMALLCIN) {
-    const bool mfma_ok = (g.ow == 32 || g.ow == 64) && g.ow == a.w && g.oh == a.h &&
-                         g.oh % (64 / g.ow) == 0 && (g.npad == 64 || g.npad == 128) &&
-                         (long long)a.n * a.h * a.w * a.s0 * 4 < 0x7ffffff0LL;  // buffer offsets
-    if (mfma_ok) {
-      const int ntiles = a.n * (g.oh / (64 / g.ow));
-      const unsigned blocks = (unsigned)smallcin_blocks(ntiles);
-      const size_t lds = 2 * sizeof(float) * (size_t)(64 / g.ow + a.kh - 1) * (g.ow + a.kw - 1) * a.c0;
-#define SCFLOW_SCM(CI, KH_, KW_)                                                                   \
-  if (a.c0 == CI && a.kh == KH_ && a.kw == KW_) {                                                  \
-    if (g.npad == 128 && smallcin_split())                                                         \
-      conv_smallcin_mfma_kernel<CI, KH_, KW_, 1><<<dim3(blocks, 2), 256, lds, st>>>(a, g.oh, g.ow, g.npad, ntiles, g_wino_stamps); \
-    else if (g.npad == 128)                                                                        \
-      conv_smallcin_mfma_kernel<CI, KH_, KW_, 2><<<blocks, 256, lds, st>>>(a, g.oh, g.ow, g.npad, ntiles, g_wino_stamps); \
-    else                                                                                           \
-      conv_smallcin_mfma_kernel<CI, KH_, KW_, 1><<<blocks, 256, lds, st>>>(a, g.oh, g.ow, g.npad, ntiles, g_wino_stamps); \
-    return scflow_launch_status();                                                                 \
+  if (g.variant == V_MFMA) {
+    if (!src_aligned || !aligned16(a.weight)) return fail(SCFLOW_EALIGN);
+    p.tm = launch_tile(a, g, &p.tr, &p.hr);
+    p.hc = g.hc, p.cp0 = g.cp0;
+    if (a.kh == 1 && a.kw == 1 && a.epilogue == SCFLOW_EPI_PLAIN && a.bk != 8 && conv1x1_enabled() &&
+        p.tm == 128) {
+      p.nst = (g.cp0 + g.cp1) / BK;
+      return is(SCFLOW_PLAN_1X1, (M + 127) / 128, g.npad / BN);
+    }
+    if (p.tr < 1 || g.oh % p.tr) return fail(SCFLOW_EUNSUPPORTED);
+    p.bks = a.bk == 8 ? 8 : 16;
+    p.nst = (g.cp0 + g.cp1) / p.bks;
+    return is(SCFLOW_PLAN_MFMA, a.n * (g.oh / p.tr), g.npad / BN, mfma_lds(p.hr, g.hc, g.taps, p.bks));
   }
-      SCFLOW_SCM(2, 7, 7)
-      SCFLOW_SCM(1, 3, 3)
-      SCFLOW_SCM(2, 3, 3)
-#undef SCFLOW_SCM
+  if (a.epilogue != SCFLOW_EPI_PLAIN || a.bias_map) return fail(SCFLOW_EUNSUPPORTED);
+  // whole image rows of 32 or 64 pixels, 64 pixels per tile: the small-cin MFMA and tiled thin kernels
+  const bool rows64 = (g.ow == 32 || g.ow == 64) && g.ow == a.w && g.oh == a.h && g.oh % (64 / g.ow) == 0;
+  if (rows64) p.tr = 64 / g.ow;
+  const bool k3 = a.kh == 3 && a.kw == 3, k7 = a.kh == 7 && a.kw == 7;
+  if (g.variant == V_SMALLCIN) {
+    const bool shape = (k7 && a.c0 == 2) || (k3 && a.c0 <= 2);  // the instantiated (cin, taps)
+    if (shape && rows64 && (g.npad == 64 || g.npad == 128) &&
+        (long long)a.n * a.h * a.w * a.s0 * 4 < 0x7ffffff0LL) {  // buffer offsets
+      const bool split = g.npad == 128 && smallcin_split();
+      p.ntiles = a.n * (g.oh / p.tr);
+      p.nbw = g.npad == 128 && !split ? 2 : 1;
+      return is(SCFLOW_PLAN_SMALLCIN_MFMA, smallcin_blocks(p.ntiles), split ? 2 : 1,
+                2 * sizeof(float) * (size_t)(p.tr + a.kh - 1) * (g.ow + a.kw - 1) * a.c0);
     }
-    const unsigned tiles = (unsigned)((long long)a.n * g.oh * ((g.ow + 31) / 32));
-    if (g.npad == 64 || g.npad == 128 || g.npad == 256) {
-      if (a.c0 == 2 && a.kh == 7 && a.kw == 7) {
-        conv_smallcin_kernel<2, 7, 7><<<tiles, 256, 0, st>>>(a, g.oh, g.ow, g.npad);
-        return scflow_launch_status();
-      }
-      if (a.c0 == 1 && a.kh == 3 && a.kw == 3) {
-        conv_smallcin_kernel<1, 3, 3><<<tiles, 256, 0, st>>>(a, g.oh, g.ow, g.npad);
-        return scflow_launch_status();
-      }
-      if (a.c0 == 2 && a.kh == 3 && a.kw == 3) {
-        conv_smallcin_kernel<2, 3, 3><<<tiles, 256, 0, st>>>(a, g.oh, g.ow, g.npad);
-        return scflow_launch_status();
-      }
-    }
-    dim3 grid((unsigned)((M + 255) / 256), g.npad / 16);
-    switch (a.c0) {
-      case 1: conv_smallcin_generic<1><<<grid, 256, 0, st>>>(a, g.oh, g.ow, g.npad); break;
-      case 2: conv_smallcin_generic<2><<<grid, 256, 0, st>>>(a, g.oh, g.ow, g.npad); break;
-      case 3: conv_smallcin_generic<3><<<grid, 256, 0, st>>>(a, g.oh, g.ow, g.npad); break;
-      case 4: conv_smallcin_generic<4><<<grid, 256, 0, st>>>(a, g.oh, g.ow, g.npad); break;
-      default: return SCFLOW_EUNSUPPORTED;
-    }
-    return scflow_launch_status();
+    if (shape && (g.npad == 64 || g.npad == 128 || g.npad == 256))
+      return is(SCFLOW_PLAN_SMALLCIN_TILED, (long long)a.n * g.oh * ((g.ow + 31) / 32));
+    return is(SCFLOW_PLAN_SMALLCIN_GENERIC, (M + 255) / 256, g.npad / 16);
   }
   // thin
-  if (!aligned16(a.src0) || (a.s0 & 3) || (a.c1 > 0 && (!aligned16(a.src1) || (a.s1 & 3))))
-    return SCFLOW_EALIGN;
-  const bool tiled = (g.ow == 32 || g.ow == 64) && (a.c0 % 8) == 0 && (a.c1 % 8) == 0 &&
-                     g.oh % (64 / g.ow) == 0 && g.ow == a.w && g.oh == a.h;
+  if (!src_aligned) return fail(SCFLOW_EALIGN);
+  const bool tiled = rows64 && (a.c0 % 8) == 0 && (a.c1 % 8) == 0;
   // channel contraction on MFMA (conv_thinz.h): 3×3 same-padded, one 256-channel source,
   // ≤ 2 outputs; SCFLOW_THINZ = 0 keeps the LDS kernels below (A/B)
   // Measured (profiles/r06/g9_thinz_ab.txt): flow predictor 3×3 256 → 2 at configs[4] 81 → 51 µs
   // alone (decoder 8.84k → 8.88k iters/s), at configs[1] 14.9 → 10.2 µs (decoder 27.49k → 27.72k).
   // The 1×1 256 → 1 mask predictor stays on the chunked kernel (20.8 vs 33.8 µs at configs[4]:
   // one Z column of 32 leaves the MFMAs 97 % idle; configs[1] equal, g10_thinz_mask1x1_ab.txt).
-  if (thinz_ok(a, g, tiled)) {
-    const int R = g.ow == 64 ? 4 : 2;
-    const unsigned blocks = (unsigned)(a.n * (g.oh / R));
-#define SCFLOW_THINZ(CO, W_, R_) conv_thinz_kernel<CO, 3, 3, W_, R_><<<blocks, 256, 0, st>>>(a)
-    if (g.ow == 64) {
-      if (a.cout == 2) SCFLOW_THINZ(2, 64, 4); else SCFLOW_THINZ(1, 64, 4);
-    } else {
-      if (a.cout == 2) SCFLOW_THINZ(2, 32, 2); else SCFLOW_THINZ(1, 32, 2);
-    }
-#undef SCFLOW_THINZ
-    return scflow_launch_status();
-  }
-  // whole-halo variant: one source, channels a multiple of 64, the halo within 160 KB of LDS
+  if (thinz_ok(a, g, tiled)) return is(SCFLOW_PLAN_THINZ, a.n * (g.oh / (g.ow == 64 ? 4 : 2)));
+  const size_t halo = tiled ? (size_t)(p.tr + a.kh - 1) * (g.ow + a.kw - 1) : 0;  // pixels
+  // whole-halo variant: one source, channels a multiple of 64, 3×3 to ≤ 2 outputs, the halo and
+  // the weights behind it within 160 KB of LDS and the staging registers
   // (1×1: the chunked kernel below is faster — its 32-channel chunks need no halo)
   static EnvSwitch thin_full_sw("SCFLOW_THIN_FULL", 1);
-  if (tiled && thin_full_sw.get() && a.c1 == 0 && a.c0 % (4 * THINF_WAVES) == 0 &&
-      (try_thin_full<1, 3, 3>(a, g, st) || try_thin_full<2, 3, 3>(a, g, st)))
-    return scflow_launch_status();
-  if (tiled) {
-    const int tr = 64 / g.ow;
-    const unsigned blocks = (unsigned)(a.n * (g.oh / tr));
-#define SCFLOW_THIN(CO, KH_, KW_)                                                               \
-  if (a.cout == CO && a.kh == KH_ && a.kw == KW_) {                                             \
-    size_t lds = sizeof(float) * (size_t)(tr + KH_ - 1) * (g.ow + KW_ - 1) * THIN_LD;           \
-    if (lds < sizeof(float) * 4 * CO * 64) lds = sizeof(float) * 4 * CO * 64;                    \
-    lds += sizeof(float) * (size_t)KH_ * KW_ * (a.c0 + a.c1) * CO; /* weights */                \
-    allow_big_lds<conv_thin_kernel<CO, KH_, KW_>>(lds);                                         \
-    conv_thin_kernel<CO, KH_, KW_><<<blocks, 256, lds, st>>>(a, g.oh, g.ow);                    \
-    return scflow_launch_status();                                                              \
+  if (tiled && thin_full_sw.get() && a.c1 == 0 && a.c0 % (4 * THINF_WAVES) == 0 && k3 && a.cout <= 2) {
+    const size_t nh4 = halo * (a.c0 / 4), nw4 = (size_t)9 * a.c0 * a.cout / 4;
+    size_t lds = sizeof(float) * halo * thinf_ld(a.c0);
+    if (lds < sizeof(float) * THINF_WAVES * a.cout * 64) lds = sizeof(float) * THINF_WAVES * a.cout * 64;
+    lds += 16 * nw4;
+    if (lds <= 160 * 1024 && nh4 <= (size_t)12 * THINF_WAVES * 64 && nw4 <= (size_t)2 * THINF_WAVES * 64 &&
+        aligned16(a.weight))
+      return is(SCFLOW_PLAN_THIN_FULL, a.n * (g.oh / p.tr), 1, lds);
   }
-    SCFLOW_THIN(1, 1, 1)
-    SCFLOW_THIN(2, 1, 1)
-    SCFLOW_THIN(1, 3, 3)
-    SCFLOW_THIN(2, 3, 3)
-    SCFLOW_THIN(2, 7, 7)  // training: dX of the 2 → 128 7×7 flow encoders
-#undef SCFLOW_THIN
+  // chunked: 1×1 and 3×3 to ≤ 2 outputs, 7×7 to 2 (training: dX of the 2 → 128 7×7 flow encoders)
+  if (tiled && a.cout <= 2 && ((a.kh == 1 && a.kw == 1) || k3 || (k7 && a.cout == 2))) {
+    size_t lds = sizeof(float) * halo * THIN_LD;
+    if (lds < sizeof(float) * 4 * a.cout * 64) lds = sizeof(float) * 4 * a.cout * 64;
+    lds += sizeof(float) * (size_t)a.kh * a.kw * (a.c0 + a.c1) * a.cout;  // weights
+    return is(SCFLOW_PLAN_THIN_CHUNKED, a.n * (g.oh / p.tr), 1, lds);
   }
-  const unsigned blocks = (unsigned)((M + 3) / 4);
-  switch (a.cout) {
-    case 1: conv_thin_generic<1><<<blocks, 256, 0, st>>>(a, g.oh, g.ow); break;
-    case 2: conv_thin_generic<2><<<blocks, 256, 0, st>>>(a, g.oh, g.ow); break;
-    case 3: conv_thin_generic<3><<<blocks, 256, 0, st>>>(a, g.oh, g.ow); break;
-    case 4: conv_thin_generic<4><<<blocks, 256, 0, st>>>(a, g.oh, g.ow); break;
+  return is(SCFLOW_PLAN_THIN_GENERIC, (M + 3) / 4);
+}
+
+#include "conv_pair.h"
+#include "xhead_pred.h"
+
+template <int EPI, int KH, int KW>
+int launch_mfma_k(const ConvPlan& c, const MfmaParams& p, hipStream_t st) {
+  if (c.tm == 64)
+    return c.bks == 8 ? launch_k<conv_mfma_kernel<EPI, KH, KW, 64, 8>>(c, c.lds, st, p)
+                      : launch_k<conv_mfma_kernel<EPI, KH, KW, 64, 16>>(c, c.lds, st, p);
+  return c.bks == 8 ? launch_k<conv_mfma_kernel<EPI, KH, KW, 128, 8>>(c, c.lds, st, p)
+                    : launch_k<conv_mfma_kernel<EPI, KH, KW, 128, 16>>(c, c.lds, st, p);
+}
+template <int EPI>
+int launch_mfma(const ConvPlan& c, const MfmaParams& p, hipStream_t st) {
+  if (p.a.kh == 1 && p.a.kw == 1) return launch_mfma_k<EPI, 1, 1>(c, p, st);
+  if (p.a.kh == 3) return launch_mfma_k<EPI, 3, 3>(c, p, st);
+  return p.a.kh == 1 ? launch_mfma_k<EPI, 1, 5>(c, p, st) : launch_mfma_k<EPI, 5, 1>(c, p, st);
+}
+template <int CI, int KH, int KW>
+int launch_smallcin_mfma(const scflow_conv_args& a, const ConvPlan& c, hipStream_t st) {
+  return c.nbw == 1 ? launch_k<conv_smallcin_mfma_kernel<CI, KH, KW, 1>>(
+                          c, c.lds, st, a, c.oh, c.ow, c.npad, c.ntiles, g_wino_stamps)
+                    : launch_k<conv_smallcin_mfma_kernel<CI, KH, KW, 2>>(
+                          c, c.lds, st, a, c.oh, c.ow, c.npad, c.ntiles, g_wino_stamps);
+}
+
+// the one place a plan becomes a template instantiation and a launch
+int launch_plan(const scflow_conv_args& a, const ConvPlan& c, hipStream_t st) {
+  const bool co2 = a.cout == 2;
+  switch (c.kind) {
+    case SCFLOW_PLAN_WINO:
+    case SCFLOW_PLAN_WINO5: return launch_wino(a, c, st);
+    case SCFLOW_PLAN_WINO4: return launch_wino4(a, st);
+    case SCFLOW_PLAN_1X1W: return launch_conv1x1w(a, c, st);
+    case SCFLOW_PLAN_MFMA:
+    case SCFLOW_PLAN_1X1: {
+      const MfmaParams p{a, c.oh, c.ow, c.tr, c.hr, c.hc, c.cp0, c.nst};
+      if (c.kind == SCFLOW_PLAN_1X1) return launch_k<conv1x1_kernel>(c, 0, st, p);
+      if (a.epilogue == SCFLOW_EPI_GRU_ZR) return launch_mfma<SCFLOW_EPI_GRU_ZR>(c, p, st);
+      if (a.epilogue == SCFLOW_EPI_GRU_Q) return launch_mfma<SCFLOW_EPI_GRU_Q>(c, p, st);
+      return launch_mfma<SCFLOW_EPI_PLAIN>(c, p, st);
+    }
+    case SCFLOW_PLAN_SMALLCIN_MFMA:
+      if (a.kh == 7) return launch_smallcin_mfma<2, 7, 7>(a, c, st);
+      return a.c0 == 1 ? launch_smallcin_mfma<1, 3, 3>(a, c, st) : launch_smallcin_mfma<2, 3, 3>(a, c, st);
+    case SCFLOW_PLAN_SMALLCIN_TILED:
+      if (a.kh == 7) return launch_k<conv_smallcin_kernel<2, 7, 7>>(c, 0, st, a, c.oh, c.ow, c.npad);
+      return a.c0 == 1 ? launch_k<conv_smallcin_kernel<1, 3, 3>>(c, 0, st, a, c.oh, c.ow, c.npad)
+                       : launch_k<conv_smallcin_kernel<2, 3, 3>>(c, 0, st, a, c.oh, c.ow, c.npad);
+    case SCFLOW_PLAN_SMALLCIN_GENERIC:
+      switch (a.c0) {
+        case 1: return launch_k<conv_smallcin_generic<1>>(c, 0, st, a, c.oh, c.ow, c.npad);
+        case 2: return launch_k<conv_smallcin_generic<2>>(c, 0, st, a, c.oh, c.ow, c.npad);
+        case 3: return launch_k<conv_smallcin_generic<3>>(c, 0, st, a, c.oh, c.ow, c.npad);
+        default: return launch_k<conv_smallcin_generic<4>>(c, 0, st, a, c.oh, c.ow, c.npad);
+      }
+    case SCFLOW_PLAN_THINZ:
+      if (c.ow == 64)
+        return co2 ? launch_k<conv_thinz_kernel<2, 3, 3, 64, 4>>(c, 0, st, a)
+                   : launch_k<conv_thinz_kernel<1, 3, 3, 64, 4>>(c, 0, st, a);
+      return co2 ? launch_k<conv_thinz_kernel<2, 3, 3, 32, 2>>(c, 0, st, a)
+                 : launch_k<conv_thinz_kernel<1, 3, 3, 32, 2>>(c, 0, st, a);
+    case SCFLOW_PLAN_THIN_FULL:
+      return !co2 ? launch_k<conv_thin_full_kernel<1, 3, 3>, THINF_WAVES * 64>(c, c.lds, st, a, c.oh, c.ow,
+                                                                              g_wino_stamps)
+                  : launch_k<conv_thin_full_kernel<2, 3, 3>, THINF_WAVES * 64>(c, c.lds, st, a, c.oh, c.ow,
+                                                                              g_wino_stamps);
+    case SCFLOW_PLAN_THIN_CHUNKED:
+      if (a.kh == 1)
+        return !co2 ? launch_k<conv_thin_kernel<1, 1, 1>>(c, c.lds, st, a, c.oh, c.ow)
+                    : launch_k<conv_thin_kernel<2, 1, 1>>(c, c.lds, st, a, c.oh, c.ow);
+      if (a.kh == 3)
+        return !co2 ? launch_k<conv_thin_kernel<1, 3, 3>>(c, c.lds, st, a, c.oh, c.ow)
+                    : launch_k<conv_thin_kernel<2, 3, 3>>(c, c.lds, st, a, c.oh, c.ow);
+      return launch_k<conv_thin_kernel<2, 7, 7>>(c, c.lds, st, a, c.oh, c.ow);
+    case SCFLOW_PLAN_THIN_GENERIC:
+      switch (a.cout) {
+        case 1: return launch_k<conv_thin_generic<1>>(c, 0, st, a, c.oh, c.ow);
+        case 2: return launch_k<conv_thin_generic<2>>(c, 0, st, a, c.oh, c.ow);
+        case 3: return launch_k<conv_thin_generic<3>>(c, 0, st, a, c.oh, c.ow);
+        default: return launch_k<conv_thin_generic<4>>(c, 0, st, a, c.oh, c.ow);
+      }
     default: return SCFLOW_EUNSUPPORTED;
   }
-  return scflow_launch_status();
+}
+
+}  // namespace
+
+SCFLOW_API int scflow_conv2d(const scflow_conv_args* args, void* stream) {
+  if (!args) return SCFLOW_EINVAL;
+  const ConvPlan p = plan_conv(*args);
+  return p.status ? p.status : launch_plan(*args, p, (hipStream_t)stream);
 }
 
 // Two independent convs (neither reads what the other writes) as one grouped launch when a paired
-// kernel covers them (conv_pair.h), else as two scflow_conv2d launches in order.  Results equal
-// the two separate launches bit for bit.  SCFLOW_CONV_PAIR=0 always launches separately (A/B).
+// kernel covers their two plans (conv_pair.h), else as two launches in order.  Results equal the
+// two separate launches bit for bit.  An invalid half is refused before either is launched.
 SCFLOW_API int scflow_conv2d_pair(const scflow_conv_args* args_a, const scflow_conv_args* args_b,
                                   void* stream) {
-  if (!args_a || !args_b || !conv_args_valid(*args_a) || !conv_args_valid(*args_b))
-    return SCFLOW_EINVAL;
-  static EnvSwitch pair_sw("SCFLOW_CONV_PAIR", 1);
-  if (pair_sw.get()) {
-    hipStream_t st = (hipStream_t)stream;
-    int r = try_pair(*args_a, *args_b, st);
-    if (r == 0) r = try_pair(*args_b, *args_a, st);
-    if (r == 1) return SCFLOW_OK;
-    if (r != 0) return r;
-  }
-  const int e = scflow_conv2d(args_a, stream);
-  return e ? e : scflow_conv2d(args_b, stream);
+  if (!args_a || !args_b) return SCFLOW_EINVAL;
+  const scflow_conv_args &a = *args_a, &b = *args_b;
+  const ConvPlan pa = plan_conv(a), pb = plan_conv(b);
+  if (pa.status || pb.status) return pa.status ? pa.status : pb.status;
+  hipStream_t st = (hipStream_t)stream;
+  if (const int k = pair_kind(a, pa, b, pb)) return launch_pair(k, a, pa, b, pb, st);
+  if (const int k = pair_kind(b, pb, a, pa)) return launch_pair(k, b, pb, a, pa, st);
+  const int e = launch_plan(a, pa, st);
+  return e ? e : launch_plan(b, pb, st);
+}
+
+// Host-only: the kernel family scflow_conv2d would launch for a (SCFLOW_PLAN_*; b NULL) or the
+// grouped kernel scflow_conv2d_pair would launch for (a, b) in either order (SCFLOW_PAIR_*), and
+// the status either would answer before launching.  No launch, no pointer dereferenced.
+SCFLOW_API int scflow_conv_plan_kind(const scflow_conv_args* a, const scflow_conv_args* b, int* kind) {
+  if (!a || !kind) return SCFLOW_EINVAL;
+  const ConvPlan pa = plan_conv(*a);
+  *kind = b ? SCFLOW_PAIR_NONE : pa.kind;
+  if (!b) return pa.status;
+  const ConvPlan pb = plan_conv(*b);
+  if (pa.status || pb.status) return pa.status ? pa.status : pb.status;
+  const int k = pair_kind(*a, pa, *b, pb);
+  *kind = k ? k : pair_kind(*b, pb, *a, pa);
+  return SCFLOW_OK;
 }
 
 // The XHeads' hidden conv with both predictors contracted in its epilogue, plus the block / tap

@@ -491,13 +491,22 @@ int launch_wino4_gemm(const Wino4Params& p, dim3 grid, hipStream_t st) {
   return scflow_launch_status();
 }
 
-// the input transform launch and the GEMM's parameters / grid (launch_wino4, launch_xhead_pred)
-int wino4_prepare(const scflow_conv_args& a, hipStream_t st, Wino4Params& p, dim3& grid) {
+// what wino4_prepare answers before it launches anything (the conv planner reads it too)
+int wino4_status(const scflow_conv_args& a) {
   if (!wino4_shape(a)) return SCFLOW_EUNSUPPORTED;
   if (!a.ws || a.ws_bytes < wino4_workspace_bytes(a)) return SCFLOW_EINVAL;
   if (!aligned16(a.src0) || (a.s0 & 3) || (a.c1 > 0 && (!aligned16(a.src1) || (a.s1 & 3))) ||
       !aligned16(a.weight) || !aligned16(a.ws))
     return SCFLOW_EALIGN;
+  const long long ntiles = (long long)a.n * (a.h / 4) * (a.w / 4);
+  const long long nsub = (round_up(a.c0, W4KC) + round_up(a.c1, W4KC)) / W4KC;
+  if (ntiles >= (1LL << 30) || nsub * W4P * 1024 >= (1LL << 31)) return SCFLOW_EUNSUPPORTED;
+  return SCFLOW_OK;
+}
+
+// the input transform launch and the GEMM's parameters / grid (launch_wino4, launch_xhead_pred)
+int wino4_prepare(const scflow_conv_args& a, hipStream_t st, Wino4Params& p, dim3& grid) {
+  if (const int e = wino4_status(a)) return e;
   p = Wino4Params{};
   p.a = a;
   p.v = a.ws;
@@ -506,7 +515,6 @@ int wino4_prepare(const scflow_conv_args& a, hipStream_t st, Wino4Params& p, dim
   p.th = a.h / 4;
   p.tw = a.w / 4;
   const long long ntiles = (long long)a.n * p.th * p.tw;
-  if (ntiles >= (1LL << 30) || (long long)p.nsub * W4P * 1024 >= (1LL << 31)) return SCFLOW_EUNSUPPORTED;
   p.ntiles = (int)ntiles;
   p.ntb = (int)((ntiles + W4TM - 1) / W4TM);
   p.stamps = g_wino_stamps;

@@ -375,6 +375,17 @@ def conv2d_pair(args_a, args_b, dev_tensor: Tensor) -> None:
     _launch("scflow_conv2d_pair", dev_tensor, ctypes.byref(args_a), ctypes.byref(args_b))
 
 
+def conv_plan_kind(args_a, args_b=None) -> int:
+    """scflow_conv_plan_kind (host-only): the kernel family scflow_conv2d launches for ``args_a``
+    (``_lib.PLAN_*``), or with ``args_b`` the grouped kernel scflow_conv2d_pair launches for the
+    two (``_lib.PAIR_*``, 0: two launches); raises what the launch would refuse with."""
+    kind = ctypes.c_int(0)
+    check(_lib.load().scflow_conv_plan_kind(ctypes.byref(args_a),
+                                            ctypes.byref(args_b) if args_b is not None else None,
+                                            ctypes.byref(kind)), "scflow_conv_plan_kind")
+    return kind.value
+
+
 def xhead_pred_pack(flow_w: Tensor, mask_w: Tensor) -> Tensor:
     """scflow_xhead_pred's predictor weights: flow predictor [2, cf, 3, 3] and mask predictor
     [1, cm, 1, 1] → [cf + cm, 20] (row c < cf: W[o][c][ty][tx] at column (3·ty + tx)·2 + o; row

@@ -926,7 +926,9 @@ def test_conv2d_pair_bit_identical(ops, size, monkeypatch):
     """scflow_conv2d_pair (round 6: the decoder tail's flow-predictor / mask-predictor branches as
     grouped launches) equals the two separate scflow_conv2d launches bit for bit, for each paired
     kernel (thin 3×3 256→2 ‖ 1×1 256→1, small-cin 7×7 2→128 ‖ 3×3 1→64, F(2×2,3×3) 128→64 ‖
-    64→32), in both argument orders, and with pairing off (SCFLOW_CONV_PAIR=0)."""
+    64→32), in both argument orders, and with pairing off (SCFLOW_CONV_PAIR=0); the launch plan
+    (scflow_conv_plan_kind) names the grouped kernel exactly when pairing is on."""
+    from scflow_amd import _lib
     from scflow_amd._lib import reload_switches
     from scflow_amd.modules import ConvRunner
     g = torch.Generator().manual_seed(17)
@@ -949,7 +951,8 @@ def test_conv2d_pair_bit_identical(ops, size, monkeypatch):
         ((conv(128, 64, 3, "ReLU"), ops.Chan.whole(torch.randn(M, 128, generator=g).cuda()), 64),
          (conv(64, 32, 3, "ReLU"), ops.Chan.whole(torch.randn(M, 64, generator=g).cuda()), 32)),
     ]
-    for (ra, sa, ca), (rb, sb, cb) in cases:
+    kinds = [_lib.PAIR_THIN, _lib.PAIR_SMALLCIN, _lib.PAIR_WINO]  # the grouped kernel of each case
+    for ((ra, sa, ca), (rb, sb, cb)), grouped in zip(cases, kinds):
         ref_a = torch.full((M, ca), 7.0, device="cuda")
         ref_b = torch.full((M, cb), 7.0, device="cuda")
         ra.run(sa, ops.Chan.whole(ref_a), n, h, w)
@@ -962,10 +965,10 @@ def test_conv2d_pair_bit_identical(ops, size, monkeypatch):
                 out_b = torch.full((M, cb), 7.0, device="cuda")
                 aa = ra.args(sa, ops.Chan.whole(out_a), n, h, w)
                 ab = rb.args(sb, ops.Chan.whole(out_b), n, h, w)
-                if order:
-                    ops.conv2d_pair(ab, aa, head)
-                else:
-                    ops.conv2d_pair(aa, ab, head)
+                first, second = (ab, aa) if order else (aa, ab)
+                # a grouped kernel really runs (not the two-launch fallback), and only when asked
+                assert ops.conv_plan_kind(first, second) == (grouped if pair == "1" else _lib.PAIR_NONE)
+                ops.conv2d_pair(first, second, head)
                 torch.cuda.synchronize()
                 assert torch.equal(out_a, ref_a), (ca, cb, order, pair)
                 assert torch.equal(out_b, ref_b), (ca, cb, order, pair)
