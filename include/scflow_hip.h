@@ -754,6 +754,21 @@ int scflow_conv_wgrad(const scflow_wgrad_args* args, void* stream);
  * images (it sizes the partial sums for any segment count). */
 int scflow_conv_wgrad_batched(const scflow_wgrad_args* args, int segs, const float* const* dys,
                               const float* const* src0s, const float* const* src1s, void* stream);
+/* scflow_conv_wgrad_plan: host-only — what the weight-gradient launch plan (plan_wgrad,
+ * train.hip) decides for `walk`, the argument struct with n = ALL segments' images (what
+ * scflow_conv_wgrad_workspace takes), cut into `segs` equal segments; nothing is launched or
+ * dereferenced.  segs 1..8: a launch — *kind = the kernel family (SCFLOW_WGRAD_*; NONE when the
+ * arguments are invalid or no family takes the shape), *floats = the workspace that launch needs,
+ * returns the status scflow_conv_wgrad / _batched answer before launching (SCFLOW_EINVAL for a
+ * walk->workspace_floats below *floats, with kind and floats still reported).  segs 0: the
+ * workspace query — pointers may be NULL, *floats = the bound that holds for any segment count. */
+int scflow_conv_wgrad_plan(const scflow_wgrad_args* walk, int segs, int* kind, long long* floats);
+#define SCFLOW_WGRAD_NONE 0
+#define SCFLOW_WGRAD_THIN 1   /* wgrad_thin_kernel: ≤ 4 channels on one side, kernels up to 5×5 */
+#define SCFLOW_WGRAD_WINO 2   /* wgrad_wino_kernel: Winograd F(2×2,3×3), 3×3 stride 1 pad 1     */
+#define SCFLOW_WGRAD_WINO5 3  /* wgrad_wino5_kernel: Winograd F(4,5), 1×5 / 5×1                 */
+#define SCFLOW_WGRAD_1X1 4    /* wgrad_1x1_kernel: 1×1 stride 1–2, 128 × 128 tiles              */
+#define SCFLOW_WGRAD_GEMM 5   /* wgrad_kernel: the direct implicit GEMM                         */
 int scflow_corr_lookup_backward(const float* dout, int out_layout, int out_stride, const float* flow,
                                 int flow_layout, float* dpyr, int n, int h, int w, int num_levels,
                                 int radius, void* stream);

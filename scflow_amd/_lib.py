@@ -27,6 +27,8 @@ CONV_WINO4 = 4  # scflow_conv_args.bk: Winograd F(4x4,3x3) packing/kernel (SCFLO
  PLAN_SMALLCIN_TILED, PLAN_SMALLCIN_GENERIC, PLAN_THINZ, PLAN_THIN_FULL, PLAN_THIN_CHUNKED,
  PLAN_THIN_GENERIC) = range(14)
 PAIR_NONE, PAIR_THIN, PAIR_SMALLCIN, PAIR_WINO = range(4)
+# scflow_conv_wgrad_plan: SCFLOW_WGRAD_* (the weight gradient's kernel family)
+WGRAD_NONE, WGRAD_THIN, WGRAD_WINO, WGRAD_WINO5, WGRAD_1X1, WGRAD_GEMM = range(6)
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 ABI_VERSION = 4  # SCFLOW_ABI_VERSION of include/scflow_hip.h this binding mirrors
 PNP_MAX_HYPS = 256  # SCFLOW_PNP_MAX_HYPS
@@ -242,6 +244,8 @@ SIGNATURES = {
     "scflow_conv_wgrad_workspace": (c_int, [ctypes.POINTER(WgradArgs), ctypes.POINTER(c_ll)]),
     "scflow_conv_wgrad": (c_int, [ctypes.POINTER(WgradArgs), c_vp]),
     "scflow_conv_wgrad_batched": (c_int, [ctypes.POINTER(WgradArgs), c_int, c_vp, c_vp, c_vp, c_vp]),
+    "scflow_conv_wgrad_plan": (c_int, [ctypes.POINTER(WgradArgs), c_int, ctypes.POINTER(c_int),
+                                       ctypes.POINTER(c_ll)]),
     "scflow_im2col": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                               c_int, c_vp]),
     "scflow_im2col_ex": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

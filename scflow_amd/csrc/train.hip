@@ -338,13 +338,6 @@ __device__ __forceinline__ const float* wg_pick(const float* const (&arr)[WG_MAX
   return p;
 }
 
-inline void wg_single_seg(const scflow_wgrad_args& a, WgSegs* s) {
-  s->nimg = a.n;
-  s->dy[0] = a.dy;
-  s->src0[0] = a.src0;
-  s->src1[0] = a.src1;
-}
-
 struct WgParams {
   scflow_wgrad_args a;
   int oh, ow, tr, tc, ltc, hr, hc, cp, nchunks, cps, co_tiles, copad, cinp, wco;
@@ -727,8 +720,8 @@ struct WtParams {
   WgSegs sg;
 };
 
-// nseg = 0: the workspace query (the whole walk as one segment, rows for any segment count)
-bool wthin_geometry(const scflow_wgrad_args& a, WtParams* P, int nseg = 1) {
+// segs = 0: the workspace query (plan_wgrad) — the walk as one segment, rows for any count
+bool wthin_geometry(const scflow_wgrad_args& a, int segs, WtParams* P, long long* floats) {
   static EnvSwitch wthin_sw("SCFLOW_WGRAD_THIN", 1);
   if (!wthin_sw.get()) return false;
   const int cin = a.cin0 + a.cin1;
@@ -759,12 +752,14 @@ bool wthin_geometry(const scflow_wgrad_args& a, WtParams* P, int nseg = 1) {
   long long ppb = (pix + 511) / 512;
   if (ppb < 64) ppb = 64;
   P->ppb = (int)ppb;
-  const int ns = nseg < 1 ? 1 : nseg;
+  const int ns = segs < 1 ? 1 : segs;
   P->nseg = ns;
   P->nimg = a.n / ns;
   const long long spix = (long long)P->nimg * P->oh * P->ow;
   P->nbp = (int)((spix + ppb - 1) / ppb);
-  if (nseg == 0) P->nbp += WG_MAXSEG;  // the query: ns·⌈spix/ppb⌉ ≤ ⌈pix/ppb⌉ + ns
+  if (segs == 0) P->nbp += WG_MAXSEG;  // the query: ns·⌈spix/ppb⌉ ≤ ⌈pix/ppb⌉ + ns
+  const long long rows = (long long)P->nseg * P->nbp;
+  *floats = rows * a.cout * P->cin * a.kh * a.kw + rows * a.cout;
   return true;
 }
 
@@ -902,15 +897,8 @@ __global__ __launch_bounds__(256) void wthin_reduce_kernel(const float* __restri
   }
 }
 
-long long wthin_workspace(const WtParams& P) {
-  const scflow_wgrad_args& a = P.a;
-  const long long rows = (long long)P.nseg * P.nbp;
-  return rows * a.cout * P.cin * a.kh * a.kw + rows * a.cout;
-}
-
 int wthin_launch(const WtParams& P, hipStream_t st) {
   const scflow_wgrad_args& a = P.a;
-  if (a.workspace_floats < wthin_workspace(P)) return SCFLOW_EINVAL;
   const bool thin_co = P.thin_co != 0;
   const int tn = thin_co ? a.cout : P.cin;
   const int rows = P.nseg * P.nbp;
@@ -1805,51 +1793,26 @@ SCFLOW_API int scflow_gru_gate_backward_r(const float* drh, int sdrh, const floa
   return scflow_launch_status();
 }
 
-SCFLOW_API int scflow_conv_wgrad_workspace(const scflow_wgrad_args* args, long long* floats) {
-  if (!args || !floats) return SCFLOW_EINVAL;
-  WtParams Q;
-  if (wthin_geometry(*args, &Q, 0)) {  // rows for a batched call of any segment count
-    *floats = wthin_workspace(Q);
-    return SCFLOW_OK;
-  }
-  WwParams R;
-  if (wwino_geometry(*args, &R)) {
-    *floats = wwino_workspace(R);
-    return SCFLOW_OK;
-  }
-  W5wParams R5;
-  if (wwino5_geometry(*args, &R5)) {
-    *floats = wwino5_workspace(R5);
-    return SCFLOW_OK;
-  }
-  W1Params R1;
-  if (w1_geometry(*args, 1, &R1)) {
-    *floats = w1_workspace(R1);
-    return SCFLOW_OK;
-  }
-  WgParams P;
-  int splits = 0;
-  if (!wgrad_geometry(*args, &P, &splits)) return SCFLOW_EUNSUPPORTED;
-  const int taps = args->kh * args->kw;
-  *floats = (long long)splits * P.copad * taps * P.cinp + (long long)splits * P.copad;
-  return SCFLOW_OK;
-}
+// ---------------------------------------------------------------------------------------------
+// The weight-gradient launch plan: plan_wgrad decides, launch_wgrad launches, and the three entry
+// points (workspace query, batched launch, its one-segment case) are calls of the two.
+//
+// wgrad_kernel's variant for a geometry: float4 loads (vec), double-buffered LDS (db2), two wave
+// sets per chunk (ks2), the dynamic LDS and the split count — the last step of its planning
+struct WgVariant {
+  int splits;
+  bool vec, db2, ks2;
+  size_t lds;
+};
 
-// the direct implicit-GEMM weight gradient (wgrad_kernel) over the segments sg: geometry, the
-// variant's launch and the split reduction
-static int wgrad_direct_launch(const scflow_wgrad_args& a, const WgSegs& sg, hipStream_t st) {
-  WgParams P;
-  int splits = 0;
-  if (!wgrad_geometry(a, &P, &splits)) return SCFLOW_EUNSUPPORTED;
-  P.sg = sg;
+bool wgemm_geometry(const scflow_wgrad_args& a, WgParams* Pp, WgVariant* V, long long* floats) {
+  if (!wgrad_geometry(a, Pp, &V->splits)) return false;
+  const WgParams& P = *Pp;
   const int taps = a.kh * a.kw;
-  const long long need = (long long)splits * P.copad * taps * P.cinp + (long long)splits * P.copad;
-  if (a.workspace_floats < need) return SCFLOW_EINVAL;
-  float* slab = a.workspace;
-  float* bslab = a.db ? a.workspace + (size_t)splits * P.copad * taps * P.cinp : nullptr;
-  const bool vec = a.cout % 4 == 0 && a.sdy % 4 == 0 && aligned16(a.dy) && a.cin0 % 4 == 0 &&
-                   a.s0 % 4 == 0 && aligned16(a.src0) &&
-                   (a.cin1 == 0 || (a.cin1 % 4 == 0 && a.s1 % 4 == 0 && aligned16(a.src1)));
+  *floats = (long long)V->splits * P.copad * taps * P.cinp + (long long)V->splits * P.copad;
+  V->vec = a.cout % 4 == 0 && a.sdy % 4 == 0 && aligned16(a.dy) && a.cin0 % 4 == 0 &&
+           a.s0 % 4 == 0 && aligned16(a.src0) &&
+           (a.cin1 == 0 || (a.cin1 % 4 == 0 && a.s1 % 4 == 0 && aligned16(a.src1)));
   // (3×3: one workgroup per CU; SCFLOW_WGRAD_KS=1 keeps one wave set, tuning only)
   static EnvSwitch ks_sw("SCFLOW_WGRAD_KS", 2);
   const int ks_env = ks_sw.get();
@@ -1861,12 +1824,73 @@ static int wgrad_direct_launch(const scflow_wgrad_args& a, const WgSegs& sg, hip
   const size_t lds1 = sizeof(float) * (size_t)(P.cp + P.hr * P.hc) * WT;
   const bool ks5 = taps == 5 && (ks5_env == 2 || (ks5_env == 1 && a.cout <= 128));
   const int occ = taps >= 9 || ks5 ? 1 : 2;
-  const bool db2 = vec && 2 * lds1 * occ <= 160 * 1024;  // double-buffer if it keeps occupancy
-  const size_t lds = lds1 * (db2 ? 2 : 1);
-  if (lds > 160 * 1024) return SCFLOW_EUNSUPPORTED;
-  const dim3 grid((unsigned)(P.co_tiles * (P.cinp / WT)), (unsigned)splits);
+  V->db2 = V->vec && 2 * lds1 * occ <= 160 * 1024;  // double-buffer if it keeps occupancy
+  V->lds = lds1 * (V->db2 ? 2 : 1);
+  if (V->lds > 160 * 1024) return false;
   // two wave sets splitting each chunk's k-steps
-  const bool ks2 = vec && ((taps >= 9 && ks_env == 2) || ks5);
+  V->ks2 = V->vec && ((taps >= 9 && ks_env == 2) || ks5);
+  return true;
+}
+
+struct WgradPlan {
+  int status;        // what the entry point answers before launching (or SCFLOW_OK)
+  int kind;          // SCFLOW_WGRAD_*: which of the parameter structs below is filled
+  long long floats;  // workspace this call needs; segs = 0: the bound for any segment count
+  WtParams thin;
+  WwParams wino;
+  W5wParams wino5;
+  W1Params w1;
+  WgParams gemm;
+  WgVariant gv;
+};
+
+// `walk`: the argument struct with n = all segments' images; segs 1..8: a launch over that many
+// equal segments, 0: the workspace query (pointers may be null, floats for any segment count).
+// Decides everything and touches nothing: no launch, no attribute call, no pointer dereferenced.
+void plan_wgrad(const scflow_wgrad_args& a, int segs, WgradPlan* p) {
+  p->status = SCFLOW_EINVAL;
+  p->kind = SCFLOW_WGRAD_NONE;
+  p->floats = 0;
+  // the one argument check: shapes and strides for every entry point, pointers for launches
+  if (a.n <= 0 || a.h <= 0 || a.w <= 0 || a.cout <= 0 || a.cin0 <= 0 || a.cin1 < 0 ||
+      a.sdy < a.cout || a.s0 < a.cin0 || (a.cin1 > 0 && a.s1 < a.cin1) || a.ph < 0 || a.pw < 0)
+    return;
+  if (segs < 0 || segs > WG_MAXSEG || (segs > 0 && a.n % segs)) return;
+  if (segs > 0 && (!a.dy || !a.src0 || (a.cin1 > 0 && !a.src1) || !a.dw || !a.workspace)) return;
+  // The family order, written once.  The four special families are pairwise disjoint, so the
+  // order among them cannot matter: thin needs ≤ 4 channels on one side (cout ≤ 4, or cin ≤ 4),
+  // while both Winograd families need cout ≥ 64 and cin ≥ 16 and the 1×1 needs cout > 4 and
+  // cin > 4; those three take different kernel shapes (3×3, 1×5 / 5×1, 1×1).  Only the implicit
+  // GEMM overlaps the others (it takes their 1×1, 3×3, 1×5 and 5×1 shapes at any alignment, width
+  // and channel count it can tile), so it comes last.
+  if (wthin_geometry(a, segs, &p->thin, &p->floats))
+    p->kind = SCFLOW_WGRAD_THIN;
+  else if (wwino_geometry(a, &p->wino, &p->floats))
+    p->kind = SCFLOW_WGRAD_WINO;
+  else if (wwino5_geometry(a, &p->wino5, &p->floats))
+    p->kind = SCFLOW_WGRAD_WINO5;
+  else if (w1_geometry(a, segs, &p->w1, &p->floats))
+    p->kind = SCFLOW_WGRAD_1X1;
+  else if (wgemm_geometry(a, &p->gemm, &p->gv, &p->floats))
+    p->kind = SCFLOW_WGRAD_GEMM;
+  else {
+    p->status = SCFLOW_EUNSUPPORTED;
+    p->floats = 0;
+    return;
+  }
+  p->status = segs > 0 && a.workspace_floats < p->floats ? SCFLOW_EINVAL : SCFLOW_OK;
+}
+
+// the direct implicit-GEMM weight gradient (wgrad_kernel): the planned variant's launch and the
+// split reduction
+static int wgrad_direct_launch(const WgParams& P, const WgVariant& V, hipStream_t st) {
+  const scflow_wgrad_args& a = P.a;
+  const int taps = a.kh * a.kw, splits = V.splits;
+  const bool vec = V.vec, db2 = V.db2, ks2 = V.ks2;
+  const size_t lds = V.lds;
+  float* slab = a.workspace;
+  float* bslab = a.db ? a.workspace + (size_t)splits * P.copad * taps * P.cinp : nullptr;
+  const dim3 grid((unsigned)(P.co_tiles * (P.cinp / WT)), (unsigned)splits);
 #define SCFLOW_WG(KH_, KW_, S_)                                                                  \
   if (a.kh == KH_ && a.kw == KW_ && a.stride == S_) {                                            \
     if (KH_ * KW_ >= 5 && ks2) {                                                                 \
@@ -1902,86 +1926,76 @@ static int wgrad_direct_launch(const scflow_wgrad_args& a, const WgSegs& sg, hip
   return scflow_launch_status();
 }
 
-SCFLOW_API int scflow_conv_wgrad_batched(const scflow_wgrad_args* args, int segs,
-                                         const float* const* dys, const float* const* src0s,
-                                         const float* const* src1s, void* stream) {
-  if (!args || segs < 1 || segs > WG_MAXSEG || !dys || !src0s || (args->cin1 > 0 && !src1s) ||
-      !args->dw || !args->workspace || args->n <= 0)
-    return SCFLOW_EINVAL;
-  for (int i = 0; i < segs; ++i)
-    if (!dys[i] || !src0s[i] || !aligned16(dys[i]) || !aligned16(src0s[i]) ||
-        (args->cin1 > 0 && (!src1s[i] || !aligned16(src1s[i]))))
-      return SCFLOW_EINVAL;
-  scflow_wgrad_args t = *args;  // the walk: all segments' images in a row
-  t.n = args->n * segs;
-  t.dy = dys[0];
-  t.src0 = src0s[0];
-  t.src1 = args->cin1 > 0 ? src1s[0] : nullptr;
+// launch an accepted plan over the segments sg
+static int launch_wgrad(WgradPlan& p, const WgSegs& sg, hipStream_t st) {
+  switch (p.kind) {
+    case SCFLOW_WGRAD_THIN: p.thin.sg = sg; return wthin_launch(p.thin, st);
+    case SCFLOW_WGRAD_WINO: p.wino.sg = sg; return wwino_launch(p.wino, st);
+    case SCFLOW_WGRAD_WINO5: p.wino5.sg = sg; return wwino5_launch(p.wino5, st);
+    case SCFLOW_WGRAD_1X1: p.w1.sg = sg; return w1_launch(p.w1, st);
+    case SCFLOW_WGRAD_GEMM: p.gemm.sg = sg; return wgrad_direct_launch(p.gemm, p.gv, st);
+  }
+  return SCFLOW_EUNSUPPORTED;
+}
+
+SCFLOW_API int scflow_conv_wgrad_workspace(const scflow_wgrad_args* args, long long* floats) {
+  if (!args || !floats) return SCFLOW_EINVAL;
+  WgradPlan p;
+  plan_wgrad(*args, 0, &p);
+  if (p.status == SCFLOW_OK) *floats = p.floats;
+  return p.status;
+}
+
+// validate, plan and launch: `seg` describes one segment (n images), segment i at dys[i] /
+// src0s[i] / src1s[i]
+static int wgrad_segments(const scflow_wgrad_args& seg, int segs, const float* const* dys,
+                          const float* const* src0s, const float* const* src1s, hipStream_t st) {
   WgSegs sg;
-  sg.nimg = args->n;
+  sg.nimg = seg.n;
   for (int i = 0; i < WG_MAXSEG; ++i) {
     const int j = i < segs ? i : 0;
     sg.dy[i] = dys[j];
     sg.src0[i] = src0s[j];
-    sg.src1[i] = args->cin1 > 0 ? src1s[j] : nullptr;
+    sg.src1[i] = seg.cin1 > 0 ? src1s[j] : nullptr;
+    if (!sg.dy[i] || !sg.src0[i] || (seg.cin1 > 0 && !sg.src1[i])) return SCFLOW_EINVAL;
   }
-  WwParams R;
-  if (wwino_geometry(t, &R)) {
-    if (t.workspace_floats < wwino_workspace(R)) return SCFLOW_EINVAL;
-    R.sg = sg;
-    return wwino_launch(R, (hipStream_t)stream);
-  }
-  W5wParams R5;
-  if (wwino5_geometry(t, &R5)) {
-    if (t.workspace_floats < wwino5_workspace(R5)) return SCFLOW_EINVAL;
-    R5.sg = sg;
-    return wwino5_launch(R5, (hipStream_t)stream);
-  }
-  WtParams Q;
-  if (wthin_geometry(t, &Q, segs)) {
-    Q.sg = sg;
-    return wthin_launch(Q, (hipStream_t)stream);
-  }
-  W1Params R1;
-  if (w1_geometry(t, segs, &R1)) {
-    R1.sg = sg;
-    return w1_launch(R1, (hipStream_t)stream);
-  }
-  return wgrad_direct_launch(t, sg, (hipStream_t)stream);
+  scflow_wgrad_args walk = seg;  // all segments' images in a row, the first one's bases
+  walk.n = seg.n > 0 ? seg.n * segs : 0;
+  walk.dy = sg.dy[0];
+  walk.src0 = sg.src0[0];
+  walk.src1 = sg.src1[0];
+  WgradPlan p;
+  plan_wgrad(walk, segs, &p);
+  return p.status != SCFLOW_OK ? p.status : launch_wgrad(p, sg, st);
 }
 
+SCFLOW_API int scflow_conv_wgrad_batched(const scflow_wgrad_args* args, int segs,
+                                         const float* const* dys, const float* const* src0s,
+                                         const float* const* src1s, void* stream) {
+  if (!args || segs < 1 || segs > WG_MAXSEG || !dys || !src0s || (args->cin1 > 0 && !src1s))
+    return SCFLOW_EINVAL;
+  // every segment at a float4 boundary: the plan reads the alignment off the first one
+  for (int i = 0; i < segs; ++i)
+    if (!aligned16(dys[i]) || !aligned16(src0s[i]) || (args->cin1 > 0 && !aligned16(src1s[i])))
+      return SCFLOW_EINVAL;
+  return wgrad_segments(*args, segs, dys, src0s, src1s, (hipStream_t)stream);
+}
+
+// the one-segment case; its pointers may be unaligned (the implicit GEMM's scalar variant)
 SCFLOW_API int scflow_conv_wgrad(const scflow_wgrad_args* args, void* stream) {
   if (!args) return SCFLOW_EINVAL;
-  const scflow_wgrad_args& a = *args;
-  if (!a.dy || !a.src0 || !a.dw || !a.workspace || a.n <= 0 || a.h <= 0 || a.w <= 0 ||
-      a.cout <= 0 || a.cin0 <= 0 || a.cin1 < 0 || (a.cin1 > 0 && !a.src1) || a.sdy < a.cout ||
-      a.s0 < a.cin0 || (a.cin1 > 0 && a.s1 < a.cin1) || a.ph < 0 || a.pw < 0)
-    return SCFLOW_EINVAL;
-  WtParams Q;
-  if (wthin_geometry(a, &Q)) {
-    wg_single_seg(a, &Q.sg);
-    return wthin_launch(Q, (hipStream_t)stream);
-  }
-  WwParams R;
-  if (wwino_geometry(a, &R)) {
-    if (a.workspace_floats < wwino_workspace(R)) return SCFLOW_EINVAL;
-    wg_single_seg(a, &R.sg);
-    return wwino_launch(R, (hipStream_t)stream);
-  }
-  W5wParams R5;
-  if (wwino5_geometry(a, &R5)) {
-    if (a.workspace_floats < wwino5_workspace(R5)) return SCFLOW_EINVAL;
-    wg_single_seg(a, &R5.sg);
-    return wwino5_launch(R5, (hipStream_t)stream);
-  }
-  W1Params R1;
-  if (w1_geometry(a, 1, &R1)) {
-    wg_single_seg(a, &R1.sg);
-    return w1_launch(R1, (hipStream_t)stream);
-  }
-  WgSegs sg;
-  wg_single_seg(a, &sg);
-  return wgrad_direct_launch(a, sg, (hipStream_t)stream);
+  return wgrad_segments(*args, 1, &args->dy, &args->src0, &args->src1, (hipStream_t)stream);
+}
+
+// Host-only: what plan_wgrad decides for the walk cut into segs segments (0: the query).
+SCFLOW_API int scflow_conv_wgrad_plan(const scflow_wgrad_args* walk, int segs, int* kind,
+                                      long long* floats) {
+  if (!walk || !kind || !floats) return SCFLOW_EINVAL;
+  WgradPlan p;
+  plan_wgrad(*walk, segs, &p);
+  *kind = p.kind;
+  *floats = p.floats;
+  return p.status;
 }
 
 SCFLOW_API int scflow_im2col_ex(const float* x, int sx, float* cols, int n, int h, int w, int cin,

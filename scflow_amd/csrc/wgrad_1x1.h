@@ -27,7 +27,7 @@ struct W1Params {
   int nseg, spl;     // segments, splits per segment (grid.y = nseg · spl)
   long long seg_pix; // output pixels per segment
   long long pps;     // pixels per split (a multiple of W1_P)
-  long long max_splits;  // the workspace bound (any segment count ≤ WG_MAXSEG)
+  long long max_splits;  // ≥ nseg · spl for any segment count ≤ WG_MAXSEG (the workspace query)
   WgSegs sg;
 };
 
@@ -156,7 +156,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_1x1_kernel(W1Params P, float* __
   }
 }
 
-bool w1_geometry(const scflow_wgrad_args& a, int nseg, W1Params* P) {
+// segs = 0: the workspace query (plan_wgrad) — the walk as one segment, floats for any count
+bool w1_geometry(const scflow_wgrad_args& a, int segs, W1Params* P, long long* floats) {
+  const int nseg = segs < 1 ? 1 : segs;
   static EnvSwitch w1_sw("SCFLOW_WGRAD_1X1", 1);
   if (!w1_sw.get()) return false;
   if (a.kh != 1 || a.kw != 1 || a.ph != 0 || a.pw != 0 || (a.stride != 1 && a.stride != 2))
@@ -183,7 +185,7 @@ bool w1_geometry(const scflow_wgrad_args& a, int nseg, W1Params* P) {
   const long long per_split = (long long)P->copad * P->cinp;
   if (want > (8LL << 20) / per_split) want = (8LL << 20) / per_split;
   if (want < 1) want = 1;
-  // the workspace query sees the whole walk as one segment: size it for any segment count
+  // nseg · spl ≤ max(want, nseg): nseg · ⌊want / nseg⌋ ≤ want, or spl = 1
   P->max_splits = want > WG_MAXSEG ? want : WG_MAXSEG;
   long long spl = want / nseg;
   const long long max_spl = (P->seg_pix + 4 * W1_P - 1) / (4 * W1_P);
@@ -192,19 +194,14 @@ bool w1_geometry(const scflow_wgrad_args& a, int nseg, W1Params* P) {
   P->pps = (P->seg_pix + spl - 1) / spl;
   P->pps = (P->pps + W1_P - 1) / W1_P * W1_P;
   P->spl = (int)((P->seg_pix + P->pps - 1) / P->pps);
+  *floats = (segs == 0 ? P->max_splits : (long long)nseg * P->spl) *
+            ((long long)P->copad * P->cinp + P->copad);
   return true;
-}
-
-// floats of partial sums for any segment count (scflow_conv_wgrad_workspace)
-long long w1_workspace(const W1Params& P) {
-  return P.max_splits * ((long long)P.copad * P.cinp + P.copad);
 }
 
 int w1_launch(const W1Params& P, hipStream_t st) {
   const scflow_wgrad_args& a = P.a;
   const int splits = P.nseg * P.spl;
-  if (a.workspace_floats < (long long)splits * ((long long)P.copad * P.cinp + P.copad))
-    return SCFLOW_EINVAL;
   float* slab = a.workspace;
   float* bslab = a.db ? a.workspace + (size_t)splits * P.copad * P.cinp : nullptr;
   const dim3 grid((unsigned)(P.co_tiles * P.ci_tiles), (unsigned)splits);

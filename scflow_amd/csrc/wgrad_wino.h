@@ -442,8 +442,10 @@ __global__ __launch_bounds__(256) void wwino_reduce_kernel(
   }
 }
 
+int wwino_splits(const WwParams& P) { return (P.nchunks + P.cps - 1) / P.cps; }
+
 // shapes: 3×3, stride 1, pad 1, h % 4 == 0, w % 32 == 0, float4-aligned channel groups
-bool wwino_geometry(const scflow_wgrad_args& a, WwParams* P) {
+bool wwino_geometry(const scflow_wgrad_args& a, WwParams* P, long long* floats) {
   static EnvSwitch wwino_sw("SCFLOW_WGRAD_WINO", 1);
   if (!wwino_sw.get()) return false;
   const int cin = a.cin0 + a.cin1;
@@ -469,14 +471,9 @@ bool wwino_geometry(const scflow_wgrad_args& a, WwParams* P) {
   if (want > P->nchunks) want = P->nchunks;
   if (want < 1) want = 1;
   P->cps = (int)((P->nchunks + want - 1) / want);
+  const long long s = wwino_splits(*P);
+  *floats = s * 16 * P->copad * P->cinp + s * P->copad;
   return true;
-}
-
-int wwino_splits(const WwParams& P) { return (P.nchunks + P.cps - 1) / P.cps; }
-
-long long wwino_workspace(const WwParams& P) {
-  const long long s = wwino_splits(P);
-  return s * 16 * P.copad * P.cinp + s * P.copad;
 }
 
 int wwino_launch(const WwParams& P, hipStream_t st) {

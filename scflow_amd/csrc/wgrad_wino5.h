@@ -371,9 +371,11 @@ __global__ __launch_bounds__(256) void wwino5_reduce_kernel(
   }
 }
 
+int wwino5_splits(const W5wParams& P) { return (P.nchunks + P.cps - 1) / P.cps; }
+
 // shapes: 1×5 (pad 0, 2) or 5×1 (pad 2, 0), stride 1, h % 4 == 0, w % 32 == 0, float4-aligned
 // channel groups, cout ≥ 64 (narrower outputs stay on wgrad_kernel / wthin)
-bool wwino5_geometry(const scflow_wgrad_args& a, W5wParams* P) {
+bool wwino5_geometry(const scflow_wgrad_args& a, W5wParams* P, long long* floats) {
   static EnvSwitch wwino5_sw("SCFLOW_WGRAD_WINO5", 1);
   if (!wwino5_sw.get()) return false;
   const int cin = a.cin0 + a.cin1;
@@ -405,14 +407,9 @@ bool wwino5_geometry(const scflow_wgrad_args& a, W5wParams* P) {
   if (want > P->nchunks) want = P->nchunks;
   if (want < 1) want = 1;
   P->cps = (int)((P->nchunks + want - 1) / want);
+  const long long s = wwino5_splits(*P);
+  *floats = s * 8 * P->copad * P->cinp + s * P->copad;
   return true;
-}
-
-int wwino5_splits(const W5wParams& P) { return (P.nchunks + P.cps - 1) / P.cps; }
-
-long long wwino5_workspace(const W5wParams& P) {
-  const long long s = wwino5_splits(P);
-  return s * 8 * P.copad * P.cinp + s * P.copad;
 }
 
 int wwino5_launch(const W5wParams& P, hipStream_t st) {

@@ -1507,39 +1507,17 @@ def conv_wgrad(dy: Tensor, src0, src1: Optional[Chan], dw: Tensor, db: Optional[
     """dw [cout, cin0+cin1, kh, kw] (+)= conv weight gradient; db [cout] (+)= Σ dy (optional).
     dy: [n·oh·ow, cout] contiguous; src0 / src1: channels-last tensors or ``Chan`` slices.
     Raises ScflowError(SCFLOW_EUNSUPPORTED) for shapes outside the kernel's set."""
-    _require(dy, "dy")
-    _require(dw, "dw")
-    srcs = []
-    for nm, x in (("src0", src0), ("src1", src1)):
-        if x is None:
-            srcs.append((None, 0, 0))
-        elif isinstance(x, Chan):
-            _require(x.buf, nm)
-            srcs.append((x.ptr, x.c, x.stride))
-        else:
-            _require(x, nm)
-            srcs.append((x.data_ptr(), x.shape[-1], x.shape[-1]))
-    a = _lib.WgradArgs()
-    a.dy, a.sdy = dy.data_ptr(), dy.shape[-1]
-    (a.src0, a.cin0, a.s0), (a.src1, a.cin1, a.s1) = srcs
-    a.dw, a.db = dw.data_ptr(), _p(db)
-    a.n, a.h, a.w, a.cout, a.kh, a.kw = n, h, w, dy.shape[-1], kh, kw
-    a.stride, a.ph, a.pw, a.accumulate = stride, ph, pw, int(accumulate)
-    lib = _lib.load()
-    need = ctypes.c_longlong(0)
-    check(lib.scflow_conv_wgrad_workspace(ctypes.byref(a), ctypes.byref(need)),
-          "scflow_conv_wgrad_workspace")
-    ws = torch.empty(max(1, need.value), device=dy.device)
-    a.workspace, a.workspace_floats = ws.data_ptr(), need.value
-    check(lib.scflow_conv_wgrad(ctypes.byref(a), _stream(dy)), "scflow_conv_wgrad")
+    a, _, _ = _wgrad_args([dy], [src0], None if src1 is None else [src1], dw, db, n, h, w, kh, kw,
+                          stride, ph, pw, accumulate)
+    check(_lib.load().scflow_conv_wgrad(ctypes.byref(a), _stream(dw)), "scflow_conv_wgrad")
 
 
-def conv_wgrad_batched(dys: List[Tensor], src0s: list, src1s: Optional[list], dw: Tensor,
-                       db: Optional[Tensor], n: int, h: int, w: int, kh: int, kw: int, stride: int,
-                       ph: int, pw: int, accumulate: bool = False) -> None:
-    """dw (+)= Σ_i weight gradient of segment i (dys[i] with src0s[i] / src1s[i], each n images
-    of h×w) in one launch (scflow_conv_wgrad_batched; ≤ 8 equally shaped segments; the Winograd,
-    1×1, implicit-GEMM and thin kernels — ScflowError(SCFLOW_EUNSUPPORTED) otherwise)."""
+def _wgrad_args(dys: List[Tensor], src0s: list, src1s: Optional[list], dw: Tensor,
+                db: Optional[Tensor], n: int, h: int, w: int, kh: int, kw: int, stride: int,
+                ph: int, pw: int, accumulate: bool):
+    """(walk, (dys, src0s, src1s) pointer arrays, workspace) of a weight gradient over len(dys)
+    segments of n images: the filled WgradArgs of the whole walk (n·segs images at the first
+    segment's bases) with the workspace scflow_conv_wgrad_workspace asks for, allocated."""
     segs = len(dys)
     if not 1 <= segs <= 8 or len(src0s) != segs or (src1s is not None and len(src1s) != segs):
         raise ValueError(f"conv_wgrad_batched: 1..8 segments with matching sources, got {segs}")
@@ -1567,19 +1545,39 @@ def conv_wgrad_batched(dys: List[Tensor], src0s: list, src1s: Optional[list], dw
     a.dw, a.db = dw.data_ptr(), _p(db)
     a.n, a.h, a.w, a.cout, a.kh, a.kw = n * segs, h, w, dys[0].shape[-1], kh, kw
     a.stride, a.ph, a.pw, a.accumulate = stride, ph, pw, int(accumulate)
-    lib = _lib.load()
     need = ctypes.c_longlong(0)
-    check(lib.scflow_conv_wgrad_workspace(ctypes.byref(a), ctypes.byref(need)),
+    check(_lib.load().scflow_conv_wgrad_workspace(ctypes.byref(a), ctypes.byref(need)),
           "scflow_conv_wgrad_workspace")
     ws = torch.empty(max(1, need.value), device=dw.device)
     a.workspace, a.workspace_floats = ws.data_ptr(), need.value
-    a.n = n
     arr = ctypes.c_void_p * segs
-    p_dy = arr(*[t.data_ptr() for t in dys])
-    p_s0 = arr(*[d[0] for d in d0])
-    p_s1 = arr(*[d[0] for d in d1]) if d1 is not None else None
-    check(lib.scflow_conv_wgrad_batched(ctypes.byref(a), segs, p_dy, p_s0, p_s1, _stream(dw)),
+    ptrs = (arr(*[t.data_ptr() for t in dys]), arr(*[d[0] for d in d0]),
+            arr(*[d[0] for d in d1]) if d1 is not None else None)
+    return a, ptrs, ws
+
+
+def conv_wgrad_batched(dys: List[Tensor], src0s: list, src1s: Optional[list], dw: Tensor,
+                       db: Optional[Tensor], n: int, h: int, w: int, kh: int, kw: int, stride: int,
+                       ph: int, pw: int, accumulate: bool = False) -> None:
+    """dw (+)= Σ_i weight gradient of segment i (dys[i] with src0s[i] / src1s[i], each n images
+    of h×w) in one launch (scflow_conv_wgrad_batched; ≤ 8 equally shaped segments; the Winograd,
+    1×1, implicit-GEMM and thin kernels — ScflowError(SCFLOW_EUNSUPPORTED) otherwise)."""
+    a, ptrs, _ = _wgrad_args(dys, src0s, src1s, dw, db, n, h, w, kh, kw, stride, ph, pw, accumulate)
+    a.n = n  # the launch takes one segment's images
+    check(_lib.load().scflow_conv_wgrad_batched(ctypes.byref(a), len(dys), *ptrs, _stream(dw)),
           "scflow_conv_wgrad_batched")
+
+
+def conv_wgrad_plan(dys: List[Tensor], src0s: list, src1s: Optional[list], dw: Tensor,
+                    db: Optional[Tensor], n: int, h: int, w: int, kh: int, kw: int, stride: int,
+                    ph: int, pw: int, accumulate: bool = False) -> Tuple[int, int]:
+    """scflow_conv_wgrad_plan (host-only) for conv_wgrad_batched's arguments: (the kernel family
+    ``_lib.WGRAD_*`` that call launches, the workspace floats it needs); nothing is launched."""
+    a, _, _ = _wgrad_args(dys, src0s, src1s, dw, db, n, h, w, kh, kw, stride, ph, pw, accumulate)
+    kind, floats = ctypes.c_int(0), ctypes.c_longlong(0)
+    check(_lib.load().scflow_conv_wgrad_plan(ctypes.byref(a), len(dys), ctypes.byref(kind),
+                                             ctypes.byref(floats)), "scflow_conv_wgrad_plan")
+    return kind.value, floats.value
 
 
 def im2col(x, n: int, h: int, w: int, cin: int, kh: int, kw: int, stride: int, ph: int, pw: int,

@@ -342,17 +342,28 @@ def _batchable(kh: int, kw: int, s: int, ph: int, pw: int) -> bool:
     return (kh, kw) in ((1, 1), (3, 3), (1, 5), (5, 1), (7, 7)) and s in (1, 2)
 
 
-def _use_holder(w: Tensor) -> dict:
+class _Uses:
+    """One weight's uses in one forward pass: how many convs ran it (``uses``), how many of their
+    backwards have arrived (``seen``) with what they recorded (``items``), and the callable that
+    sums the items into the parameters' gradient sinks (``flush``)."""
+    __slots__ = ("fwd", "uses", "seen", "items", "flush")
+
+    def __init__(self, fwd: int):
+        self.fwd, self.uses, self.seen, self.items, self.flush = fwd, 0, 0, [], None
+
+
+def _use_holder(w: Tensor) -> Optional[_Uses]:
     """The per-forward-pass use record of weight ``w`` (module parameters persist across steps:
-    the record restarts with each forward pass, begin_forward)."""
+    the record restarts with each forward pass, begin_forward); None for a tensor that takes no
+    attribute."""
     hold = getattr(w, "_scflow_uses", None)
-    if hold is None or hold["fwd"] != _FWD_ID:
-        hold = {"fwd": _FWD_ID, "uses": 0, "seen": 0, "items": [], "buf": None}
+    if hold is None or hold.fwd != _FWD_ID:
+        hold = _Uses(_FWD_ID)
         try:
             w._scflow_uses = hold
         except (AttributeError, RuntimeError):
             return None
-    hold["uses"] += 1
+    hold.uses += 1
     return hold
 
 
@@ -436,34 +447,49 @@ def _concat_gemm_wgrad(items, w: Tensor, with_bias: bool, dw: Tensor, db: Option
 _PENDING: dict = {}  # id(holder) → holder with recorded uses not yet summed
 
 
-def _defer(hold: dict, item, flush) -> None:
+def _defer(hold: _Uses, item, flush) -> None:
     """Record this use's item; at the last use of the pass, ``flush(items)`` adds the summed weight
     gradient into the parameter's gradient sinks (direct_weight_grads)."""
-    if not hold["items"]:
-        hold["flush"] = flush
+    if not hold.items:
+        hold.flush = flush
         _PENDING[id(hold)] = hold
-    hold["items"].append(item)
-    hold["seen"] += 1
-    if hold["seen"] >= hold["uses"]:
+    hold.items.append(item)
+    hold.seen += 1
+    if hold.seen >= hold.uses:
         _flush_holder(hold)
 
 
-def _deferred_wgrad(hold: dict, w: Tensor, item, with_bias: bool, s: int, ph: int, pw: int,
-                    sink_w: Tensor, sink_b: Optional[Tensor]) -> None:
-    """Record this conv use's (g, x0, x1); on the last use, one batched weight gradient over all
-    of them, added into the sinks."""
-    _defer(hold, item, lambda items: _flush_wgrad(items, w, with_bias, sink_w, sink_b, True, s,
-                                                  ph, pw))
-
-
-def _flush_holder(hold: dict) -> None:
-    items = hold["items"]
+def _flush_holder(hold: _Uses) -> None:
+    items = hold.items
     if items:
-        hold["flush"](items)
-    hold["items"] = []
-    hold["seen"] = 0
-    hold["buf"] = None
+        hold.flush(items)
+    hold.items, hold.seen, hold.flush = [], 0, None  # (the callable may hold activations)
     _PENDING.pop(id(hold), None)
+
+
+def _param_grads(wants, params, hold: Optional[_Uses], item, summed, defer: bool = True) -> list:
+    """Where a layer's parameter gradients go — the one rule of every backward that computes
+    them.  ``wants[i]``: autograd needs parameter ``params[i]``'s gradient; ``item``: what this
+    use contributes; ``summed(items, sinks)`` computes the gradients of the listed uses and either
+    ADDS them into ``sinks`` (one destination per parameter, None where not wanted) or, given
+    ``sinks`` None, returns them as fresh tensors (one use only).  Returns the gradients to hand
+    to autograd, one per parameter.
+
+    All or nothing: only when EVERY wanted gradient has a sink (``_grad_sink``: inside
+    direct_weight_grads, a leaf with an allocated ``.grad``) do the gradients bypass autograd —
+    summed once at the pass's last use when the weight has several (``hold``, and ``defer``), else
+    added in place now.  Otherwise this use's gradients go back to autograd as fresh tensors."""
+    none = [None] * len(params)
+    if not any(wants):
+        return none
+    sinks = [_grad_sink(p) if wt else None for p, wt in zip(params, wants)]
+    if any(wt and sk is None for sk, wt in zip(sinks, wants)):
+        return summed([item], None)
+    if defer and hold is not None and hold.uses > 1:
+        _defer(hold, item, lambda items: summed(items, sinks))
+    else:
+        summed([item], sinks)
+    return none
 
 
 def flush_pending_wgrads() -> None:
@@ -581,21 +607,20 @@ def _conv_backward(ctx, dy):
         dx0 = dx if x1 is None else dx[..., :c0]
         dx1 = None if x1 is None else dx[..., c0:]
     want_b = ctx.has_b and ctx.needs_input_grad[3]
-    hold = getattr(ctx, "uses", None)
-    sw = _grad_sink(w) if ctx.needs_input_grad[2] else None
-    sb = _grad_sink(ctx.bias) if want_b else None
-    if (hold is not None and hold["uses"] > 1 and sw is not None and (sb is not None or not want_b)
-            and (want_b or not ctx.has_b)):
-        # a weight used by several convs of this pass (the decoder's 8 iterations), gradients
-        # added straight into the parameters: one batched weight gradient at the last use
-        _deferred_wgrad(hold, w, (gp, x0, x1), want_b, s, ph, pw, sw, sb)
-    elif ctx.needs_input_grad[2] or want_b:
-        sw = _grad_sink(w) if ctx.needs_input_grad[2] else None
-        sb = _grad_sink(ctx.bias) if want_b else None
-        if sw is not None and (sb is not None or not want_b):
-            _weight_grad(gp, x0, x1, w, s, ph, pw, want_b, dw=sw, db=sb)  # added in place
-        else:
-            dw, db = _weight_grad(gp, x0, x1, w, s, ph, pw, want_b)
+
+    def summed(items, sinks):
+        if sinks is None:
+            return list(_weight_grad(*items[0], w, s, ph, pw, want_b))
+        sw, sb = sinks
+        if sw is None:  # a frozen weight under a trained bias: dW is computed and dropped
+            sw = torch.zeros_like(w)
+        if len(items) == 1:
+            _weight_grad(*items[0], w, s, ph, pw, want_b, dw=sw, db=sb)
+        else:  # the decoder's 8 iterations: one batched weight gradient at the last use
+            _flush_wgrad(items, w, want_b, sw, sb, True, s, ph, pw)
+
+    dw, db = _param_grads((ctx.needs_input_grad[2], want_b), (w, ctx.bias),
+                          getattr(ctx, "uses", None), (gp, x0, x1), summed)
     return dx0, dx1, dw, db, dbm, None, None, None, None
 
 
@@ -643,39 +668,21 @@ class _DualConv2dNHWC(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = _conv_forward(g, None, _flip_t(wcat), None, 1, (kh - 1 - ph, kw - 1 - pw))
-        sinks = [_grad_sink(t) if t is not None and t.requires_grad else None for t in ctx.params]
-        want = [t is not None and t.requires_grad for t in ctx.params]
-        direct = all(s_ is not None or not w_ for s_, w_ in zip(sinks, want))
         with_bias = ba is not None
-        hold = ctx.uses
 
-        def flush(items, into_sinks=True):
+        def summed(items, sinks):
+            # the stacked weight's gradient over the uses in one launch, split per parameter
             tw = torch.empty_like(wcat)
             tb = torch.empty(wcat.shape[0], device=wcat.device) if with_bias else None
             _flush_wgrad(items, wcat, with_bias, tw, tb, False, 1, ph, pw)
-            return tw, tb
+            grads = [tw[:ca], tb[:ca] if with_bias else None, tw[ca:], tb[ca:] if with_bias else None]
+            if sinks is None:
+                return grads
+            for i in (0, 2, 1, 3):  # the weights, then the biases
+                if sinks[i] is not None:
+                    sinks[i] += grads[i]
 
-        if direct and hold is not None and hold["uses"] > 1:
-            def flush_sinks(items):
-                tw, tb = flush(items)
-                sw_a, sb_a, sw_b, sb_b = sinks
-                if sw_a is not None:
-                    sw_a += tw[:ca]
-                if sw_b is not None:
-                    sw_b += tw[ca:]
-                if with_bias and sb_a is not None:
-                    sb_a += tb[:ca]
-                if with_bias and sb_b is not None:
-                    sb_b += tb[ca:]
-            _defer(hold, (g, x, None), flush_sinks)
-            return dx, None, None, None, None, None, None, None
-        tw, tb = flush([(g, x, None)])
-        grads = [tw[:ca], tb[:ca] if with_bias else None, tw[ca:], tb[ca:] if with_bias else None]
-        if direct:
-            for s_, gr in zip(sinks, grads):
-                if s_ is not None and gr is not None:
-                    s_ += gr
-            grads = [None] * 4
+        grads = _param_grads(ctx.needs_input_grad[1:5], ctx.params, ctx.uses, (g, x, None), summed)
         return (dx, *grads, None, None, None)
 
 
@@ -1266,12 +1273,15 @@ def group_norm_nhwc(x: Tensor, weight: Tensor, bias: Tensor, groups: int, eps: f
 
 
 # ------------------------------------------------------------------------------- linear
-def _flush_linear(items, sink_w: Tensor, sink_b: Optional[Tensor]) -> None:
+def _flush_linear(items, sink_w: Optional[Tensor], sink_b: Optional[Tensor]) -> None:
     """dW += Σ_uses dYᵀ·X as ONE GEMM over the uses' rows (the pose head's FC layers: 8 uses of
-    16 rows each — a 16-deep GEMM per use is all launch latency), db += the column sum."""
-    dys = torch.cat([d for d, _ in items])
-    xs = torch.cat([x for _, x in items])
-    ops.gemm(dys.t(), xs, out=sink_w, beta=1.0)
+    16 rows each — a 16-deep GEMM per use is all launch latency), db += the column sum; a sink
+    that is None (a gradient not wanted) is skipped."""
+    one = len(items) == 1  # a single use: its own rows, no copy
+    dys = items[0][0] if one else torch.cat([d for d, _ in items])
+    if sink_w is not None:
+        ops.gemm(dys.t(), items[0][1] if one else torch.cat([x for _, x in items]), out=sink_w,
+                 beta=1.0)
     if sink_b is not None:
         ops.colsum(dys, sink_b, accumulate=True)
 
@@ -1291,29 +1301,19 @@ class _Linear(torch.autograd.Function):
         x, w = ctx.saved_tensors
         dy = dy.contiguous()
         dx = ops.gemm(dy, w.detach()) if ctx.needs_input_grad[0] else None
-        dw = db = None
-        want_b = ctx.has_b and ctx.needs_input_grad[2]
-        hold = getattr(ctx, "uses", None)
-        sw = _grad_sink(w) if ctx.needs_input_grad[1] else None
-        sb = _grad_sink(ctx.bias) if want_b else None
-        if (_DEFER_LINEAR and hold is not None and hold["uses"] > 1 and sw is not None
-                and (sb is not None or not want_b) and (want_b or not ctx.has_b)):
-            # a layer run once per refinement iteration: its uses' weight gradients as one GEMM
-            # at the last use, added straight into the parameters
-            _defer(hold, (dy, x), lambda items: _flush_linear(items, sw, sb))
-            return dx, None, None
-        if ctx.needs_input_grad[1]:
-            sw = _grad_sink(w)
-            if sw is not None:  # dW added in place: beta = 1 onto the parameter's .grad
-                ops.gemm(dy.t(), x, out=sw, beta=1.0)
-            else:
-                dw = ops.gemm(dy.t(), x)
-        if ctx.has_b and ctx.needs_input_grad[2]:
-            sb = _grad_sink(ctx.bias)
-            if sb is not None:
-                ops.colsum(dy, sb, accumulate=True)
-            else:
-                db = ops.colsum(dy, torch.empty(dy.shape[1], device=dy.device))
+        wants = (ctx.needs_input_grad[1], ctx.has_b and ctx.needs_input_grad[2])
+
+        def summed(items, sinks):
+            if sinks is not None:  # dW / db added in place: beta = 1 onto the parameters' .grad
+                return _flush_linear(items, *sinks)
+            (g, xin), = items
+            return [ops.gemm(g.t(), xin) if wants[0] else None,
+                    ops.colsum(g, torch.empty(g.shape[1], device=g.device)) if wants[1] else None]
+
+        # a layer run once per refinement iteration: its uses' weight gradients as one GEMM at
+        # the last use
+        dw, db = _param_grads(wants, (w, ctx.bias), getattr(ctx, "uses", None), (dy, x), summed,
+                              defer=_DEFER_LINEAR)
         return dx, dw, db
 
 

@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from scflow_amd import _lib
 from tests.helpers import switches
 
 pytestmark = pytest.mark.gpu
@@ -155,6 +156,45 @@ def test_dual_conv_heads_and_channel_slice_consumers():
         _close(a.grad, r.grad, 1e-5, 1e-4 * np.sqrt(3 * n * h * w), name)
 
 
+@pytest.mark.parametrize("bias_sink", [False, True])
+def test_linear_param_grads_all_or_nothing(bias_sink):
+    """``linear`` under direct_weight_grads, three uses of one 64 → 32 layer on 16 rows each: the
+    conv's rule (functions._param_grads).  With a ``.grad`` buffer on the weight only, BOTH
+    gradients come back through autograd; with one on each, both are added in place and autograd
+    is handed neither.  Values against fp64 autograd either way."""
+    from scflow_amd.train.functions import begin_forward, direct_weight_grads, linear
+    g = torch.Generator().manual_seed(5)
+    rows, cin, cout, uses = 16, 64, 32, 3
+    w, b = torch.randn(cout, cin, generator=g) * cin ** -0.5, torch.randn(cout, generator=g) * 0.1
+    xs = [torch.randn(rows, cin, generator=g) for _ in range(uses)]
+    gys = [torch.randn(rows, cout, generator=g) for _ in range(uses)]
+    wr, br = w.double().requires_grad_(), b.double().requires_grad_()
+    xr = [x.double().requires_grad_() for x in xs]
+    sum((F.linear(x, wr, br) * gy.double()).sum() for x, gy in zip(xr, gys)).backward()
+    wd, bd = w.cuda().requires_grad_(), b.cuda().requires_grad_()
+    wd.grad = torch.zeros_like(wd)
+    if bias_sink:
+        bd.grad = torch.zeros_like(bd)
+    xd = [x.cuda().requires_grad_() for x in xs]
+    with direct_weight_grads():
+        begin_forward()
+        tot = sum((linear(x, wd, bd) * gy.cuda()).sum() for x, gy in zip(xd, gys))
+        # what the backward hands autograd for each leaf (None: nothing, it was added in place)
+        gw, gb, *gx = torch.autograd.grad(tot, [wd, bd] + xd, allow_unused=True)
+    torch.cuda.synchronize()
+    tol = 1e-4 * np.sqrt(uses * rows)
+    if bias_sink:
+        assert gw is None and gb is None
+        _close(wd.grad, wr.grad, 1e-5, tol, "dw")
+        _close(bd.grad, br.grad, 1e-5, tol, "db")
+    else:
+        assert not wd.grad.any() and bd.grad is None  # nothing was added in place
+        _close(gw, wr.grad, 1e-5, tol, "dw")
+        _close(gb, br.grad, 1e-5, tol, "db")
+    for i in range(uses):
+        _close(gx[i], xr[i].grad, 1e-5, 1e-4 * np.sqrt(cout), f"dx[{i}]")
+
+
 def test_conv_wgrad_accumulate_and_split():
     """scflow_conv_wgrad directly: a Chan slice as the second source, accumulate = 1 adds onto
     dw / db, and a batch large enough to split the pixel reduction over many workgroups."""
@@ -171,8 +211,9 @@ def test_conv_wgrad_accumulate_and_split():
     dw = torch.ones(cout, c0 + c1, 3, 3).cuda()
     db = torch.ones(cout).cuda()
     bufc = buf.cuda()
-    ops.conv_wgrad(dy.cuda().view(-1, cout), x0.cuda(), Chan(bufc.view(-1, 48), 8, c1), dw, db, n, h, w,
-                   3, 3, 1, 1, 1, accumulate=True)
+    args = (dy.cuda().view(-1, cout), x0.cuda(), Chan(bufc.view(-1, 48), 8, c1))
+    assert ops.conv_wgrad_plan(*([a] for a in args), dw, db, n, h, w, 3, 3, 1, 1, 1)[0] == _lib.WGRAD_WINO
+    ops.conv_wgrad(*args, dw, db, n, h, w, 3, 3, 1, 1, 1, accumulate=True)
     torch.cuda.synchronize()
     _close(dw - 1, ref, 1e-5, 1e-4 * np.sqrt(n * h * w), "dw")
     _close(db - 1, dy.double().sum((0, 1, 2)), 1e-5, 1e-4 * np.sqrt(n * h * w), "db")
@@ -206,8 +247,10 @@ def test_conv_wgrad_thin(case):
     dw = torch.ones(cout, c0 + c1, kh, kw).cuda()
     db = torch.ones(cout).cuda()
     src1 = Chan(buf.cuda().view(-1, c1 + 8), 4, c1) if c1 else None
-    ops.conv_wgrad(dy.cuda().view(-1, cout), x0.cuda(), src1, dw, db, n, h, w, kh, kw, s, ph, pw,
-                   accumulate=True)
+    dyc, x0c = dy.cuda().view(-1, cout), x0.cuda()
+    assert ops.conv_wgrad_plan([dyc], [x0c], [src1] if c1 else None, dw, db, n, h, w, kh, kw, s, ph,
+                               pw)[0] == _lib.WGRAD_THIN
+    ops.conv_wgrad(dyc, x0c, src1, dw, db, n, h, w, kh, kw, s, ph, pw, accumulate=True)
     torch.cuda.synchronize()
     _close(dw - 1, ref, 1e-5, 1e-4 * np.sqrt(n * oh * ow), "dw")
     _close(db - 1, dy.double().sum((0, 1, 2)), 1e-5, 1e-4 * np.sqrt(n * oh * ow), "db")
@@ -241,8 +284,10 @@ def test_conv_wgrad_wino5(case):
     dw = torch.ones(cout, c0 + c1, kh, kw).cuda()
     db = torch.ones(cout).cuda() if bias else None
     src1 = Chan(buf.cuda().view(-1, c1 + 8), 4, c1) if c1 else None
-    ops.conv_wgrad(dy.cuda().view(-1, cout), x0.cuda(), src1, dw, db, n, h, w, kh, kw, 1, ph, pw,
-                   accumulate=True)
+    dyc, x0c = dy.cuda().view(-1, cout), x0.cuda()
+    assert ops.conv_wgrad_plan([dyc], [x0c], [src1] if c1 else None, dw, db, n, h, w, kh, kw, 1, ph,
+                               pw)[0] == _lib.WGRAD_WINO5
+    ops.conv_wgrad(dyc, x0c, src1, dw, db, n, h, w, kh, kw, 1, ph, pw, accumulate=True)
     torch.cuda.synchronize()
     err = float(((dw - 1).cpu().double() - ref).abs().max() / ref.abs().max())
     print(f"wino5 wgrad {case}: max error / max |dW| = {err:.2e}")
@@ -281,6 +326,9 @@ def test_conv_wgrad_batched(case):
         s1.append(Chan(buf.cuda().view(-1, c1 + 8), 4, c1))
     dw = torch.ones(cout, c0 + c1, kh, kw).cuda()
     db = torch.ones(cout).cuda() if bias else None
+    family = _lib.WGRAD_WINO if (kh, kw) == (3, 3) else _lib.WGRAD_WINO5
+    assert ops.conv_wgrad_plan(dys, s0, s1 if c1 else None, dw, db, n, h, w, kh, kw, 1, ph,
+                               pw)[0] == family
     ops.conv_wgrad_batched(dys, s0, s1 if c1 else None, dw, db, n, h, w, kh, kw, 1, ph, pw,
                            accumulate=True)
     torch.cuda.synchronize()
@@ -323,6 +371,8 @@ def test_conv_wgrad_batched_1x1_thin(case):
         s1.append(Chan(buf.cuda().view(-1, c1 + 8), 4, c1))
     dw = torch.ones(cout, c0 + c1, k, k).cuda()
     db = torch.ones(cout).cuda() if bias else None
+    family = _lib.WGRAD_THIN if min(c0 + c1, cout) <= 4 else _lib.WGRAD_1X1
+    assert ops.conv_wgrad_plan(dys, s0, s1 if c1 else None, dw, db, n, h, w, k, k, s, p, p)[0] == family
     ops.conv_wgrad_batched(dys, s0, s1 if c1 else None, dw, db, n, h, w, k, k, s, p, p,
                            accumulate=True)
     torch.cuda.synchronize()
@@ -426,9 +476,12 @@ def test_conv_wgrad_switches(env, case, monkeypatch):
     dw = torch.ones(cout, c0 + c1, kh, kw).cuda()
     db = torch.ones(cout).cuda()
     src1 = Chan(buf.cuda().view(-1, c1 + 8), 4, c1) if c1 else None
+    dyc, x0c = dy.cuda().view(-1, cout), x0.cuda()
     with switches(monkeypatch,**env):
-        ops.conv_wgrad(dy.cuda().view(-1, cout), x0.cuda(), src1, dw, db, n, h, w, kh, kw, 1, ph, pw,
-                       accumulate=True)
+        # every case here lands on the implicit GEMM (the special family off, or a 16-wide 3×3)
+        assert ops.conv_wgrad_plan([dyc], [x0c], [src1] if c1 else None, dw, db, n, h, w, kh, kw, 1,
+                                   ph, pw)[0] == _lib.WGRAD_GEMM
+        ops.conv_wgrad(dyc, x0c, src1, dw, db, n, h, w, kh, kw, 1, ph, pw, accumulate=True)
         torch.cuda.synchronize()
     if kw == 5:
         _close(dw - 1, ref, 2e-5, 0.0, f"dw {env}")
