@@ -828,6 +828,46 @@ typedef struct {
 long long scflow_render_workspace(int n_img, int size, int total_verts);
 int scflow_render(const scflow_render_args* args, void* stream);
 
+/* UV-textured meshes on the same renderer (pytorch3d's TexturesUV behind HardPhongShader, what
+ * load_objs_as_meshes / join_meshes_as_batch(include_textures=True) give the reference's Renderer
+ * for its mesh_ext='obj' configs, rendering.py:64-68, 189-190).  scflow_render_textured is
+ * scflow_render with one change: on an image that has a texture map, the texel that enters
+ *   rgb = (ambient + diffuse·dif)·texel + specular·spec
+ * is not the interpolated vertex colour but the map's bilinear sample at
+ *   uv = b0·verts_uvs[faces_uvs[f][0]] + b1·verts_uvs[faces_uvs[f][1]] + b2·verts_uvs[faces_uvs[f][2]]
+ * (f the winning face, b its perspective-corrected barycentrics), sampled as TexturesUV.
+ * sample_textures does with its defaults (rows flipped, grid_sample bilinear, align_corners=True,
+ * padding_mode='border'); on the map as stored, [H][W] with row 0 the image file's first row:
+ *   x = clamp(u·(W−1), 0, W−1), y = clamp((1−v)·(H−1), 0, H−1), taps (x0, y0), (x0+1, y0),
+ *   (x0, y0+1), (x0+1, y0+1) with the upper indices clamped to the map; a 1×1 map is its texel.
+ * Maps are RGBA8 (one dword load per tap; 4 MB for a 1024² map against 16 MB as fp32), texel =
+ * byte/255 in fp32, A unread.  Every image samples its own map at that map's own H, W: maps of
+ * different sizes in one batch are not padded to a common size (pytorch3d pads; the reference's
+ * data has one size).  Alpha, background, zbuf, pix_to_face, bary and light_out are
+ * scflow_render's bits, and so is the whole image where tex_offset < 0: in a batch that mixes
+ * both kinds scflow_render's own shading launch runs first, over the whole batch, and a second
+ * launch then writes the images that have a map.  No mip chain.
+ * tex NULL, or every tex_offset < 0: scflow_render, bit for bit.  texels, verts_uvs, faces_uvs:
+ * device memory; tex_offset, tex_hw: HOST arrays, read before the launch (they travel to the
+ * kernel as launch arguments, 64 images per shading launch; a captured graph therefore bakes the
+ * per-image table in: a replay shades with the offsets and sizes given at capture, whatever the
+ * host arrays hold by then — capture again when labels or maps change).
+ * SCFLOW_EINVAL before any launch: tex_offset NULL; with some tex_offset ≥ 0, a NULL texels / tex_hw / verts_uvs / faces_uvs or
+ * total_uvs ≤ 0; a textured image with H or W < 1, an offset that is no multiple of 4 or a map
+ * that ends past texel_bytes.  faces_uvs must index [0, total_uvs): device data, not checked. */
+typedef struct {
+  const unsigned char* texels;  /* device: RGBA8 maps back to back, each [H][W][4], 4-byte aligned */
+  long long texel_bytes;        /* size of texels */
+  const long long* tex_offset;  /* host [n_img]: byte offset of image i's map; < 0: image i is
+                                   untextured (vertex colours) */
+  const int* tex_hw;            /* host [n_img][2]: H, W of image i's map */
+  const float* verts_uvs;       /* device [total_uvs][2] */
+  const int* faces_uvs;         /* device [total_faces][3], parallel to faces: packed uv indices;
+                                   unread for untextured images */
+  int total_uvs;
+} scflow_render_tex;
+int scflow_render_textured(const scflow_render_args* args, const scflow_render_tex* tex, void* stream);
+
 /* Batched RANSAC-PnP (replaces BaseFlowRefiner.solve_pose's per-sample host loop,
  * models/refiner/base_flow_refiner.py:99-155, over get_2d_3d_corr_by_fw_flow and
  * cv2.solvePnPRansac, models/utils/pose.py:182-249; deliberately not cv2's algorithm — DESIGN.md

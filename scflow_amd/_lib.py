@@ -115,6 +115,17 @@ class RenderArgs(ctypes.Structure):
     ]
 
 
+class RenderTex(ctypes.Structure):
+    """Mirror of ``scflow_render_tex`` (include/scflow_hip.h).  ``tex_offset`` (int64) and
+    ``tex_hw`` (int32) point at host arrays; the other pointers at device memory."""
+    _fields_ = [
+        ("texels", c_vp), ("texel_bytes", c_ll),
+        ("tex_offset", c_vp), ("tex_hw", c_vp),
+        ("verts_uvs", c_vp), ("faces_uvs", c_vp),
+        ("total_uvs", c_int),
+    ]
+
+
 SCFLOW_LIGHT_FIXED, SCFLOW_LIGHT_PER_IMAGE, SCFLOW_LIGHT_BATCH_ZNEAR = 0, 1, 2
 
 # name -> (restype, argtypes); every function the header declares
@@ -241,6 +252,7 @@ SIGNATURES = {
     "scflow_enc_apply": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "scflow_render_workspace": (c_ll, [c_int, c_int, c_int]),
     "scflow_render": (c_int, [ctypes.POINTER(RenderArgs), c_vp]),
+    "scflow_render_textured": (c_int, [ctypes.POINTER(RenderArgs), ctypes.POINTER(RenderTex), c_vp]),
     "scflow_conv_wgrad_workspace": (c_int, [ctypes.POINTER(WgradArgs), ctypes.POINTER(c_ll)]),
     "scflow_conv_wgrad": (c_int, [ctypes.POINTER(WgradArgs), c_vp]),
     "scflow_conv_wgrad_batched": (c_int, [ctypes.POINTER(WgradArgs), c_int, c_vp, c_vp, c_vp, c_vp]),

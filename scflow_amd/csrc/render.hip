@@ -24,7 +24,15 @@
 //     correct barycentrics and depth, writes zbuf / pix_to_face / bary, interpolates position,
 //     normal and vertex colour and applies pytorch3d's Phong model (ambient + diffuse·texel +
 //     specular, shininess 64) with one point light; background colour, alpha 0 where empty.
+//     scflow_render_textured launches its ShadeTex form when some image has a UV texture map:
+//     for those images the texel is the bilinear sample of the image's RGBA8 map at the
+//     interpolated per-corner texture coordinate (pytorch3d TexturesUV.sample_textures: rows
+//     flipped, align_corners=True, border padding) — four dword loads per pixel, no LDS, no
+//     atomics; the geometry outputs are the NoTex form's bits, and the images without a map
+//     are shaded by the NoTex form itself (a mixed batch: one launch of each).
 #include "common.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -214,14 +222,66 @@ __device__ __forceinline__ void light_of(const scflow_render_args& a, int n,
   L[2] = R[8] * lz;
 }
 
-__global__ void render_shade_kernel(scflow_render_args a, const float* __restrict__ vproj,
+// UV texture of up to SHADE_TEX_IMGS consecutive images, handed to the textured launch by value
+// (it lands in the kernel-argument segment: no device table to build or copy).  map: image's
+// RGBA8 map [h][w], one dword per texel (R in the low byte); nullptr = vertex colours.
+constexpr int SHADE_TEX_IMGS = 64;
+struct ShadeTex {
+  const unsigned* map[SHADE_TEX_IMGS];
+  int hw[SHADE_TEX_IMGS][2];
+  const float* verts_uvs;
+  const int* faces_uvs;
+  int n0;  // first image of this launch
+};
+struct NoTex {};
+
+// pytorch3d TexturesUV.sample_textures (bilinear, align_corners=True, border padding, rows
+// flipped) on the unflipped map: x = clamp(u·(W−1)), y = clamp((1−v)·(H−1)), four taps with the
+// upper indices clamped to the map.  fmaxf/fminf also send a NaN coordinate to texel 0.
+__device__ __forceinline__ void sample_rgba8(const unsigned* __restrict__ map, int H, int W, float u,
+                                             float v, float (&T)[3]) {
+  const float x = fminf(fmaxf(u * (float)(W - 1), 0.f), (float)(W - 1));
+  const float y = fminf(fmaxf((1.f - v) * (float)(H - 1), 0.f), (float)(H - 1));
+  const int x0 = (int)x, y0 = (int)y;  // x, y ≥ 0: truncation is floor
+  const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
+  const float fx = x - (float)x0, fy = y - (float)y0;
+  const unsigned t00 = map[(size_t)y0 * W + x0], t10 = map[(size_t)y0 * W + x1];
+  const unsigned t01 = map[(size_t)y1 * W + x0], t11 = map[(size_t)y1 * W + x1];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float c00 = (float)((t00 >> (8 * k)) & 0xffu), c10 = (float)((t10 >> (8 * k)) & 0xffu);
+    const float c01 = (float)((t01 >> (8 * k)) & 0xffu), c11 = (float)((t11 >> (8 * k)) & 0xffu);
+    const float top = c00 + fx * (c10 - c00), bot = c01 + fx * (c11 - c01);
+    T[k] = (top + fy * (bot - top)) / 255.f;
+  }
+}
+
+// TEX = NoTex: one thread per pixel of the batch, vertex colours (scflow_render, and the images
+// without a map of scflow_render_textured: their bits are this kernel's by construction — the
+// same statements compiled into the ShadeTex form come out with other fused multiply-adds).
+// TEX = ShadeTex: blockIdx.y = image within the launch's chunk, so textured-or-not is uniform
+// per workgroup and the image's table entry is a scalar read; the workgroups of an image
+// without a map leave at once, that image is the NoTex launch's.
+template <class TEX>
+__global__ void render_shade_kernel(scflow_render_args a, TEX tex, const float* __restrict__ vproj,
                                     const unsigned long long* __restrict__ zf,
                                     const unsigned* __restrict__ zmin_bits, int n_img) {
+  constexpr bool kTex = !std::is_same<TEX, NoTex>::value;
   const int S = a.size;
-  const long long pix = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (pix >= (long long)n_img * S * S) return;
-  const int n = (int)(pix / ((long long)S * S));
-  const int rc = (int)(pix % ((long long)S * S));
+  long long pix;
+  int n, rc;
+  if constexpr (kTex) {
+    rc = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (rc >= S * S) return;
+    if (!tex.map[blockIdx.y]) return;
+    n = tex.n0 + (int)blockIdx.y;
+    pix = (long long)n * S * S + rc;
+  } else {
+    pix = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (pix >= (long long)n_img * S * S) return;
+    n = (int)(pix / ((long long)S * S));
+    rc = (int)(pix % ((long long)S * S));
+  }
   const int r = rc / S, c = rc % S;
   const unsigned long long key = zf[pix];
   float* img = a.images ? a.images + pix * 4 : nullptr;
@@ -259,7 +319,15 @@ __global__ void render_shade_kernel(scflow_render_args a, const float* __restric
   for (int k = 0; k < 3; ++k) {
     P[k] = b.b0 * a.verts[3 * i0 + k] + b.b1 * a.verts[3 * i1 + k] + b.b2 * a.verts[3 * i2 + k];
     N[k] = b.b0 * a.normals[3 * i0 + k] + b.b1 * a.normals[3 * i1 + k] + b.b2 * a.normals[3 * i2 + k];
-    T[k] = b.b0 * a.colors[3 * i0 + k] + b.b1 * a.colors[3 * i1 + k] + b.b2 * a.colors[3 * i2 + k];
+    if constexpr (!kTex)
+      T[k] = b.b0 * a.colors[3 * i0 + k] + b.b1 * a.colors[3 * i1 + k] + b.b2 * a.colors[3 * i2 + k];
+  }
+  if constexpr (kTex) {  // the texel replaces the interpolated vertex colour
+    const int j0 = tex.faces_uvs[3 * f], j1 = tex.faces_uvs[3 * f + 1], j2 = tex.faces_uvs[3 * f + 2];
+    const float* uv = tex.verts_uvs;
+    const float u = b.b0 * uv[2 * j0] + b.b1 * uv[2 * j1] + b.b2 * uv[2 * j2];
+    const float v = b.b0 * uv[2 * j0 + 1] + b.b1 * uv[2 * j1 + 1] + b.b2 * uv[2 * j2 + 1];
+    sample_rgba8(tex.map[blockIdx.y], tex.hw[blockIdx.y][0], tex.hw[blockIdx.y][1], u, v, T);
   }
   const float* R = a.R + 9 * n;
   const float* t = a.t + 3 * n;
@@ -291,7 +359,9 @@ SCFLOW_API long long scflow_render_workspace(int n_img, int size, int total_vert
   return (long long)n_img * size * size * 8 + (long long)total_verts * 12 + (long long)n_img * 4 + 64;
 }
 
-SCFLOW_API int scflow_render(const scflow_render_args* args, void* stream) {
+// validates, then runs the projection and tile launches and the shading launch(es); tex NULL or
+// no image with a map: the one NoTex shading launch
+static int render_impl(const scflow_render_args* args, const scflow_render_tex* tex, void* stream) {
   if (!args) return SCFLOW_EINVAL;
   const scflow_render_args& a = *args;
   if (!a.verts || !a.faces || !a.vert_img || !a.face_img || !a.R || !a.t || !a.K ||
@@ -303,6 +373,22 @@ SCFLOW_API int scflow_render(const scflow_render_args* args, void* stream) {
   if (a.light_mode < 0 || a.light_mode > 2 || (a.light_mode == SCFLOW_LIGHT_FIXED && !a.light_location))
     return SCFLOW_EINVAL;
   if (a.workspace_bytes < scflow_render_workspace(a.n_img, a.size, a.total_verts)) return SCFLOW_EINVAL;
+  bool textured = false, plain = !tex;  // some image has a map / some image has none
+  if (tex) {
+    if (!tex->tex_offset) return SCFLOW_EINVAL;
+    for (int i = 0; i < a.n_img; ++i) {
+      const long long off = tex->tex_offset[i];
+      if (off < 0) {
+        plain = true;
+        continue;
+      }
+      textured = true;
+      if (!tex->texels || !tex->tex_hw || !tex->verts_uvs || !tex->faces_uvs || tex->total_uvs <= 0)
+        return SCFLOW_EINVAL;
+      const long long h = tex->tex_hw[2 * i], w = tex->tex_hw[2 * i + 1];
+      if (h < 1 || w < 1 || (off & 3) || off + h * w * 4 > tex->texel_bytes) return SCFLOW_EINVAL;
+    }
+  }
   hipStream_t st = (hipStream_t)stream;
   const size_t npix = (size_t)a.n_img * a.size * a.size;
   unsigned long long* zf = (unsigned long long*)a.workspace;
@@ -314,6 +400,39 @@ SCFLOW_API int scflow_render(const scflow_render_args* args, void* stream) {
                                                                       a.total_verts);
   const int tiles = ((a.size + RT - 1) / RT) * ((a.size + RT - 1) / RT);
   render_tile_kernel<<<dim3(tiles, a.n_img), 256, 0, st>>>(a, a.face_img, vproj, zf);
-  render_shade_kernel<<<(unsigned)((npix + 255) / 256), 256, 0, st>>>(a, vproj, zf, zmin, a.n_img);
+  // a mixed batch is shaded by the NoTex launch as a whole, then the ShadeTex launch writes the
+  // images that have a map once more (same stream: in order)
+  if (plain)
+    render_shade_kernel<NoTex><<<(unsigned)((npix + 255) / 256), 256, 0, st>>>(a, NoTex{}, vproj, zf,
+                                                                                zmin, a.n_img);
+  if (!textured) return scflow_launch_status();
+  const unsigned blocks = (unsigned)(((size_t)a.size * a.size + 255) / 256);
+  for (int n0 = 0; n0 < a.n_img; n0 += SHADE_TEX_IMGS) {
+    const int cnt = a.n_img - n0 < SHADE_TEX_IMGS ? a.n_img - n0 : SHADE_TEX_IMGS;
+    ShadeTex t = {};
+    t.verts_uvs = tex->verts_uvs;
+    t.faces_uvs = tex->faces_uvs;
+    t.n0 = n0;
+    bool any = false;
+    for (int i = 0; i < cnt; ++i) {
+      const long long off = tex->tex_offset[n0 + i];
+      if (off < 0) continue;
+      any = true;
+      t.map[i] = (const unsigned*)(tex->texels + off);
+      t.hw[i][0] = tex->tex_hw[2 * (n0 + i)];
+      t.hw[i][1] = tex->tex_hw[2 * (n0 + i) + 1];
+    }
+    if (any)
+      render_shade_kernel<ShadeTex><<<dim3(blocks, cnt), 256, 0, st>>>(a, t, vproj, zf, zmin, a.n_img);
+  }
   return scflow_launch_status();
+}
+
+SCFLOW_API int scflow_render(const scflow_render_args* args, void* stream) {
+  return render_impl(args, nullptr, stream);
+}
+
+SCFLOW_API int scflow_render_textured(const scflow_render_args* args, const scflow_render_tex* tex,
+                                      void* stream) {
+  return render_impl(args, tex, stream);
 }

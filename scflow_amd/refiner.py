@@ -7,7 +7,9 @@ the context encoder is separate), ``extract_feat`` :84-106, ``get_pose`` :108-13
 Also here: the renderer-driven inference loop of ``BaseRefiner`` (base_refiner.py: the render
 step of ``format_data_test`` :106-117, ``update_data`` :239-252, ``forward_multiple_pass``
 :301-312, test cycles from ``test_cfg['cycles']``) as ``render`` / ``refine`` when a
-``renderer`` config is given (the HIP renderer, scflow_amd/renderer.py).  Data loading /
+``renderer`` config is given (the HIP renderer, scflow_amd/renderer.py; with ``mesh_ext='obj'``
+or textured ``meshes=`` it renders UV-textured images, and ``render`` / ``refine`` /
+``refine_frames`` take no argument for that).  Data loading /
 pre-processing stay the reference's; the loss configuration arguments are accepted and the
 losses live in ``scflow_amd.train``.
 

@@ -7,18 +7,37 @@ Same constructor keywords and ``forward(rotations, translations, internel_k, lab
 pytorch3d's shapes (``[N, H, W, 1]``, ``[N, H, W, 1, 3]``) and values (zbuf = view depth, −1
 where empty; pix_to_face indexes the batch's packed faces).  Meshes are read from
 ``mesh_dir`` (``*.ply`` / ``*.obj``; label from the file name ``obj_XXXXXX`` or
-``label_obj_id_map``) or passed in as ``meshes={label: (verts, faces, colors)}``.
+``label_obj_id_map``) or passed in as ``meshes={label: (verts, faces, colors)}`` or
+``meshes={label: dict(verts=, faces=, colors=, verts_uvs=, faces_uvs=, texture=)}``
+(``add_mesh``'s keywords).
 
-Supported configuration = what SCFlow uses (scflow_ycbv_real.py:261-274): Phong shading, hard
-blending, faces_per_pixel 1, blur_radius 0, square images, all four light placements
-(default/separate lights).  Soft blending and the silhouette (mask) renderer raise
-NotImplementedError.  ``dists`` is not computed (None): nothing on the SCFlow path reads it.
+Supported configuration = what SCFlow's configs use (scflow_ycbv_real.py:261-274,
+scflow_lumi_piano_*.py):
+
+* Phong shading, hard blending, faces_per_pixel 1, blur_radius 0, square images, all four light
+  placements (default / separate lights);
+* vertex-coloured meshes (PLY with red/green/blue, OBJ with ``v x y z r g b``, white otherwise) —
+  pytorch3d's TexturesVertex;
+* UV-textured meshes — pytorch3d's TexturesUV, what its OBJ reader returns for an OBJ with a
+  material: per-corner texture coordinates (``vt``, a seam vertex has several), one RGB map
+  (the first ``map_Kd`` of the ``mtllib``, decoded with PIL), sampled bilinearly in the shader with
+  pytorch3d's defaults (rows flipped, ``align_corners=True``, border padding); maps are stored as
+  RGBA8 on the device, once (``Renderer.texture_store``).  Both kinds mix freely in one batch, and
+  so do maps of different sizes: each mesh samples its own map at that map's own H, W (pytorch3d
+  pads the maps of a batch to a common size; the reference's data has one size).  A PLY's
+  ``texture_u`` / ``texture_v`` properties are ignored, as by pytorch3d's PLY reader.
+
+Soft blending, the silhouette (mask) renderer, Gouraud / flat shading, texture atlases, several
+maps per mesh and mip-mapping are not implemented (the first two raise NotImplementedError).
+``dists`` is not computed (None): nothing on the SCFlow path reads it.  Parity with pytorch3d
+itself is unpinned: it is not installed where this project is built.
 """
 from __future__ import annotations
 
 import glob
 import os
 import struct
+import warnings
 from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
@@ -175,9 +194,42 @@ def save_ply(path: str, verts: np.ndarray, faces: np.ndarray, colors: Optional[n
                 f.write(f"3 {fc[0]} {fc[1]} {fc[2]}\n".encode("ascii"))
 
 
-def load_obj(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
-    """Minimal OBJ reader (v, optional per-vertex rgb after xyz, f with fan triangulation)."""
-    verts, cols, faces = [], [], []
+def read_texture_image(path: str) -> np.ndarray:
+    """An image file → uint8 [H, W, 3] RGB (row 0 = the file's first row): alpha dropped,
+    greyscale expanded.  Decoded with PIL, imported here and nowhere else."""
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise ScflowError(f"{path}: decoding a texture image needs PIL (Pillow), which is not "
+                          "installed; decode the image yourself and pass it to Renderer.add_mesh "
+                          "as the texture= array (uint8 [H, W, 3]) with verts_uvs= and "
+                          "faces_uvs=") from e
+    with Image.open(path) as im:
+        return np.array(im.convert("RGB"), dtype=np.uint8)  # a writable copy
+
+
+def _read_mtl_map(path: str) -> Optional[str]:
+    """The ``map_Kd`` file of the first material of an MTL file that has one (None: no material
+    has), as written in the file (options such as ``-s 1 1 1`` in front of it dropped)."""
+    current, maps = None, {}
+    with open(path) as f:
+        for line in f:
+            tok = line.split()
+            if not tok:
+                continue
+            if tok[0] == "newmtl":
+                current = " ".join(tok[1:])
+            elif tok[0] == "map_Kd" and len(tok) > 1 and current is not None:
+                maps.setdefault(current, tok[-1])
+    return next(iter(maps.values()), None)  # dicts keep the file's order
+
+
+def _parse_obj(path: str):
+    """The lines of an OBJ file that the renderer reads: (verts, vertex colours, uvs, triangles,
+    their vt indices (−1: none), mtllib names) as lists.  An ``mtllib`` line gives one name, the
+    rest of the line (it may hold spaces, as for pytorch3d), and, if it has several words, also
+    each word (the OBJ format allows several files on one line)."""
+    verts, cols, uvs, faces, faces_uv, mtllibs = [], [], [], [], [], []
     with open(path) as f:
         for line in f:
             tok = line.split()
@@ -187,10 +239,85 @@ def load_obj(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
                 verts.append([float(x) for x in tok[1:4]])
                 if len(tok) >= 7:
                     cols.append([float(x) for x in tok[4:7]])
+            elif tok[0] == "vt":
+                uvs.append([float(x) for x in tok[1:3]])
             elif tok[0] == "f":
-                idx = [int(x.split("/")[0]) - 1 for x in tok[1:]]
+                idx, tdx = [], []
+                for corner in tok[1:]:
+                    part = corner.split("/")
+                    i = int(part[0])
+                    idx.append(i - 1 if i > 0 else len(verts) + i)
+                    if len(part) > 1 and part[1]:
+                        j = int(part[1])
+                        tdx.append(j - 1 if j > 0 else len(uvs) + j)
+                    else:
+                        tdx.append(-1)
                 for k in range(1, len(idx) - 1):
                     faces.append((idx[0], idx[k], idx[k + 1]))
+                    faces_uv.append((tdx[0], tdx[k], tdx[k + 1]))
+            elif tok[0] == "mtllib" and len(tok) > 1:
+                mtllibs.append(line.strip()[len(tok[0]):].strip())
+                if len(tok) > 2:
+                    mtllibs += tok[1:]
+    return verts, cols, uvs, faces, faces_uv, mtllibs
+
+
+def load_obj_textured(path: str) -> Dict[str, Optional[np.ndarray]]:
+    """OBJ reader, as far as pytorch3d's ``load_obj`` / ``load_objs_as_meshes`` goes for the
+    reference's renderer: ``v x y z [r g b]``, ``vt u v``, faces with ``v``, ``v/vt``, ``v//vn``
+    or ``v/vt/vn`` corners, negative (relative) indices, polygons fanned into triangles with the
+    ``vt`` indices following the same fan, ``mtllib`` → the MTL's ``newmtl`` / ``map_Kd``.  The
+    first material (in the MTL's order) that has a ``map_Kd`` supplies the one map of the whole
+    mesh; its path is relative to the OBJ's directory.  ``vn``, ``usemtl``, groups and the other
+    material properties are not read.
+
+    Returns dict(verts [V,3] float32, faces [F,3] int64, colors [V,3] float32 or None,
+    verts_uvs [U,2] float32, faces_uvs [F,3] int64, texture [H,W,3] uint8); the last three are
+    None when the file has no ``vt`` or no map (vertex colours, or white, as before).  Without
+    ``vt`` no MTL file is opened.  An ``mtllib`` whose file is not there, or a ``map_Kd`` whose
+    image is not there, counts as no map, with a warning, as in pytorch3d ("Mtl file does not
+    exist", "Texture file does not exist"): the geometry and the vertex colours load as they did
+    before textures were read.  An image that is there but cannot be decoded raises.  A map with a
+    face corner that has no ``vt`` raises: pytorch3d indexes −1 there, which reads the last
+    texture coordinate; nobody means that."""
+    verts, cols, uvs, faces, faces_uv, mtllibs = _parse_obj(path)
+    out = dict(verts=np.asarray(verts, np.float32).reshape(-1, 3),
+               faces=np.asarray(faces, np.int64).reshape(-1, 3),
+               colors=np.asarray(cols, np.float32) if len(cols) == len(verts) and cols else None,
+               verts_uvs=None, faces_uvs=None, texture=None)
+    if not uvs:
+        return out
+    here = os.path.dirname(os.path.abspath(path))
+    image = None
+    for m in mtllibs:
+        if os.path.isfile(os.path.join(here, m)):
+            image = _read_mtl_map(os.path.join(here, m))
+            if image is not None:
+                break
+    if mtllibs and not any(os.path.isfile(os.path.join(here, m)) for m in mtllibs):
+        warnings.warn(f"{path}: Mtl file does not exist: {mtllibs[0]}; the mesh loads untextured")
+    if image is None:
+        return out
+    if not os.path.isfile(os.path.join(here, image)):
+        warnings.warn(f"{path}: Texture file does not exist: {image}; the mesh loads untextured")
+        return out
+    fuv = np.asarray(faces_uv, np.int64).reshape(-1, 3)
+    if (fuv < 0).any():
+        bad = int(np.nonzero((fuv < 0).any(1))[0][0])
+        raise ScflowError(f"{path}: the mesh has a texture map ({image}) but triangle {bad} has a "
+                          "corner without a texture coordinate (v or v//vn); give every corner "
+                          "a vt index or remove the map")
+    if fuv.size and fuv.max() >= len(uvs):
+        raise ScflowError(f"{path}: a face refers to vt {int(fuv.max()) + 1} of {len(uvs)}")
+    out.update(verts_uvs=np.asarray(uvs, np.float32).reshape(-1, 2), faces_uvs=fuv,
+               texture=read_texture_image(os.path.join(here, image)))
+    return out
+
+
+def load_obj(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+    """The geometry of an OBJ file: (verts [V,3] float32, faces [F,3] int64, colors [V,3] float32
+    or None) — ``load_obj_textured`` without the texture; no MTL or image file is opened."""
+    verts, cols, _, faces, _, _ = _parse_obj(path)
     colors = np.asarray(cols, np.float32) if len(cols) == len(verts) and cols else None
     return np.asarray(verts, np.float32), np.asarray(faces, np.int64).reshape(-1, 3), colors
 
@@ -275,24 +402,98 @@ class Renderer(nn.Module):
         self.label_obj_id_map = label_obj_id_map
         self.mesh_ext = mesh_ext
         self.meshes: Dict[int, Tuple[Tensor, Tensor, Tensor, Tensor]] = {}
+        # label → (verts_uvs [U,2] float32, faces_uvs [F,3] int32, texture [H,W,3] uint8 on the
+        # host) of the meshes that have a UV texture
+        self.textures: Dict[int, Tuple[Tensor, Tensor, Tensor]] = {}
+        self._tex_store = None
         if meshes is not None:
             for lab, m in meshes.items():
-                self.add_mesh(int(lab), *m)
+                if isinstance(m, dict):
+                    self.add_mesh(int(lab), **m)
+                else:
+                    self.add_mesh(int(lab), *m)
         if mesh_dir is not None:
             self.load_meshes(mesh_dir)
         self._device = torch.device("cpu")
 
     # mesh registry
-    def add_mesh(self, label: int, verts, faces, colors=None) -> None:
+    def add_mesh(self, label: int, verts, faces, colors=None, *, verts_uvs=None, faces_uvs=None,
+                 texture=None) -> None:
+        """Register (or replace) the mesh of ``label``: verts [V,3], faces [F,3], vertex colours
+        [V,3] in [0, 1] (1.0 when None).  With a UV texture — ``verts_uvs`` [U,2], ``faces_uvs``
+        [F,3] (the texture coordinate of every face corner, indices into ``verts_uvs``: a vertex on
+        a seam has several) and ``texture`` [H,W,3] (row 0 = the image file's first row), all three
+        or none — the shader samples the map instead of interpolating the vertex colours
+        (pytorch3d's TexturesUV; include/scflow_hip.h, scflow_render_textured).  ``texture`` is
+        uint8, or float in [0, 1], which is QUANTISED to ``round(x·255)``: the device stores maps
+        as RGBA8.  Everything is checked here, on the host, once."""
         v = torch.as_tensor(np.asarray(verts), dtype=torch.float32)
         f = torch.as_tensor(np.asarray(faces), dtype=torch.long)
         c = (torch.full_like(v, 1.0) if colors is None
              else torch.as_tensor(np.asarray(colors), dtype=torch.float32))
+        tex = None
+        given = [x is not None for x in (verts_uvs, faces_uvs, texture)]
+        if any(given):
+            if not all(given):
+                raise ValueError(f"mesh {label}: verts_uvs, faces_uvs and texture come together "
+                                 f"(given: verts_uvs {given[0]}, faces_uvs {given[1]}, texture {given[2]})")
+            uv = np.asarray(verts_uvs, np.float32)
+            fuv = np.asarray(faces_uvs)
+            img = np.asarray(texture)
+            if uv.ndim != 2 or uv.shape[1] != 2 or len(uv) == 0:
+                raise ValueError(f"mesh {label}: verts_uvs has shape {uv.shape}, not [U, 2] with U ≥ 1")
+            if not np.isfinite(uv).all():
+                raise ValueError(f"mesh {label}: verts_uvs holds a NaN or an infinity")
+            if fuv.shape != tuple(f.shape) or fuv.dtype.kind not in "iu":
+                raise ValueError(f"mesh {label}: faces_uvs has shape {fuv.shape} and dtype {fuv.dtype}, "
+                                 f"not the faces' shape {tuple(f.shape)} of integers")
+            if fuv.size and (fuv.min() < 0 or fuv.max() >= len(uv)):
+                raise ValueError(f"mesh {label}: faces_uvs indices span [{fuv.min()}, {fuv.max()}], "
+                                 f"outside [0, {len(uv)})")
+            if img.ndim != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+                raise ValueError(f"mesh {label}: texture has shape {img.shape}, not [H, W, 3]")
+            if img.dtype != np.uint8:
+                if img.dtype.kind != "f":
+                    raise ValueError(f"mesh {label}: texture is {img.dtype}; uint8, or float in [0, 1]")
+                if not (np.isfinite(img).all() and img.min() >= 0.0 and img.max() <= 1.0):
+                    raise ValueError(f"mesh {label}: a float texture holds values in [0, 1]")
+                img = np.round(img.astype(np.float64) * 255.0).astype(np.uint8)
+            tex = (torch.from_numpy(np.ascontiguousarray(uv)),
+                   torch.from_numpy(np.ascontiguousarray(fuv.astype(np.int32))),
+                   torch.from_numpy(np.ascontiguousarray(img)))
         self.meshes[label] = (v, f, c, verts_normals(v.double(), f).float())
+        if tex is not None:
+            self.textures[label] = tex
+        else:
+            self.textures.pop(label, None)
+        self._tex_store = None  # rebuilt by the next forward
+
+    def texture_store(self, device=None):
+        """The device-resident texel store, built once per renderer and device and again after
+        ``add_mesh``: dict(device, texels uint8 [bytes] — every textured mesh's map as RGBA8
+        [H][W][4], back to back —, offset {label: byte offset}, hw {label: (H, W)}).  ``forward``
+        points each image at its label's map and never copies texels."""
+        device = torch.device(self._device if device is None else device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        st = self._tex_store
+        if st is None or st["device"] != device:
+            offset, hw, parts, pos = {}, {}, [], 0
+            for lab in sorted(self.textures):
+                img = self.textures[lab][2]
+                h, w = int(img.shape[0]), int(img.shape[1])
+                parts.append(torch.cat([img, torch.full((h, w, 1), 255, dtype=torch.uint8)], 2).reshape(-1))
+                offset[lab], hw[lab] = pos, (h, w)
+                pos += h * w * 4
+            texels = torch.cat(parts) if parts else torch.empty(0, dtype=torch.uint8)
+            st = self._tex_store = dict(device=device, texels=texels.to(device), offset=offset, hw=hw)
+        return st
 
     def load_meshes(self, mesh_dir: str) -> None:
         """Renderer.load_meshes (:138-153): label = trailing integer of the file name − 1, or
-        ``label_obj_id_map[name]``."""
+        ``label_obj_id_map[name]``.  An OBJ brings its UV texture along (``load_obj_textured``); a
+        PLY gives vertex colours only, as pytorch3d's PLY reader does: BOP-style ``texture_u`` /
+        ``texture_v`` vertex properties stay ignored."""
         if not self.obj_label_in_file and self.label_obj_id_map is None:
             raise ValueError("label_obj_id_map is required when obj_label_in_file=False")
         paths = sorted(glob.glob(os.path.join(mesh_dir, "*." + self.mesh_ext))) if os.path.isdir(mesh_dir) \
@@ -300,13 +501,17 @@ class Renderer(nn.Module):
         for p in paths:
             stem = os.path.basename(p).split(".")[0]
             label = (int(stem.split("_")[-1]) - 1) if self.obj_label_in_file else self.label_obj_id_map[stem]
-            v, f, c = load_ply(p) if p.endswith(".ply") else load_obj(p)
-            self.add_mesh(label, v, f, c)
+            if p.endswith(".ply"):
+                self.add_mesh(label, *load_ply(p))
+            else:
+                self.add_mesh(label, **load_obj_textured(p))
 
     def to(self, device):  # the reference's Renderer.to moves the meshes (:132-136)
         device = torch.device(device)
         self._device = device
         self.meshes = {k: tuple(x.to(device) for x in m) for k, m in self.meshes.items()}
+        # texture coordinates move with the meshes; the maps stay on the host (texture_store)
+        self.textures = {k: (uv.to(device), fuv.to(device), img) for k, (uv, fuv, img) in self.textures.items()}
         return self
 
     def forward(self, rotations: Tensor, translations: Tensor, internel_k: Tensor, labels: Tensor):
@@ -373,8 +578,39 @@ class Renderer(nn.Module):
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
         a.light_out = light.data_ptr()
         import ctypes
-        check(lib.scflow_render(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream),
-              "scflow_render")
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if self.textures and images is not None and any(lab in self.textures for lab in labs):
+            # per-image tables only: the texels are the store's, a label that appears twice
+            # points at the same map
+            store = self.texture_store(dev)
+            tex_offset = np.full(n, -1, np.int64)
+            tex_hw = np.zeros((n, 2), np.int32)
+            uvs, fuvs, uvoff, nuv = [], [], [], 0
+            for i, lab in enumerate(labs):
+                uvoff.append(nuv)
+                if lab not in self.textures:  # unread by the kernel: any block of the right size
+                    fuvs.append(ms[i][1].to(torch.int32))
+                    continue
+                uv, fuv, img = self.textures[lab]
+                if uv.device != dev:
+                    uv, fuv = uv.to(dev), fuv.to(dev)
+                    self.textures[lab] = (uv, fuv, img)
+                tex_offset[i], tex_hw[i] = store["offset"][lab], store["hw"][lab]
+                uvs.append(uv)
+                fuvs.append(fuv)
+                nuv += uv.shape[0]
+            verts_uvs = torch.cat(uvs).contiguous()
+            # packed uv indices: each image's own indices + its offset, one gather and one add
+            base = torch.tensor(uvoff, dtype=torch.int32, device=dev)[face_img.long()]
+            faces_uvs = (torch.cat(fuvs) + base[:, None]).contiguous()
+            tx = _lib.RenderTex()
+            tx.texels, tx.texel_bytes = store["texels"].data_ptr(), store["texels"].numel()
+            tx.tex_offset, tx.tex_hw = tex_offset.ctypes.data, tex_hw.ctypes.data  # host arrays
+            tx.verts_uvs, tx.faces_uvs, tx.total_uvs = verts_uvs.data_ptr(), faces_uvs.data_ptr(), nuv
+            check(lib.scflow_render_textured(ctypes.byref(a), ctypes.byref(tx), stream),
+                  "scflow_render_textured")
+        else:
+            check(lib.scflow_render(ctypes.byref(a), stream), "scflow_render")
         frags = Fragments(pix_to_face=p2f.long(), zbuf=zbuf, bary_coords=bary, dists=None)
         # extension: the light location each image was shaded with (the reference builds it into
         # its PointLights, :209-230)

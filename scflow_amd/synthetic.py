@@ -264,6 +264,44 @@ def ellipsoid_mesh(semi_axes, n_lat: int = 24, n_lon: int = 48) -> Tuple[np.ndar
     return verts.astype(np.float32), np.asarray(faces, np.int64), colors.astype(np.float32)
 
 
+def textured_ellipsoid_mesh(semi_axes, n_lat: int = 24, n_lon: int = 48, tex_hw=(64, 128),
+                            seed: int = 0) -> Dict[str, np.ndarray]:
+    """``ellipsoid_mesh`` with a UV texture, as ``Renderer.add_mesh``'s keywords: dict(verts, faces,
+    colors, verts_uvs [U,2] float32, faces_uvs [F,3] int64, texture [H,W,3] uint8).
+
+    The unwrapping is the sphere's: u = longitude / 2π, v = 1 at the +z pole and 0 at the −z pole.
+    It has a real seam: the vertices of the column at longitude 0 are shared by the faces on both
+    sides of it, and carry u = 0 towards one side and u = 1 towards the other — every ring has
+    n_lon + 1 texture coordinates for its n_lon vertices — and each pole has one coordinate per
+    triangle (u at the triangle's middle), so U = (n_lat − 1)(n_lon + 1) + 2·n_lon > V.
+
+    The texture has no symmetry under flips or transposition: R is a ramp along the columns, G a
+    ramp along the rows, B seeded noise (row 0 = the image file's first row, sampled where v = 1)."""
+    verts, faces, colors = ellipsoid_mesh(semi_axes, n_lat, n_lon)
+    uvs = []
+    for i in range(1, n_lat):
+        uvs += [[j / n_lon, 1.0 - i / n_lat] for j in range(n_lon + 1)]
+    top = len(uvs)
+    uvs += [[(j + 0.5) / n_lon, 1.0] for j in range(n_lon)]
+    bottom = len(uvs)
+    uvs += [[(j + 0.5) / n_lon, 0.0] for j in range(n_lon)]
+    ring = lambda i, j: (i - 1) * (n_lon + 1) + j  # noqa: E731  (j = n_lon: the seam's far side)
+    fuv = [[top + j, ring(1, j), ring(1, j + 1)] for j in range(n_lon)]
+    for i in range(1, n_lat - 1):
+        for j in range(n_lon):
+            fuv.append([ring(i, j), ring(i + 1, j), ring(i + 1, j + 1)])
+            fuv.append([ring(i, j), ring(i + 1, j + 1), ring(i, j + 1)])
+    fuv += [[bottom + j, ring(n_lat - 1, j + 1), ring(n_lat - 1, j)] for j in range(n_lon)]
+    h, w = int(tex_hw[0]), int(tex_hw[1])
+    rng = np.random.default_rng(seed + 7919)
+    tex = np.empty((h, w, 3), np.uint8)
+    tex[..., 0] = np.rint(np.linspace(20.0, 250.0, w))[None, :]
+    tex[..., 1] = np.rint(np.linspace(240.0, 10.0, h))[:, None]
+    tex[..., 2] = rng.integers(0, 256, (h, w))
+    return dict(verts=verts, faces=faces, colors=colors, verts_uvs=np.asarray(uvs, np.float32),
+                faces_uvs=np.asarray(fuv, np.int64), texture=tex)
+
+
 def make_background_pool(slots: int, height: int, width: int, seed: int = 0,
                          full: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """A stand-in for the reference's ``background_dir`` (data/coco is absent and no image decoder
