@@ -34,6 +34,8 @@
  *                               models/utils/pose.py:182-249
  *   scflow_patch_*           <- ComputeBbox, Crop, Resize, Pad, RemapPose, Normalize: 256² patches and their
  *                               intrinsics from full frames   datasets/pipelines/geometry_transform.py:155-500
+ *   scflow_pose_err_sym, scflow_vsd_counts <- bop_toolkit's MSSD / MSPD / VSD pose errors, which the
+ *                               reference leaves to that CPU tool after ADD.format_results   metrics/add.py:402-446
  *   scflow_transpose         <- layout plumbing (NCHW <-> channels-last slices), no reference equivalent
  *   scflow_ph_*              <- MultiClassPoseHead.forward                models/head/pose_head.py:201-211
  *   scflow_enc_*             <- RAFTEncoder.forward (Basic; IN / BN)      models/encoder/raft_encoder.py:286-314
@@ -867,6 +869,49 @@ typedef struct {
   int total_uvs;
 } scflow_render_tex;
 int scflow_render_textured(const scflow_render_args* args, const scflow_render_tex* tex, void* stream);
+
+/* BOP pose errors (bop_toolkit pose_error.py with the BOP19 settings; the toolkit is what the
+ * reference hands its format_results dumps to).  Both calls enqueue on the stream, synchronise
+ * nothing, and give bitwise reproducible results (max, min and integer sums only).
+ *
+ * scflow_pose_err_sym: for estimate i of class l = labels[i], vertices V = points[l][0 ..
+ *   counts[l]) (points [num_classes][max_points][3]; the padding past counts[l] is never read) and
+ *   symmetry transforms Sym = sym[sym_offset[l] .. sym_offset[l+1]) (sym [total_syms][12], each a
+ *   row-major 3×4 [S_R | S_t]; sym_offset [num_classes + 1]; the set holds the identity):
+ *     mssd[i] = min_{S ∈ Sym} max_{x ∈ V} ‖(R̂x + t̂) − (R̄(S_R·x + S_t) + t̄)‖₂   (model units)
+ *     mspd[i] = the same with both points projected, proj(X) = (K·X)[:2] / (K·X)[2]  (pixels;
+ *               no ε guard: depths are positive)
+ *   with (R̂, t̂) = R_est / t_est [n][3][3] / [n][3], (R̄, t̄) = R_gt / t_gt, K [n][3][3].  mssd or
+ *   mspd may be NULL (not both); mspd needs K.  The call first sets the outputs to +inf on the
+ *   stream; +inf stays where counts[l] ≤ 0, the class has no symmetry entry, or l is outside
+ *   [0, num_classes).  fp32; no [n][S][P] intermediate.  SCFLOW_EINVAL before any launch, outputs
+ *   untouched: a NULL required pointer, both outputs NULL, mspd without K, num_classes /
+ *   max_points / total_syms < 1, n < 0.  n = 0: success, nothing enqueued.
+ *
+ * scflow_vsd_counts: the pixel counts of the visible surface discrepancy of n pairs.  depth_est,
+ *   depth_gt [n][h][w]: depth renders of the class's mesh at the two poses (≤ 0: empty);
+ *   depth_test [n_frames][h][w]: the sensor depth (0: no measurement), pair i reads frame
+ *   frame_index[i]; K [n][3][3] (fx, fy, cx, cy read; no skew); diameter [n], or NULL for costs
+ *   that are not normalised; taus [n_taus], 1 ≤ n_taus ≤ 16; delta in depth units.  Per pixel
+ *   (x, y) depth D becomes the distance D·sqrt(((x − cx)/fx)² + ((y − cy)/fy)² + 1); with T the
+ *   test distance,
+ *     vis(M) = ((M − T ≤ delta) or (T == 0)) and (M > 0)                       ('bop19' visibility)
+ *     V_gt = vis(dist_gt), V_est = vis(dist_est) or (V_gt and dist_est > 0), I = V_gt ∧ V_est,
+ *     U = V_gt ∨ V_est, cost_k = #{p ∈ I : |dist_gt − dist_est| / diameter ≥ taus[k]}
+ *   counts [n][2 + n_taus] int = (|U|, |I|, cost_0 …), cleared by the call on the stream; the
+ *   caller forms e_k = (cost_k + |U| − |I|) / |U| (1 where |U| = 0).  A frame_index outside
+ *   [0, n_frames) leaves that pair's counts 0.  SCFLOW_EINVAL before any launch, counts untouched:
+ *   a NULL pointer other than diameter, n < 0, n_frames / h / w < 1, n_taus outside [1, 16];
+ *   SCFLOW_EUNSUPPORTED: h·w > 2^30 or n > 65535.  n = 0: success, nothing enqueued. */
+int scflow_pose_err_sym(const float* points, const int* counts, int num_classes, int max_points,
+                        const float* sym, const int* sym_offset, int total_syms, const int* labels,
+                        const float* R_est, const float* t_est, const float* R_gt,
+                        const float* t_gt, const float* K, float* mssd, float* mspd, int n,
+                        void* stream);
+int scflow_vsd_counts(const float* depth_est, const float* depth_gt, const float* depth_test,
+                      const int* frame_index, const float* K, const float* diameter,
+                      const float* taus, int n_taus, float delta, int* counts, int n, int n_frames,
+                      int h, int w, void* stream);
 
 /* Batched RANSAC-PnP (replaces BaseFlowRefiner.solve_pose's per-sample host loop,
  * models/refiner/base_flow_refiner.py:99-155, over get_2d_3d_corr_by_fw_flow and

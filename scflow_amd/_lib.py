@@ -253,6 +253,10 @@ SIGNATURES = {
     "scflow_render_workspace": (c_ll, [c_int, c_int, c_int]),
     "scflow_render": (c_int, [ctypes.POINTER(RenderArgs), c_vp]),
     "scflow_render_textured": (c_int, [ctypes.POINTER(RenderArgs), ctypes.POINTER(RenderTex), c_vp]),
+    "scflow_pose_err_sym": (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int] + [c_vp] * 8 +
+                            [c_int, c_vp]),
+    "scflow_vsd_counts": (c_int, [c_vp] * 7 + [c_int, c_float, c_vp, c_int, c_int, c_int, c_int,
+                                               c_vp]),
     "scflow_conv_wgrad_workspace": (c_int, [ctypes.POINTER(WgradArgs), ctypes.POINTER(c_ll)]),
     "scflow_conv_wgrad": (c_int, [ctypes.POINTER(WgradArgs), c_vp]),
     "scflow_conv_wgrad_batched": (c_int, [ctypes.POINTER(WgradArgs), c_int, c_vp, c_vp, c_vp, c_vp]),

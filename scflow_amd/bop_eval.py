@@ -13,6 +13,8 @@ metric (metrics/add.py) around the numeric core in ``metrics.py``.
 * ``evaluate`` — compute_metrics (add.py:134-180): match, ADD(-S)/diameter + reprojection error
   (``metrics.pose_errors``), the table.
 * ``format_results`` — predictions dumped as BOP ``scene_gt.json`` per sequence (add.py:402-446).
+* ``load_models_info`` / ``load_depth`` / ``evaluate_bop`` — BOP19 average recall over VSD, MSSD
+  and MSPD (``bop_metrics``), what the reference leaves to bop_toolkit after ``format_results``.
 
 Inputs are plain dicts / arrays (the reference's ``results`` entries: ``img_metas.img_path``,
 ``pred.labels / rotations / translations``); model points are passed in (the reference samples
@@ -251,3 +253,136 @@ def format_results(results: Sequence[dict], data_root: str, save_dir: str,
             f.write(dumps_json(content))
         paths.append(path)
     return paths
+
+
+# ------------------------------------------------------------------ BOP19 average recall
+def load_models_info(path: str) -> Dict[str, dict]:
+    """``models_info.json`` of a BOP model folder: {obj_id (str): {diameter, symmetries_discrete,
+    symmetries_continuous, …}}."""
+    with open(path) as f:
+        return {str(k): v for k, v in json.load(f).items()}
+
+
+def load_depth(path: str, depth_scale: float = 1.0) -> np.ndarray:
+    """A BOP depth image (16-bit PNG) as [H, W] float32 in mm: the stored value times the
+    camera's ``depth_scale``; 0 stays 0 (no measurement).  PIL is imported here, not at module
+    import."""
+    try:
+        from PIL import Image
+    except ImportError as e:  # pragma: no cover
+        raise ImportError(f"reading the depth image {path} needs PIL (pillow)") from e
+    with Image.open(path) as im:
+        d = np.asarray(im)
+    if d.ndim != 2:
+        raise ValueError(f"{path}: a depth image has one channel, got shape {d.shape}")
+    return d.astype(np.float32) * np.float32(depth_scale)
+
+
+DEPTH_PNG = "{}/depth/{:06d}.png"
+
+
+def _device_bop_errors(batch: dict, renderer):
+    """The three error functions of the matched pairs on the device (``bop_metrics``)."""
+    from . import bop_metrics as bm
+    from .patches import point_table
+    dev = renderer._device if renderer._device.type == "cuda" else torch.device("cuda")
+    T = lambda a, dt=torch.float32: torch.as_tensor(np.asarray(a)).to(dt).to(dev)  # noqa: E731
+    points, counts = point_table(renderer)
+    num_classes = points.shape[0]
+    table, offset = bm.symmetry_table(batch["models_info"], num_classes, dev)
+    lab = T(batch["labels"], torch.int64)
+    args = [T(batch[k]) for k in ("R_est", "t_est", "R_gt", "t_gt")]
+    K = T(batch["K"])
+    mssd, mspd = bm.mssd_mspd(points.to(dev), counts.to(dev), table, offset, lab, *args, K)
+    e = bm.vsd(renderer, lab, *args, K, T(batch["depth_test"]), T(batch["frame_index"], torch.int32),
+               T(batch["diameters"]), batch["taus"], batch["delta"])
+    return e.cpu().numpy(), mssd.double().cpu().numpy(), mspd.double().cpu().numpy()
+
+
+def evaluate_bop(results: Sequence[dict], gt_annots: Dict[str, dict], models_info: Dict[str, dict],
+                 renderer, depth_root_or_loader, class_names: Optional[Sequence[str]] = None,
+                 inverse_label_mapping: Optional[Dict[int, int]] = None,
+                 match_points: Optional[Sequence[np.ndarray]] = None,
+                 taus: Optional[Sequence[float]] = None, delta: Optional[float] = None,
+                 min_visib_fract: float = 0.1, error_fn=None) -> Dict[str, float]:
+    """BOP19 average recall of ``results`` → the flat '{name}/{metric}' dictionary: 'all/AR',
+    'all/AR_VSD', 'all/AR_MSSD', 'all/AR_MSPD' over every target, the per-threshold recalls
+    'all/mssd_05' … 'all/mssd_50' and 'all/mspd_05' … 'all/mspd_50', and with ``class_names``
+    '{class}/AR…' over that class's targets (−1 for a class without a target).
+
+    ``match_results`` pairs one estimate with every GT instance; its errors are VSD, MSSD and MSPD
+    (``bop_metrics``), a GT without an estimate has +inf errors, and ``average_recall`` thresholds
+    them.  Targets: the GT instances with ``visib_fract`` ≥ ``min_visib_fract`` where the
+    annotations hold ``scene_gt_info``, otherwise every GT instance.  bop_toolkit matches estimates
+    to GTs greedily by score; this keeps ``match_results``' one estimate per GT — the refiner emits
+    one estimate per detection with score 1, where the two coincide; with several estimates per
+    instance they do not (unpinned, as is every parity with the toolkit itself: it is absent).
+
+    ``models_info``: ``load_models_info`` (diameters and symmetries; obj_id = label + 1).
+    ``renderer``: a ``Renderer`` holding the classes' meshes, at least as large as the frames; its
+    vertices are the error functions' model points (and ``match_points``' default).
+    ``depth_root_or_loader``: a callable ``(sequence, image id) → [H, W]`` depth in mm, or the
+    dataset root, read as '{root}/{sequence}/depth/{image:06d}.png' times the camera's
+    ``depth_scale``.  All frames have one size.  ``error_fn(batch, renderer) → (vsd [M, n_taus],
+    mssd [M], mspd [M])`` replaces the device computation (tests inject a restatement)."""
+    from . import bop_metrics as bm
+    taus = bm.BOP19_TAUS if taus is None else tuple(taus)
+    delta = bm.BOP19_DELTA if delta is None else float(delta)
+    num_classes = max(renderer.meshes) + 1
+    diam_of = [float((models_info.get(str(l + 1)) or {}).get("diameter", 1.0)) for l in range(num_classes)]
+    symmetric = [l for l in range(num_classes)
+                 if (models_info.get(str(l + 1)) or {}).get("symmetries_discrete")
+                 or (models_info.get(str(l + 1)) or {}).get("symmetries_continuous")]
+    if match_points is None:
+        match_points = [renderer.meshes[l][0].cpu().numpy() if l in renderer.meshes
+                        else np.zeros((1, 3), np.float32) for l in range(num_classes)]
+    gR, gT, pR, pT, labels, valid, K = match_results(results, gt_annots, match_points, symmetric, diam_of,
+                                                     inverse_label_mapping)
+    # the walk of match_results once more: the frame and the visibility of every GT instance
+    frames, frame_index, targets = [], [], []
+    for fi, res in enumerate(results):
+        seq, img_id = _seq_and_image(res["img_metas"]["img_path"])
+        ann = gt_annots[seq]
+        if callable(depth_root_or_loader):
+            d = np.asarray(depth_root_or_loader(seq, img_id), np.float32)
+        else:
+            scale = float(ann["camera"][str(img_id)].get("depth_scale", 1.0))
+            d = load_depth(osp.join(depth_root_or_loader, DEPTH_PNG.format(seq, img_id)), scale)
+        if frames and d.shape != frames[0].shape:
+            raise ValueError(f"frame {seq}/{img_id} is {d.shape}, the first one {frames[0].shape}")
+        frames.append(d)
+        info = ann.get("gt_info", {}).get(str(img_id))
+        for k in range(len(ann["pose"][str(img_id)])):
+            frame_index.append(fi)
+            targets.append(True if info is None else float(info[k]["visib_fract"]) >= min_visib_fract)
+    frame_index, targets = np.asarray(frame_index, np.int32), np.asarray(targets, bool)
+    m = labels.shape[0]
+    diam = np.asarray([diam_of[l] for l in labels], np.float64)
+    vsd_e = np.full((m, len(taus)), np.inf)
+    mssd_e, mspd_e = np.full(m, np.inf), np.full(m, np.inf)
+    if valid.any():
+        batch = dict(labels=labels[valid], R_est=pR[valid], t_est=pT[valid], R_gt=gR[valid], t_gt=gT[valid],
+                     K=K[valid], depth_test=np.stack(frames), frame_index=frame_index[valid],
+                     diameters=diam[valid].astype(np.float32), models_info=models_info, taus=taus,
+                     delta=delta)
+        v, s, p = (error_fn or _device_bop_errors)(batch, renderer)
+        vsd_e[valid], mssd_e[valid], mspd_e[valid] = v, s, p
+    width = frames[0].shape[1]
+    out: Dict[str, float] = {}
+
+    def put(name, sel):
+        if not (targets & sel).any():
+            out.update({f"{name}/{k}": -1.0 for k in ("AR", "AR_VSD", "AR_MSSD", "AR_MSPD")})
+            return None
+        ar = bm.average_recall(vsd_e, mssd_e, mspd_e, diam, width, targets & sel)
+        out.update({f"{name}/{k}": ar[k] for k in ("AR", "AR_VSD", "AR_MSSD", "AR_MSPD")})
+        return ar
+    ar = put("all", np.ones(m, bool))
+    if ar is not None:
+        for i, th in enumerate(bm.BOP19_THETAS):
+            out["all/mssd_{:0>2d}".format(int(round(th * 100)))] = float(ar["recall_mssd"][i])
+        for i, th in enumerate(bm.BOP19_MSPD_THETAS):
+            out["all/mspd_{:0>2d}".format(int(th))] = float(ar["recall_mspd"][i])
+    for l, name in enumerate(class_names or ()):
+        put(name, labels == l)
+    return out

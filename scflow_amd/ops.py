@@ -1673,6 +1673,57 @@ def knn1(gt: Tensor, pred: Tensor) -> Tensor:
     return idx
 
 
+def pose_err_sym(points: Tensor, counts: Tensor, sym: Tensor, sym_offset: Tensor, labels: Tensor,
+                 R_est: Tensor, t_est: Tensor, R_gt: Tensor, t_gt: Tensor, K: Optional[Tensor],
+                 want_mssd: bool = True, want_mspd: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """(mssd [N], mspd [N]) of scflow_pose_err_sym (None for the one not asked for): points
+    [C, P, 3] / counts [C] int32 (``patches.point_table``), sym [T, 12] / sym_offset [C + 1] int32,
+    labels [N] int32, poses [N, 3, 3] / [N, 3], K [N, 3, 3] (needed for mspd)."""
+    for nm, t in (("points", points), ("sym", sym), ("R_est", R_est), ("t_est", t_est),
+                  ("R_gt", R_gt), ("t_gt", t_gt)) + ((("K", K),) if K is not None else ()):
+        _require(t, nm)
+    for nm, t in (("counts", counts), ("sym_offset", sym_offset), ("labels", labels)):
+        _require(t, nm, dtype=torch.int32)
+    C, P, _ = points.shape
+    n = labels.shape[0]
+    if counts.shape[0] != C or sym_offset.shape[0] != C + 1 or sym.dim() != 2 or sym.shape[1] != 12:
+        raise ValueError(f"counts {tuple(counts.shape)}, sym_offset {tuple(sym_offset.shape)}, sym "
+                         f"{tuple(sym.shape)} do not fit {C} classes")
+    for nm, t, shp in (("R_est", R_est, (n, 3, 3)), ("t_est", t_est, (n, 3)), ("R_gt", R_gt, (n, 3, 3)),
+                       ("t_gt", t_gt, (n, 3))) + ((("K", K, (n, 3, 3)),) if K is not None else ()):
+        if tuple(t.shape) != shp:
+            raise ValueError(f"{nm} must be {shp}, got {tuple(t.shape)}")
+    mssd = torch.empty(n, device=points.device) if want_mssd else None
+    mspd = torch.empty(n, device=points.device) if want_mspd else None
+    _launch("scflow_pose_err_sym", points, _p(points), _p(counts), C, P, _p(sym), _p(sym_offset),
+            sym.shape[0], _p(labels), _p(R_est), _p(t_est), _p(R_gt), _p(t_gt), _p(K), _p(mssd),
+            _p(mspd), n)
+    return mssd, mspd
+
+
+def vsd_counts(depth_est: Tensor, depth_gt: Tensor, depth_test: Tensor, frame_index: Tensor, K: Tensor,
+               diameter: Optional[Tensor], taus: Tensor, delta: float) -> Tensor:
+    """counts [N, 2 + n_taus] int32 = (|U|, |I|, cost_k …) of scflow_vsd_counts: depth_est /
+    depth_gt [N, H, W], depth_test [F, H, W], frame_index [N] int32, K [N, 3, 3], diameter [N] or
+    None (costs not normalised), taus [n_taus]."""
+    for nm, t in (("depth_est", depth_est), ("depth_gt", depth_gt), ("depth_test", depth_test),
+                  ("K", K), ("taus", taus)) + ((("diameter", diameter),) if diameter is not None else ()):
+        _require(t, nm)
+    _require(frame_index, "frame_index", dtype=torch.int32)
+    n, h, w = depth_est.shape
+    if depth_gt.shape != depth_est.shape or depth_test.dim() != 3 or tuple(depth_test.shape[1:]) != (h, w):
+        raise ValueError(f"depth maps disagree: est {tuple(depth_est.shape)}, gt {tuple(depth_gt.shape)}, "
+                         f"test {tuple(depth_test.shape)}")
+    if frame_index.shape[0] != n or tuple(K.shape) != (n, 3, 3) or \
+            (diameter is not None and diameter.shape[0] != n):
+        raise ValueError("frame_index, K and diameter hold one entry per pair")
+    counts = torch.empty(n, 2 + taus.shape[0], dtype=torch.int32, device=depth_est.device)
+    _launch("scflow_vsd_counts", depth_est, _p(depth_est), _p(depth_gt), _p(depth_test),
+            _p(frame_index), _p(K), _p(diameter), _p(taus), taus.shape[0], float(delta), _p(counts),
+            n, depth_test.shape[0], h, w)
+    return counts
+
+
 def group_norm_forward(x: Tensor, gamma: Tensor, beta: Tensor, groups: int, eps: float,
                        relu: bool) -> Tuple[Tensor, Tensor]:
     """GroupNorm (+ReLU) of channels-last x [n, h, w, c] (c == 4·groups) → (y, stats [n·groups, 2]
