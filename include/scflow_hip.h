@@ -36,6 +36,8 @@
  *                               intrinsics from full frames   datasets/pipelines/geometry_transform.py:155-500
  *   scflow_pose_err_sym, scflow_vsd_counts <- bop_toolkit's MSSD / MSPD / VSD pose errors, which the
  *                               reference leaves to that CPU tool after ADD.format_results   metrics/add.py:402-446
+ *   scflow_scene_visibility  <- bop_toolkit's calc_gt_masks / calc_gt_info (instance masks, visib_fract,
+ *                               boxes), which a ready-made BOP data set ships as files; no reference code
  *   scflow_transpose         <- layout plumbing (NCHW <-> channels-last slices), no reference equivalent
  *   scflow_ph_*              <- MultiClassPoseHead.forward                models/head/pose_head.py:201-211
  *   scflow_enc_*             <- RAFTEncoder.forward (Basic; IN / BN)      models/encoder/raft_encoder.py:286-314
@@ -912,6 +914,71 @@ int scflow_vsd_counts(const float* depth_est, const float* depth_gt, const float
                       const int* frame_index, const float* K, const float* diameter,
                       const float* taus, int n_taus, float delta, int* counts, int n, int n_frames,
                       int h, int w, void* stream);
+
+/* Scene visibility: what bop_toolkit's calc_gt_masks / calc_gt_info produce on the CPU with one
+ * render per instance (instance masks, visib_fract, the two boxes), for all instances of all
+ * frames of a batch in one call.  The definitions are the project's own; parity with the toolkit
+ * is unpinned (it is absent): its half-pixel convention, its w = x_max − x_min boxes and its 3×
+ * canvas are not reproduced.
+ *
+ * The mesh table (built once; scflow_amd/scene.py mesh_table): verts [total_verts][3], faces
+ * [total_faces][3] with vertex indices local to the class's block, vert_offset / face_offset
+ * [num_classes + 1] (class l owns verts [vert_offset[l], vert_offset[l+1]) and the faces likewise;
+ * a class without a mesh has an empty range), bounds [num_classes][6] = (min x, y, z, max x, y, z)
+ * of the class's vertices.  A face with an index outside its class's block is dropped, unread.
+ *
+ * Instances: labels [n], frame_index [n] non-decreasing (instances packed frame by frame), R
+ * [n][3][3], t [n][3]; K [n_frames][3][3] (fx, fy, cx, cy read; no skew term).
+ *
+ *   View point X = R·v + t; projected vertex (u, v) = (fx·X/Z + cx, fy·Y/Z + cy).  Pixel (x, y)
+ *   samples (x + pixel_offset, y + pixel_offset): with 0, integer coordinates are pixel centres
+ *   (metrics.project, the patch code, cv2).
+ *   Dropped faces (there is no clipping): a face with any vertex at Z ≤ 0; a face with zero
+ *   screen area.
+ *   Coverage: a face covers a sample where its three screen-space edge-function weights are > 0.
+ *   Depth at a sample: 1 / (w0/Z0 + w1/Z1 + w2/Z2), the weights summing to 1; the nearest face wins.
+ *   Canvas: [−margin_x, width + margin_x) × [−margin_y, height + margin_y).  px_count_all and
+ *   bbox_obj are taken over the canvas, everything else over the frame.
+ *   Distance: M = depth · sqrt(((x − cx)/fx)² + ((y − cy)/fy)² + 1), scflow_vsd_counts' factor.
+ *   Test distance T: with depth_test [n_frames][height][width] (mm, 0 = no measurement) the
+ *   sensor depth's distance; without it the minimum of M over the frame's instances (mutual
+ *   occlusion only), 0 where there is none.
+ *   Visibility: an instance is visible at a frame pixel ⇔ M > 0 ∧ (T = 0 ∨ M − T ≤ delta), VSD's
+ *   vis above.
+ *
+ * Outputs, each optional, at least one given:
+ *   stats [n][12] int: px_count_all (silhouette pixels on the canvas), px_count_valid (silhouette
+ *     pixels in the frame with T > 0; without depth_test the in-frame silhouette), px_count_visib,
+ *     bbox_obj (x, y, w, h) over the canvas (x, y may be negative), bbox_visib (x, y, w, h), 0.
+ *     Boxes are (x_min, y_min, x_max − x_min + 1, y_max − y_min + 1), (−1, −1, −1, −1) when empty.
+ *   inst_id [n_frames][height][width] int: among the visible instances the one with the smallest
+ *     M, ties to the lower index; −1 if none.
+ *   depth_scene [n_frames][height][width]: the nearest depth over the frame's instances, 0 if none.
+ *   depth_inst [n][height][width]: the instance's own depth, 0 where empty.
+ *   mask_visib [n][height][width] bytes: 1 where the instance is visible.
+ * An instance whose label is outside [0, num_classes), whose class is empty or whose frame_index is
+ * outside [0, n_frames) is skipped: counts 0, both boxes (−1, −1, −1, −1), its planes 0.
+ * All counters are integers: the results do not depend on any order and are bitwise
+ * reproducible, and an output asked for alone has the bits it has in a call with all of them.
+ * The call enqueues on the stream and synchronises nothing; it needs no workspace.
+ * SCFLOW_EINVAL before any launch, outputs untouched: args NULL, a NULL pointer other than
+ * depth_test and the outputs, num_classes / total_verts / total_faces / n_frames / height / width
+ * < 1, n < 0, a negative margin, delta < 0 (or NaN), no output given.  SCFLOW_EUNSUPPORTED: a
+ * canvas side > 2^24, n_frames > 65535.  n = 0: success, nothing enqueued. */
+typedef struct {
+  const float* verts; const int* faces;          /* the mesh table */
+  const int* vert_offset; const int* face_offset;
+  const float* bounds;
+  int num_classes, total_verts, total_faces;
+  const int* labels; const int* frame_index;     /* [n] */
+  const float* R; const float* t;                /* [n][3][3], [n][3] */
+  const float* K;                                /* [n_frames][3][3] */
+  int n, n_frames, height, width, margin_x, margin_y;
+  float pixel_offset, delta;
+  const float* depth_test;                       /* optional [n_frames][height][width] */
+  int* stats; int* inst_id; float* depth_scene; float* depth_inst; unsigned char* mask_visib;
+} scflow_scene_args;
+int scflow_scene_visibility(const scflow_scene_args* args, void* stream);
 
 /* Batched RANSAC-PnP (replaces BaseFlowRefiner.solve_pose's per-sample host loop,
  * models/refiner/base_flow_refiner.py:99-155, over get_2d_3d_corr_by_fw_flow and

@@ -126,6 +126,22 @@ class RenderTex(ctypes.Structure):
     ]
 
 
+class SceneArgs(ctypes.Structure):
+    """Mirror of ``scflow_scene_args`` (include/scflow_hip.h)."""
+    _fields_ = [
+        ("verts", c_vp), ("faces", c_vp), ("vert_offset", c_vp), ("face_offset", c_vp),
+        ("bounds", c_vp),
+        ("num_classes", c_int), ("total_verts", c_int), ("total_faces", c_int),
+        ("labels", c_vp), ("frame_index", c_vp), ("R", c_vp), ("t", c_vp), ("K", c_vp),
+        ("n", c_int), ("n_frames", c_int), ("height", c_int), ("width", c_int),
+        ("margin_x", c_int), ("margin_y", c_int),
+        ("pixel_offset", c_float), ("delta", c_float),
+        ("depth_test", c_vp),
+        ("stats", c_vp), ("inst_id", c_vp), ("depth_scene", c_vp), ("depth_inst", c_vp),
+        ("mask_visib", c_vp),
+    ]
+
+
 SCFLOW_LIGHT_FIXED, SCFLOW_LIGHT_PER_IMAGE, SCFLOW_LIGHT_BATCH_ZNEAR = 0, 1, 2
 
 # name -> (restype, argtypes); every function the header declares
@@ -257,6 +273,7 @@ SIGNATURES = {
                             [c_int, c_vp]),
     "scflow_vsd_counts": (c_int, [c_vp] * 7 + [c_int, c_float, c_vp, c_int, c_int, c_int, c_int,
                                                c_vp]),
+    "scflow_scene_visibility": (c_int, [ctypes.POINTER(SceneArgs), c_vp]),
     "scflow_conv_wgrad_workspace": (c_int, [ctypes.POINTER(WgradArgs), ctypes.POINTER(c_ll)]),
     "scflow_conv_wgrad": (c_int, [ctypes.POINTER(WgradArgs), c_vp]),
     "scflow_conv_wgrad_batched": (c_int, [ctypes.POINTER(WgradArgs), c_int, c_vp, c_vp, c_vp, c_vp]),

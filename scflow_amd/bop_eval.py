@@ -281,6 +281,102 @@ def load_depth(path: str, depth_scale: float = 1.0) -> np.ndarray:
 DEPTH_PNG = "{}/depth/{:06d}.png"
 
 
+GT_INFO_KEYS = ("px_count_all", "px_count_valid", "px_count_visib", "visib_fract", "bbox_obj", "bbox_visib")
+
+
+def _device_scene_stats(table, labels, frame_index, R, t, K, height, width, depth_test, delta, margin):
+    """``scene.scene_visibility``'s stats [n, 12] of one batch of frames as a numpy array."""
+    from . import scene
+    dev = table.verts.device
+    T = lambda a, dt=torch.float32: torch.as_tensor(np.asarray(a)).to(dt).to(dev)  # noqa: E731
+    out = scene.scene_visibility(table, T(labels, torch.int32), T(frame_index, torch.int32), T(R), T(t),
+                                 T(K), height, width, None if depth_test is None else T(depth_test),
+                                 delta, margin, want=("stats",))
+    return out["stats"].cpu().numpy()
+
+
+def compute_gt_info(gt_annots: Dict[str, dict], renderer, depth_root_or_loader=None,
+                    delta: float = 15.0, margin: Optional[Tuple[int, int]] = None, *,
+                    image_size: Optional[Tuple[int, int]] = None, frames_per_call: int = 32,
+                    visibility_fn=None) -> Dict[str, dict]:
+    """Fills ``ann['gt_info']`` of every sequence of ``gt_annots`` (``load_bop_annotations``) in the
+    shape of ``scene_gt_info.json``: per image a list parallel to ``scene_gt`` of {px_count_all,
+    px_count_valid, px_count_visib, visib_fract, bbox_obj, bbox_visib}, computed from the poses and
+    the meshes ``renderer`` holds (obj_id = label + 1) by ``scene.scene_visibility`` (DESIGN.md
+    §23; the definitions are the project's own, parity with bop_toolkit's calc_gt_info is
+    unpinned).  After it ``evaluate_bop`` applies ``min_visib_fract`` as with a shipped file.
+
+    ``depth_root_or_loader``: as for ``evaluate_bop`` (the sensor depth decides visibility), or None:
+    mutual occlusion of the annotated instances only, and the frames are ``image_size`` = (H, W)
+    (default: the renderer's).  ``margin`` = (x, y): the canvas around the frame on which
+    px_count_all and bbox_obj are taken, default (W, H).  ``visibility_fn(table, labels,
+    frame_index, R, t, K, H, W, depth_test, delta, margin) → stats [n, 12]`` replaces the device
+    call (tests inject a restatement); it gets ``renderer.meshes`` for ``table``."""
+    if visibility_fn is None:
+        from . import scene
+        dev = renderer._device if renderer._device.type == "cuda" else torch.device("cuda")
+        table, fn = scene.mesh_table(renderer, dev), _device_scene_stats
+    else:
+        table, fn = renderer.meshes, visibility_fn
+    for seq, ann in gt_annots.items():
+        info: Dict[str, list] = {}
+        ids = list(ann["pose"])
+        for b0 in range(0, len(ids), frames_per_call):
+            chunk = ids[b0:b0 + frames_per_call]
+            labels, fidx, R, t, K, depth = [], [], [], [], [], []
+            for fi, img in enumerate(chunk):
+                cam = ann["camera"][img]
+                K.append(np.asarray(cam["cam_K"], np.float32).reshape(3, 3))
+                if callable(depth_root_or_loader):
+                    depth.append(np.asarray(depth_root_or_loader(seq, int(img)), np.float32))
+                elif depth_root_or_loader is not None:
+                    depth.append(load_depth(osp.join(depth_root_or_loader, DEPTH_PNG.format(seq, int(img))),
+                                            float(cam.get("depth_scale", 1.0))))
+                for obj in ann["pose"][img]:
+                    labels.append(int(obj["obj_id"]) - 1)
+                    fidx.append(fi)
+                    R.append(np.asarray(obj["cam_R_m2c"], np.float32).reshape(3, 3))
+                    t.append(np.asarray(obj["cam_t_m2c"], np.float32).reshape(3))
+            if depth:
+                if any(d.shape != depth[0].shape for d in depth):
+                    raise ValueError(f"sequence {seq}: the frames differ in size")
+                h, w = depth[0].shape
+            else:
+                h, w = image_size if image_size is not None else renderer.image_size
+            n = len(labels)
+            stats = np.zeros((0, 12), np.int64)
+            if n:
+                stats = np.asarray(fn(table, np.asarray(labels, np.int32), np.asarray(fidx, np.int32),
+                                      np.stack(R), np.stack(t), np.stack(K), int(h), int(w),
+                                      np.stack(depth) if depth else None, float(delta),
+                                      (int(w), int(h)) if margin is None else tuple(margin)))
+            k = 0
+            for img in chunk:
+                rows = []
+                for _ in ann["pose"][img]:
+                    s = [int(v) for v in stats[k]]
+                    rows.append(dict(px_count_all=s[0], px_count_valid=s[1], px_count_visib=s[2],
+                                     visib_fract=s[2] / s[0] if s[0] > 0 else 0.0,
+                                     bbox_obj=s[3:7], bbox_visib=s[7:11]))
+                    k += 1
+                info[img] = rows
+        ann["gt_info"] = info
+    return gt_annots
+
+
+def write_gt_info(root: str, gt_annots: Dict[str, dict]) -> List[str]:
+    """``ann['gt_info']`` of every sequence as '{root}/{sequence:06d}/scene_gt_info.json' (where
+    ``load_bop_annotations`` reads it); returns the written paths."""
+    paths = []
+    for seq, ann in gt_annots.items():
+        path = osp.join(root, INFO_JSON.format(int(seq)))
+        os.makedirs(osp.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(dumps_json(ann["gt_info"]))
+        paths.append(path)
+    return paths
+
+
 def _device_bop_errors(batch: dict, renderer):
     """The three error functions of the matched pairs on the device (``bop_metrics``)."""
     from . import bop_metrics as bm

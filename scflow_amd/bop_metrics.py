@@ -159,6 +159,26 @@ def vsd(renderer, labels: Tensor, R_est: Tensor, t_est: Tensor, R_gt: Tensor, t_
     return vsd_errors(vsd_counts(z_est, z_gt, depth_test, frame_index, K, diameters, taus, delta))
 
 
+def vsd_frames(table, labels: Tensor, R_est: Tensor, t_est: Tensor, R_gt: Tensor, t_gt: Tensor, K: Tensor,
+               depth_test: Tensor, frame_index: Tensor, diameters: Tensor,
+               taus: Sequence[float] = BOP19_TAUS, delta: float = BOP19_DELTA) -> Tensor:
+    """``vsd`` without the square renderer: both pose sets are rendered at the frames' own H × W
+    by ``scene.scene_visibility`` (``want=("depth_inst",)``, two calls) from a ``scene.mesh_table``
+    and go to ``vsd_counts`` / ``vsd_errors``.  K [N, 3, 3] per pair, as for ``vsd`` (the pairs of
+    one frame share it).  The pixel convention is scene visibility's (integer
+    coordinates are pixel centres), not the square renderer's: the two functions' depth maps differ
+    along silhouettes."""
+    from . import scene
+    f, h, w = depth_test.shape
+    fi = frame_index.to(torch.int64)
+    # per-frame K from the pairs' (a frame_index outside the frames lands in a row that is dropped)
+    row = torch.where((fi >= 0) & (fi < f), fi, torch.full_like(fi, f))
+    kf = torch.zeros(f + 1, 3, 3, dtype=torch.float32, device=K.device).index_copy_(0, row, _f32(K))[:f]
+    z_est = scene.scene_visibility(table, labels, fi, R_est, t_est, kf, h, w, want=("depth_inst",))["depth_inst"]
+    z_gt = scene.scene_visibility(table, labels, fi, R_gt, t_gt, kf, h, w, want=("depth_inst",))["depth_inst"]
+    return vsd_errors(vsd_counts(z_est, z_gt, depth_test, frame_index, K, diameters, taus, delta))
+
+
 # ------------------------------------------------------------------------------ recall (host)
 def recall(errors, thresholds, targets) -> np.ndarray:
     """Recall per threshold, float64: the number of target instances whose error is below the

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -1722,6 +1722,62 @@ def vsd_counts(depth_est: Tensor, depth_gt: Tensor, depth_test: Tensor, frame_in
             _p(frame_index), _p(K), _p(diameter), _p(taus), taus.shape[0], float(delta), _p(counts),
             n, depth_test.shape[0], h, w)
     return counts
+
+
+SCENE_OUTPUTS = ("stats", "inst_id", "depth_scene", "depth_inst", "mask_visib")
+
+
+def scene_visibility(verts: Tensor, faces: Tensor, vert_offset: Tensor, face_offset: Tensor,
+                     bounds: Tensor, labels: Tensor, frame_index: Tensor, R: Tensor, t: Tensor,
+                     K: Tensor, height: int, width: int, depth_test: Optional[Tensor] = None,
+                     delta: float = 15.0, margin: Tuple[int, int] = (0, 0), pixel_offset: float = 0.0,
+                     want: Sequence[str] = ("stats", "inst_id")) -> Dict[str, Tensor]:
+    """scflow_scene_visibility: the mesh table (verts [ΣV, 3], faces [ΣF, 3] int32, vert_offset /
+    face_offset [C + 1] int32, bounds [C, 6]), labels / frame_index [n] int32 (frame_index
+    non-decreasing), R [n, 3, 3], t [n, 3], K [F, 3, 3], depth_test [F, H, W] or None, margin
+    (x, y) → {name: tensor} for the names in ``want`` (``SCENE_OUTPUTS``): stats [n, 12] int32,
+    inst_id [F, H, W] int32, depth_scene [F, H, W], depth_inst [n, H, W], mask_visib [n, H, W]
+    uint8.  n = 0: the empty scene (inst_id −1, depths 0), nothing launched."""
+    for nm, x in (("verts", verts), ("bounds", bounds), ("R", R), ("t", t), ("K", K)) + \
+            ((("depth_test", depth_test),) if depth_test is not None else ()):
+        _require(x, nm)
+    for nm, x in (("faces", faces), ("vert_offset", vert_offset), ("face_offset", face_offset),
+                  ("labels", labels), ("frame_index", frame_index)):
+        _require(x, nm, dtype=torch.int32)
+    want = tuple(want)
+    if not want or any(w not in SCENE_OUTPUTS for w in want):
+        raise ValueError(f"want = {want!r}: one or more of {SCENE_OUTPUTS}")
+    n, F, C = labels.shape[0], K.shape[0], bounds.shape[0]
+    H, W = int(height), int(width)
+    if vert_offset.shape[0] != C + 1 or face_offset.shape[0] != C + 1 or tuple(bounds.shape) != (C, 6):
+        raise ValueError(f"vert_offset {tuple(vert_offset.shape)}, face_offset {tuple(face_offset.shape)}, "
+                         f"bounds {tuple(bounds.shape)} do not fit one class count")
+    for nm, x, shp in (("frame_index", frame_index, (n,)), ("R", R, (n, 3, 3)), ("t", t, (n, 3)),
+                       ("K", K, (F, 3, 3))) + \
+            ((("depth_test", depth_test, (F, H, W)),) if depth_test is not None else ()):
+        if tuple(x.shape) != shp:
+            raise ValueError(f"{nm} must be {shp}, got {tuple(x.shape)}")
+    dev = verts.device
+    new = {"stats": lambda: torch.empty(n, 12, dtype=torch.int32, device=dev),
+           "inst_id": lambda: torch.full((F, H, W), -1, dtype=torch.int32, device=dev) if n == 0
+           else torch.empty(F, H, W, dtype=torch.int32, device=dev),
+           "depth_scene": lambda: torch.zeros(F, H, W, device=dev) if n == 0
+           else torch.empty(F, H, W, device=dev),
+           "depth_inst": lambda: torch.empty(n, H, W, device=dev),
+           "mask_visib": lambda: torch.empty(n, H, W, dtype=torch.uint8, device=dev)}
+    out = {w: new[w]() for w in want}
+    a = _lib.SceneArgs()
+    a.verts, a.faces, a.vert_offset, a.face_offset = _p(verts), _p(faces), _p(vert_offset), _p(face_offset)
+    a.bounds, a.num_classes, a.total_verts, a.total_faces = _p(bounds), C, verts.shape[0], faces.shape[0]
+    a.labels, a.frame_index, a.R, a.t, a.K = _p(labels), _p(frame_index), _p(R), _p(t), _p(K)
+    a.n, a.n_frames, a.height, a.width = n, F, H, W
+    a.margin_x, a.margin_y = int(margin[0]), int(margin[1])
+    a.pixel_offset, a.delta = float(pixel_offset), float(delta)
+    a.depth_test = _p(depth_test)
+    for w in SCENE_OUTPUTS:
+        setattr(a, w, _p(out.get(w)))
+    _launch("scflow_scene_visibility", verts, ctypes.byref(a))
+    return out
 
 
 def group_norm_forward(x: Tensor, gamma: Tensor, beta: Tensor, groups: int, eps: float,
