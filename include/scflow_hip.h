@@ -159,7 +159,8 @@ int scflow_debug_reload_switches(void);
  * stamps per workgroup of 16 query pixels to `stamps` (phase boundaries; NULL turns it off). */
 int scflow_debug_lookup_stamps(void* stamps);
 /* Profiling only: later instrumented conv launches (the Winograd F(2×2,3×3), F(4,5) and F(4×4,3×3)
- * kernels, the small-cin MFMA conv, the whole-halo thin conv, scflow_enc_conv) write 4 u64
+ * kernels, the bf16 1×5 / 5×1 conv, the small-cin MFMA conv, the whole-halo thin conv,
+ * scflow_enc_conv) write 4 u64
  * real-time-clock stamps per workgroup (start, prologue done, main loop done, epilogue done), NULL
  * turns it off. */
 int scflow_debug_conv_stamps(void* stamps);
@@ -216,6 +217,15 @@ typedef struct scflow_conv_args {
  * the 36 point GEMMs with the output transform in their epilogue.  fp32 throughout; error vs fp64
  * ≈ 10× a direct fp32 conv's (points {0, ±1, 2, −½, ∞}). */
 #define SCFLOW_CONV_WINO4 4
+/* scflow_conv_args.bk = SCFLOW_CONV_BF16 selects the bf16 direct conv for the SeqConv GRU (opt-in:
+ * scflow_conv_pick_bk never returns it): 1×5 (pad 0,2) / 5×1 (pad 2,0), stride 1, width 32 or 64,
+ * the height conditions of F(4,5), c0 and c1 multiples of 32 (c1 may be 0), cout a multiple of 32,
+ * every epilogue, no fused normalisation or residual; anything else is SCFLOW_EUNSUPPORTED.
+ * Inputs are rounded to bf16 (nearest even) on their way into LDS and the weights when packed;
+ * products are exact and accumulate in fp32 on v_mfma_f32_32x32x16_bf16; bias, bias map,
+ * activation and the GRU epilogues are fp32 and every buffer stays fp32.  No workspace.  Packed
+ * size in floats (two bf16 per float): 64·⌈cout/64⌉ · (c0 + c1) · 5 / 2.  (5 is not a format.) */
+#define SCFLOW_CONV_BF16 6
 /* Two independent convolutions (neither reads what the other writes, no overlapping outputs) in
  * ONE grouped launch when a paired kernel covers the pair — the decoder tail's flow-predictor /
  * mask-predictor branches: 3×3 256→2 with 1×1 256→1, 7×7 2→128 with 3×3 1→64, two F(2×2,3×3)
@@ -247,7 +257,8 @@ long long scflow_conv_workspace_bytes(const scflow_conv_args* args);
 /* Number of floats of the packed weight buffer for bk 8 and 16 (the same for both); w_oihw is
  * nn.Conv2d's [cout][c0+c1][kh][kw]. */
 long long scflow_conv_packed_size(int cout, int c0, int c1, int kh, int kw, int stride, int w);
-/* The same for any packing format bk (0, 8, 16, SCFLOW_CONV_WINO or SCFLOW_CONV_1X1W). */
+/* The same for any packing format bk (0, 8, 16, SCFLOW_CONV_WINO, SCFLOW_CONV_1X1W,
+ * SCFLOW_CONV_WINO4 or SCFLOW_CONV_BF16). */
 long long scflow_conv_packed_size_bk(int cout, int c0, int c1, int kh, int kw, int stride, int w,
                                      int bk);
 /* bk: packing format (0 → 16, 8, SCFLOW_CONV_WINO or SCFLOW_CONV_1X1W); pass the same value in
@@ -281,6 +292,7 @@ int scflow_conv_plan_kind(const scflow_conv_args* a, const scflow_conv_args* b, 
 #define SCFLOW_PLAN_THIN_FULL 11        /* cout ≤ 2: 3×3, the whole halo in LDS                  */
 #define SCFLOW_PLAN_THIN_CHUNKED 12     /* cout ≤ 2: halo in 32-channel chunks                   */
 #define SCFLOW_PLAN_THIN_GENERIC 13     /* cout ≤ 4, any shape                                   */
+#define SCFLOW_PLAN_SEP_BF16 14         /* bf16 direct 1×5 / 5×1 (SCFLOW_CONV_BF16)              */
 #define SCFLOW_PAIR_NONE 0
 #define SCFLOW_PAIR_THIN 1              /* THINZ (cout 2) beside THIN_CHUNKED 1×1 (cout 1)       */
 #define SCFLOW_PAIR_SMALLCIN 2          /* SMALLCIN_MFMA 7×7 2→128 beside 3×3 1→64               */

@@ -1047,6 +1047,35 @@ int wino_swz(int R, int C) {
 }
 
 #include "conv_wino4.h"
+#include "conv_sep_bf16.h"
+
+// The bf16 direct conv's domain (SCFLOW_CONV_BF16, conv_sep_bf16.h): F(4,5)'s shapes with both
+// sources' channels multiples of the 32-channel stage and whole 32-channel output blocks
+bool sep_bf16_shape(int cout, int c0, int c1, int kh, int kw, int stride, int w) {
+  const bool k = (kh == 1 && kw == 5) || (kh == 5 && kw == 1);
+  return k && stride == 1 && (w == 32 || w == 64) && c0 > 0 && c1 >= 0 && c0 % SBSC == 0 &&
+         c1 % SBSC == 0 && cout > 0 && cout % 32 == 0;
+}
+bool sep_bf16_launchable(const scflow_conv_args& a) {
+  // (buffer-load byte offsets stay below WINO_OOB)
+  const long long span = (long long)a.n * a.h * a.w * (a.s0 > a.s1 ? a.s0 : a.s1) * 4;
+  return sep_bf16_shape(a.cout, a.c0, a.c1, a.kh, a.kw, a.stride, a.w) && wino_launchable(a) &&
+         a.s0 >= a.c0 && (a.c1 == 0 || a.s1 >= a.c1) && span < WINO_OOB;
+}
+// packed floats: two bf16 per float, output channels padded to 64
+long long sep_bf16_packed_size(int cout, int c0, int c1) {
+  return (long long)round_up(cout, 64) * (c0 + c1) * 5 / 2;
+}
+// 128 output channels per workgroup when that still fills both workgroup slots of every CU, else
+// 64 (measured, B = 16 at 32×32, z|r 256 → 256: 256 workgroups of 128 channels 25.2 µs, 512 of 64
+// 19.7 µs; B = 32 at 64×64: 129 vs 140 µs (1×5), 142 vs 190 µs (5×1))
+#ifndef SEP_BF16_NBW  // tuning build flag: 1 / 2 forces 64 / 128 channels where the shape allows
+#define SEP_BF16_NBW 0
+#endif
+int sep_bf16_nbw(const scflow_conv_args& a, int cus) {
+  if (SEP_BF16_NBW) return SEP_BF16_NBW == 2 && a.cout % 128 == 0 ? 2 : 1;
+  return a.cout % 128 == 0 && wino_blocks(a) * (a.cout / 128) >= 2LL * cus ? 2 : 1;
+}
 
 // F(4×4,3×3) (conv_wino4.h) for the 3×3 convs it covers with at least WINO4_MIN_COUT output
 // channels; SCFLOW_CONV_WINO4 = 0 off, 1 default, 2 every covered shape (A/B).  Measured at
@@ -1246,6 +1275,10 @@ SCFLOW_API long long scflow_conv_packed_size_bk(int cout, int c0, int c1, int kh
       return SCFLOW_EUNSUPPORTED;
     return wino4_packed_size(cout, c0, c1);
   }
+  if (bk == SCFLOW_CONV_BF16) {
+    if (!sep_bf16_shape(cout, c0, c1, kh, kw, stride, w)) return SCFLOW_EUNSUPPORTED;
+    return sep_bf16_packed_size(cout, c0, c1);
+  }
   if (bk != 0 && bk != 8 && bk != 16) return SCFLOW_EINVAL;
   return scflow_conv_packed_size(cout, c0, c1, kh, kw, stride, w);
 }
@@ -1265,6 +1298,13 @@ SCFLOW_API int scflow_conv_pack_weights(const float* w_oihw, float* packed, int 
     const int blocks = pack_blocks(total);
     conv1x1w_pack_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(w_oihw, packed, cout, c0,
                                                                    conv1x1w_kb(c0), total);
+    return scflow_launch_status();
+  }
+  if (bk == SCFLOW_CONV_BF16) {
+    const long long total = scflow_conv_packed_size_bk(cout, c0, c1, kh, kw, stride, w, bk);
+    if (total < 0) return (int)total;
+    sep_bf16_pack_kernel<<<pack_blocks(total), 256, 0, (hipStream_t)stream>>>(
+        w_oihw, packed, cout, c0 + c1, (c0 + c1) / SBKC, total);
     return scflow_launch_status();
   }
   if (bk == SCFLOW_CONV_WINO4) {
@@ -1329,6 +1369,7 @@ SCFLOW_API int scflow_conv_pick_bk(const scflow_conv_args* args) {
 
 SCFLOW_API long long scflow_conv_workspace_bytes(const scflow_conv_args* args) {
   if (!args) return SCFLOW_EINVAL;
+  if (args->bk == SCFLOW_CONV_BF16) return sep_bf16_launchable(*args) ? 0 : SCFLOW_EUNSUPPORTED;
   if (args->bk != SCFLOW_CONV_WINO4) return 0;
   if (!wino4_shape(*args) || args->n <= 0 || args->c0 <= 0) return SCFLOW_EUNSUPPORTED;
   return wino4_workspace_bytes(*args);
@@ -1395,6 +1436,14 @@ ConvPlan plan_conv(const scflow_conv_args& a) {
   if (a.bk == SCFLOW_CONV_WINO4) {  // launch_wino4 derives its own grids (shared with the XHead)
     p.status = wino4_status(a);
     return p.status ? p : is(SCFLOW_PLAN_WINO4, 0);
+  }
+  if (a.bk == SCFLOW_CONV_BF16) {  // bf16 direct 1×5 / 5×1 (opt-in: never scflow_conv_pick_bk's choice)
+    if (!sep_bf16_launchable(a)) return fail(SCFLOW_EUNSUPPORTED);
+    if (!src_aligned || !aligned16(a.weight)) return fail(SCFLOW_EALIGN);
+    p.cp0 = a.c0;
+    p.nst = (a.c0 + a.c1) / SBSC;
+    p.nbw = sep_bf16_nbw(a, device_cus());
+    return is(SCFLOW_PLAN_SEP_BF16, wino_blocks(a), round_up(a.cout, 64 * p.nbw) / (64 * p.nbw));
   }
   if (a.bk == SCFLOW_CONV_1X1W) {
     if (!conv1x1w_launchable(a)) return fail(SCFLOW_EUNSUPPORTED);
@@ -1500,6 +1549,25 @@ int launch_smallcin_mfma(const scflow_conv_args& a, const ConvPlan& c, hipStream
                           c, c.lds, st, a, c.oh, c.ow, c.npad, c.ntiles, g_wino_stamps);
 }
 
+template <int EPI, int DIR, int W>
+int launch_sep_bf16_k(const ConvPlan& c, const SepBf16Params& p, hipStream_t st) {
+  return c.nbw == 2
+             ? launch_k<conv_sep_bf16_kernel<DIR, W, 2, EPI>>(c, sep_bf16_lds_bytes<DIR, W>(), st, p)
+             : launch_k<conv_sep_bf16_kernel<DIR, W, 1, EPI>>(c, sep_bf16_lds_bytes<DIR, W>(), st, p);
+}
+template <int EPI>
+int launch_sep_bf16_e(const ConvPlan& c, const SepBf16Params& p, hipStream_t st) {
+  if (c.ow == 32)
+    return p.a.kh == 1 ? launch_sep_bf16_k<EPI, 0, 32>(c, p, st) : launch_sep_bf16_k<EPI, 1, 32>(c, p, st);
+  return p.a.kh == 1 ? launch_sep_bf16_k<EPI, 0, 64>(c, p, st) : launch_sep_bf16_k<EPI, 1, 64>(c, p, st);
+}
+int launch_sep_bf16(const scflow_conv_args& a, const ConvPlan& c, hipStream_t st) {
+  const SepBf16Params p{a, c.cp0 / SBSC, c.nst, g_wino_stamps};
+  if (a.epilogue == SCFLOW_EPI_GRU_ZR) return launch_sep_bf16_e<SCFLOW_EPI_GRU_ZR>(c, p, st);
+  if (a.epilogue == SCFLOW_EPI_GRU_Q) return launch_sep_bf16_e<SCFLOW_EPI_GRU_Q>(c, p, st);
+  return launch_sep_bf16_e<SCFLOW_EPI_PLAIN>(c, p, st);
+}
+
 // the one place a plan becomes a template instantiation and a launch
 int launch_plan(const scflow_conv_args& a, const ConvPlan& c, hipStream_t st) {
   const bool co2 = a.cout == 2;
@@ -1507,6 +1575,7 @@ int launch_plan(const scflow_conv_args& a, const ConvPlan& c, hipStream_t st) {
     case SCFLOW_PLAN_WINO:
     case SCFLOW_PLAN_WINO5: return launch_wino(a, c, st);
     case SCFLOW_PLAN_WINO4: return launch_wino4(a, st);
+    case SCFLOW_PLAN_SEP_BF16: return launch_sep_bf16(a, c, st);
     case SCFLOW_PLAN_1X1W: return launch_conv1x1w(a, c, st);
     case SCFLOW_PLAN_MFMA:
     case SCFLOW_PLAN_1X1: {

@@ -446,6 +446,8 @@ class _DecoderRun:
         self.mark = defer and self.pair_tail  # the mark / wait pair of the deferred launches (tail)
         dec._last_plan = dict(fuse_tail=fuse_tail, defer=defer, pair_tail=self.pair_tail,
                               fuse_lc=core.fuse_lc, tiled=core.tiled, side_stream=self.st.two)
+        if core.gru_bf16:
+            dec._last_plan["gru_bf16"] = True
 
         def bufs(channels, two):
             return [torch.empty(core.M, channels, device=dev, dtype=torch.float32)

@@ -102,6 +102,9 @@ class ConvRunner:
     The packed copy is cached and re-packed whenever a weight's data pointer or version
     changes (optimizer step, load_state_dict, .to())."""
     force_bk = 0  # 8 / 16 overrides the library's per-launch K-stage depth (tuning only)
+    # per-instance packing format (e.g. ``_lib.CONV_BF16``) taken instead of the library's choice;
+    # None: ``conv_pick_bk`` decides.  An unsupported shape then raises ScflowError (no fallback).
+    fmt = None
 
     def __init__(self, convs: Sequence[nn.Conv2d], act: Optional[str], split: Optional[int] = None,
                  in_select: Optional[Sequence[Tuple[int, int]]] = None, with_bias: bool = True):
@@ -122,6 +125,21 @@ class ConvRunner:
         self._key = None
         self._packed = None
         self._bias = None
+
+    def _pick(self, n: int, h: int, w: int, c0: int, c1: int) -> int:
+        """The packing format of a launch: the instance's ``fmt`` if set, the class-wide tuning
+        override, else the library's choice (a host-only query, cached per launch shape)."""
+        if self.fmt is not None:
+            self._bk_shape = None  # (the library is asked again once the override is lifted)
+            return self.fmt
+        shape = (n, h, w, c0, c1)
+        if ConvRunner.force_bk:  # tuning / A-B only
+            self._bk_shape, self._bk = shape, ConvRunner.force_bk
+        if getattr(self, "_bk_shape", None) != shape:
+            self._bk = ops.conv_pick_bk(n, h, w, c0, c1, self.cout, self.kh, self.kw, self.ph,
+                                        self.pw, self.stride)
+            self._bk_shape = shape
+        return self._bk
 
     @staticmethod
     def of(conv: nn.Conv2d, act: Optional[str]) -> "ConvRunner":
@@ -170,13 +188,7 @@ class ConvRunner:
         c1 = 0 if src1 is None else src1.c
         if src0.c + c1 != self.cin:
             raise ValueError(f"conv expects {self.cin} input channels, got {src0.c}+{c1}")
-        shape = (n, h, w, src0.c, c1)
-        if ConvRunner.force_bk:
-            self._bk_shape, self._bk = shape, ConvRunner.force_bk
-        if getattr(self, "_bk_shape", None) != shape:
-            self._bk = ops.conv_pick_bk(n, h, w, src0.c, c1, self.cout, self.kh, self.kw, self.ph,
-                                        self.pw, self.stride)
-            self._bk_shape = shape
+        self._bk = self._pick(n, h, w, src0.c, c1)
         packed, bias = self.packed(src0.c, c1, w, self._bk)
         args = ops.conv2d_args(src0, packed, bias, n, h, w, self.cout, self.kh, self.kw, self.ph,
                                self.pw, self.act, out=out, src1=src1, epilogue=epilogue, gate=gate,
@@ -192,13 +204,7 @@ class ConvRunner:
         c1 = 0 if src1 is None else src1.c
         if src0.c + c1 != self.cin:
             raise ValueError(f"conv expects {self.cin} input channels, got {src0.c}+{c1}")
-        shape = (n, h, w, src0.c, c1)
-        if ConvRunner.force_bk:  # tuning / A-B only
-            self._bk_shape, self._bk = shape, ConvRunner.force_bk
-        if getattr(self, "_bk_shape", None) != shape:  # host-only query, once per launch shape
-            self._bk = ops.conv_pick_bk(n, h, w, src0.c, c1, self.cout, self.kh, self.kw, self.ph,
-                                        self.pw, self.stride)
-            self._bk_shape = shape
+        self._bk = self._pick(n, h, w, src0.c, c1)
         packed, bias = self.packed(src0.c, c1, w, self._bk)
         ops.conv2d(src0, packed, bias, n, h, w, self.cout, self.kh, self.kw, self.ph, self.pw,
                    self.act, out=out, src1=src1, epilogue=epilogue, gate=gate, rh=rh, hid=hid,
@@ -232,6 +238,8 @@ class ConvRunner:
             return 2.0 * pts * (m / tile) * kpad * npad
         if getattr(self, "_bk", None) == _lib.CONV_1X1W:  # K padded to 8, N to 64
             return 2.0 * m * ru(self.cout, 64) * ru(c0, 8)
+        if getattr(self, "_bk", None) == _lib.CONV_BF16:  # direct, K in 32-channel stages, N to 64
+            return 2.0 * m * ru(self.cout, 64) * self.kh * self.kw * kpad
         return 2.0 * m * npad * self.kh * self.kw * (ru(c0, 16) + ru(c1, 16))
 
 
@@ -400,7 +408,14 @@ def run_chain_pair(chain_a: Sequence[ConvModule], src_a: Chan, dst_a: Chan,
 # ---------------------------------------------------------------------------------- a4
 class ConvGRU(nn.Module):
     """raft_decoder.py:168-253.  z and r share one conv launch (cout = 2·h_channels) whose
-    epilogue writes z and r·h; the q launch's epilogue applies h ← (1−z)h + z·tanh(q)."""
+    epilogue writes z and r·h; the q launch's epilogue applies h ← (1−z)h + z·tanh(q).
+
+    ``bf16`` (default False; inference only — the training forward never selects it and stays
+    fp32): the z|r and q launches take the bf16 direct conv (``_lib.CONV_BF16``): h, r·h and the
+    motion features are rounded to bf16 on load and the weights when packed, products accumulate
+    in fp32, every buffer and the epilogues stay fp32.  The hoisted-context conv keeps its fp32
+    kernel (once per forward, its output is the fp32 bias map).  Read at every ``step`` /
+    ``bind_step``; a shape the kernel does not cover raises ScflowError (no fallback)."""
     _kernel = {"Conv": 3, "SeqConv": ((1, 5), (5, 1))}
     _padding = {"Conv": 1, "SeqConv": ((0, 2), (2, 0))}
 
@@ -422,6 +437,10 @@ class ConvGRU(nn.Module):
         self.h_channels = h_channels
         self.x_channels = x_channels
         self._runners = None
+        self.bf16 = False
+
+    def _gate_fmt(self, rzr: "ConvRunner", rq: "ConvRunner") -> None:
+        rzr.fmt = rq.fmt = _lib.CONV_BF16 if self.bf16 else None
 
     def init_weights(self) -> None:
         for m in self.modules():
@@ -432,6 +451,8 @@ class ConvGRU(nn.Module):
         if self._runners is None:
             self._runners = [(ConvRunner([z.conv, r.conv], "Sigmoid"), ConvRunner([q.conv], "Tanh"))
                              for z, r, q in zip(self.conv_z, self.conv_r, self.conv_q)]
+        for rzr, rq in self._runners:
+            self._gate_fmt(rzr, rq)
         return self._runners
 
     # -------------------------------------------------------------- loop-invariant context
@@ -450,6 +471,8 @@ class ConvGRU(nn.Module):
                           ConvRunner([z.conv, r.conv, q.conv], None, in_select=ctx))
                          for z, r, q in zip(self.conv_z, self.conv_r, self.conv_q)]
             self._ctx_key = key
+        for rzr, rq, _ in self._ctx:  # (the context runner keeps the library's fp32 choice)
+            self._gate_fmt(rzr, rq)
         return self._ctx
 
     def context_map(self, cxt: Chan, n: int, h: int, w: int) -> Tensor:

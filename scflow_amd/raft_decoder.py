@@ -176,6 +176,8 @@ class RAFTDecoder(_RecurrentDecoder):
         # last_plan's keys (hoist: hoisted context)
         self._last_plan = dict(convex=convex, fuse_lc=core.fuse_lc, tiled=core.tiled,
                                hoist=core.ctx_map is not None)
+        if core.gru_bf16:
+            self._last_plan["gru_bf16"] = True
 
         for it in range(iters):
             par = str(it % 2)

@@ -85,6 +85,11 @@ class _RecurrentDecoder(nn.Module):
         # larger or untileable maps take (the tests run them at 32 × 32 this way)
         self.fuse_lookup_conv = True
         self.fuse_lookup_conv_max_px = 32 * 32
+        # the GRU's z|r and q convs on the bf16 direct kernel (ConvGRU.bf16): operands rounded to
+        # bf16, fp32 accumulation, every buffer fp32.  Inference only, off by default, read at
+        # every forward; a feature map the kernel does not cover raises ScflowError (no fallback).
+        # last_plan carries gru_bf16=True only for a forward that ran it.
+        self.gru_bf16 = False
 
     def make_gru_block(self):
         return ConvGRU(self.h_channels, self.encoder.out_channels[0] + 2 + self.cxt_channels,
@@ -181,6 +186,7 @@ class RecurrentCore:
             ops.nchw_into(h_feat.contiguous().float(), Chan(HX, 0, hc))
             ops.nchw_into(cxt_feat.contiguous().float(), Chan(HX, hc, xc))
         self.HX = HX
+        self.gru_bf16 = dec.gru.bf16 = bool(dec.gru_bf16)
         # loop-invariant context share of the GRU pre-activations (once per forward)
         self.ctx_map = dec.gru.context_map(Chan(HX, hc, xc), N, h, w) if dec.hoist_context else None
         self.hx_flow = Chan(HX, hx_c - 2, 2)
