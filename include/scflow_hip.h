@@ -226,6 +226,17 @@ typedef struct scflow_conv_args {
  * activation and the GRU epilogues are fp32 and every buffer stays fp32.  No workspace.  Packed
  * size in floats (two bf16 per float): 64·⌈cout/64⌉ · (c0 + c1) · 5 / 2.  (5 is not a format.) */
 #define SCFLOW_CONV_BF16 6
+/* scflow_conv_args.bk = SCFLOW_CONV_BF16_3X3 selects the bf16 direct 3×3 conv for the motion
+ * encoder (opt-in: scflow_conv_pick_bk never returns it; SCFLOW_CONV_BF16 keeps refusing 3×3):
+ * 3×3, pad (1,1), stride 1, width 32 or 64, height a multiple of 4, c0 and c1 multiples of 32
+ * (c1 may be 0), any cout ≥ 1 (stores are masked per channel: nothing at or past cout of the
+ * output's pixel stride is written), the plain epilogue only — no GRU epilogue, bias map, fused
+ * normalisation or residual; anything else is SCFLOW_EUNSUPPORTED.  Inputs are rounded to bf16
+ * (nearest even) on their way into LDS and the weights when packed; products are exact and
+ * accumulate in fp32 on v_mfma_f32_32x32x16_bf16; bias and activation are fp32 and every buffer
+ * stays fp32.  No workspace.  Packed size in floats (two bf16 per float):
+ * 32·⌈cout/32⌉ · (c0 + c1) · 9 / 2. */
+#define SCFLOW_CONV_BF16_3X3 7
 /* Two independent convolutions (neither reads what the other writes, no overlapping outputs) in
  * ONE grouped launch when a paired kernel covers the pair — the decoder tail's flow-predictor /
  * mask-predictor branches: 3×3 256→2 with 1×1 256→1, 7×7 2→128 with 3×3 1→64, two F(2×2,3×3)
@@ -258,7 +269,7 @@ long long scflow_conv_workspace_bytes(const scflow_conv_args* args);
  * nn.Conv2d's [cout][c0+c1][kh][kw]. */
 long long scflow_conv_packed_size(int cout, int c0, int c1, int kh, int kw, int stride, int w);
 /* The same for any packing format bk (0, 8, 16, SCFLOW_CONV_WINO, SCFLOW_CONV_1X1W,
- * SCFLOW_CONV_WINO4 or SCFLOW_CONV_BF16). */
+ * SCFLOW_CONV_WINO4, SCFLOW_CONV_BF16 or SCFLOW_CONV_BF16_3X3). */
 long long scflow_conv_packed_size_bk(int cout, int c0, int c1, int kh, int kw, int stride, int w,
                                      int bk);
 /* bk: packing format (0 → 16, 8, SCFLOW_CONV_WINO or SCFLOW_CONV_1X1W); pass the same value in
@@ -293,6 +304,7 @@ int scflow_conv_plan_kind(const scflow_conv_args* a, const scflow_conv_args* b, 
 #define SCFLOW_PLAN_THIN_CHUNKED 12     /* cout ≤ 2: halo in 32-channel chunks                   */
 #define SCFLOW_PLAN_THIN_GENERIC 13     /* cout ≤ 4, any shape                                   */
 #define SCFLOW_PLAN_SEP_BF16 14         /* bf16 direct 1×5 / 5×1 (SCFLOW_CONV_BF16)              */
+#define SCFLOW_PLAN_C3_BF16 15          /* bf16 direct 3×3 (SCFLOW_CONV_BF16_3X3)                */
 #define SCFLOW_PAIR_NONE 0
 #define SCFLOW_PAIR_THIN 1              /* THINZ (cout 2) beside THIN_CHUNKED 1×1 (cout 1)       */
 #define SCFLOW_PAIR_SMALLCIN 2          /* SMALLCIN_MFMA 7×7 2→128 beside 3×3 1→64               */

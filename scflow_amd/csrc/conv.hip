@@ -1077,6 +1077,39 @@ int sep_bf16_nbw(const scflow_conv_args& a, int cus) {
   return a.cout % 128 == 0 && wino_blocks(a) * (a.cout / 128) >= 2LL * cus ? 2 : 1;
 }
 
+#include "conv3_bf16.h"
+
+// The bf16 direct 3×3 conv's domain (SCFLOW_CONV_BF16_3X3, conv3_bf16.h): "same" 3×3 at stride 1
+// on 32- or 64-wide maps of whole 4-row blocks, both sources' channels multiples of the 32-channel
+// stage, any cout, the plain epilogue without bias map, fused normalisation or residual
+bool c3_bf16_shape(int cout, int c0, int c1, int kh, int kw, int stride, int w) {
+  return kh == 3 && kw == 3 && stride == 1 && (w == 32 || w == 64) && c0 > 0 && c1 >= 0 &&
+         c0 % SBSC == 0 && c1 % SBSC == 0 && cout > 0;
+}
+long long c3_bf16_blocks(const scflow_conv_args& a) {
+  return (long long)a.n * (a.h / C3OR) * (a.w / C3OC);
+}
+bool c3_bf16_launchable(const scflow_conv_args& a) {
+  if (!c3_bf16_shape(a.cout, a.c0, a.c1, a.kh, a.kw, a.stride, a.w) || a.ph != 1 || a.pw != 1 ||
+      a.n <= 0 || a.h <= 0 || a.h % C3OR || a.epilogue != SCFLOW_EPI_PLAIN || a.bias_map ||
+      has_fused_norm(a))
+    return false;
+  // (buffer-load byte offsets stay below WINO_OOB; the grid's x extent fits)
+  const int smax = a.c1 > 0 && a.s1 > a.s0 ? a.s1 : a.s0;
+  const long long span = (long long)a.n * a.h * a.w * smax * 4;
+  return a.s0 >= a.c0 && (a.c1 == 0 || a.s1 >= a.c1) && span < WINO_OOB &&
+         c3_bf16_blocks(a) <= 0x7fffffffLL;
+}
+// packed floats: two bf16 per float, output channels padded to a 32-channel block
+long long c3_bf16_packed_size(int cout, int c0, int c1) {
+  return (long long)round_up(cout, 32) * (c0 + c1) * 9 / 2;
+}
+// Always 64 output channels per workgroup (four workgroups per CU).  A 128-channel variant of the
+// kernel (170 VGPRs, two per CU) measured slower for every motion-encoder conv at both benchmark
+// shapes (profiles/menc_bf16/nbw_variants.txt: B = 16 at 32×32, corr_net.1 22 vs 54 µs, out_net 20
+// vs 50; B = 32 at 64×64, corr_net.1 131 vs 235 µs, out_net 90 vs 120) and was dropped: sep_bf16_nbw's
+// rule — 128 once that fills both workgroup slots of every CU — is not taken over.
+
 // F(4×4,3×3) (conv_wino4.h) for the 3×3 convs it covers with at least WINO4_MIN_COUT output
 // channels; SCFLOW_CONV_WINO4 = 0 off, 1 default, 2 every covered shape (A/B).  Measured at
 // configs[1] (B=16, 32×32; tools/sess_w4c.sh, round 5): XHead hidden 128→512 59 vs 91 µs,
@@ -1279,6 +1312,10 @@ SCFLOW_API long long scflow_conv_packed_size_bk(int cout, int c0, int c1, int kh
     if (!sep_bf16_shape(cout, c0, c1, kh, kw, stride, w)) return SCFLOW_EUNSUPPORTED;
     return sep_bf16_packed_size(cout, c0, c1);
   }
+  if (bk == SCFLOW_CONV_BF16_3X3) {
+    if (!c3_bf16_shape(cout, c0, c1, kh, kw, stride, w)) return SCFLOW_EUNSUPPORTED;
+    return c3_bf16_packed_size(cout, c0, c1);
+  }
   if (bk != 0 && bk != 8 && bk != 16) return SCFLOW_EINVAL;
   return scflow_conv_packed_size(cout, c0, c1, kh, kw, stride, w);
 }
@@ -1304,6 +1341,13 @@ SCFLOW_API int scflow_conv_pack_weights(const float* w_oihw, float* packed, int 
     const long long total = scflow_conv_packed_size_bk(cout, c0, c1, kh, kw, stride, w, bk);
     if (total < 0) return (int)total;
     sep_bf16_pack_kernel<<<pack_blocks(total), 256, 0, (hipStream_t)stream>>>(
+        w_oihw, packed, cout, c0 + c1, (c0 + c1) / SBKC, total);
+    return scflow_launch_status();
+  }
+  if (bk == SCFLOW_CONV_BF16_3X3) {
+    const long long total = scflow_conv_packed_size_bk(cout, c0, c1, kh, kw, stride, w, bk);
+    if (total < 0) return (int)total;
+    c3_bf16_pack_kernel<<<pack_blocks(total), 256, 0, (hipStream_t)stream>>>(
         w_oihw, packed, cout, c0 + c1, (c0 + c1) / SBKC, total);
     return scflow_launch_status();
   }
@@ -1370,6 +1414,7 @@ SCFLOW_API int scflow_conv_pick_bk(const scflow_conv_args* args) {
 SCFLOW_API long long scflow_conv_workspace_bytes(const scflow_conv_args* args) {
   if (!args) return SCFLOW_EINVAL;
   if (args->bk == SCFLOW_CONV_BF16) return sep_bf16_launchable(*args) ? 0 : SCFLOW_EUNSUPPORTED;
+  if (args->bk == SCFLOW_CONV_BF16_3X3) return c3_bf16_launchable(*args) ? 0 : SCFLOW_EUNSUPPORTED;
   if (args->bk != SCFLOW_CONV_WINO4) return 0;
   if (!wino4_shape(*args) || args->n <= 0 || args->c0 <= 0) return SCFLOW_EUNSUPPORTED;
   return wino4_workspace_bytes(*args);
@@ -1444,6 +1489,13 @@ ConvPlan plan_conv(const scflow_conv_args& a) {
     p.nst = (a.c0 + a.c1) / SBSC;
     p.nbw = sep_bf16_nbw(a, device_cus());
     return is(SCFLOW_PLAN_SEP_BF16, wino_blocks(a), round_up(a.cout, 64 * p.nbw) / (64 * p.nbw));
+  }
+  if (a.bk == SCFLOW_CONV_BF16_3X3) {  // bf16 direct 3×3 (opt-in: never scflow_conv_pick_bk's choice)
+    if (!c3_bf16_launchable(a)) return fail(SCFLOW_EUNSUPPORTED);
+    if (!src_aligned || !aligned16(a.weight)) return fail(SCFLOW_EALIGN);
+    p.cp0 = a.c0;
+    p.nst = (a.c0 + a.c1) / SBSC;
+    return is(SCFLOW_PLAN_C3_BF16, c3_bf16_blocks(a), round_up(a.cout, 64) / 64);
   }
   if (a.bk == SCFLOW_CONV_1X1W) {
     if (!conv1x1w_launchable(a)) return fail(SCFLOW_EUNSUPPORTED);
@@ -1567,6 +1619,10 @@ int launch_sep_bf16(const scflow_conv_args& a, const ConvPlan& c, hipStream_t st
   if (a.epilogue == SCFLOW_EPI_GRU_Q) return launch_sep_bf16_e<SCFLOW_EPI_GRU_Q>(c, p, st);
   return launch_sep_bf16_e<SCFLOW_EPI_PLAIN>(c, p, st);
 }
+int launch_c3_bf16(const scflow_conv_args& a, const ConvPlan& c, hipStream_t st) {
+  const C3Bf16Params p{a, c.cp0 / SBSC, c.nst, round_up(a.cout, 32) / 32};
+  return launch_k<conv3_bf16_kernel>(c, c3_bf16_lds_bytes(), st, p);
+}
 
 // the one place a plan becomes a template instantiation and a launch
 int launch_plan(const scflow_conv_args& a, const ConvPlan& c, hipStream_t st) {
@@ -1576,6 +1632,7 @@ int launch_plan(const scflow_conv_args& a, const ConvPlan& c, hipStream_t st) {
     case SCFLOW_PLAN_WINO5: return launch_wino(a, c, st);
     case SCFLOW_PLAN_WINO4: return launch_wino4(a, st);
     case SCFLOW_PLAN_SEP_BF16: return launch_sep_bf16(a, c, st);
+    case SCFLOW_PLAN_C3_BF16: return launch_c3_bf16(a, c, st);
     case SCFLOW_PLAN_1X1W: return launch_conv1x1w(a, c, st);
     case SCFLOW_PLAN_MFMA:
     case SCFLOW_PLAN_1X1: {

@@ -448,6 +448,8 @@ class _DecoderRun:
                               fuse_lc=core.fuse_lc, tiled=core.tiled, side_stream=self.st.two)
         if core.gru_bf16:
             dec._last_plan["gru_bf16"] = True
+        if core.menc_bf16:
+            dec._last_plan["menc_bf16"] = True
 
         def bufs(channels, two):
             return [torch.empty(core.M, channels, device=dev, dtype=torch.float32)

@@ -240,6 +240,8 @@ class ConvRunner:
             return 2.0 * m * ru(self.cout, 64) * ru(c0, 8)
         if getattr(self, "_bk", None) == _lib.CONV_BF16:  # direct, K in 32-channel stages, N to 64
             return 2.0 * m * ru(self.cout, 64) * self.kh * self.kw * kpad
+        if getattr(self, "_bk", None) == _lib.CONV_BF16_3X3:  # the same for the bf16 direct 3×3
+            return 2.0 * m * ru(self.cout, 64) * 9 * kpad
         return 2.0 * m * npad * self.kh * self.kw * (ru(c0, 16) + ru(c1, 16))
 
 
@@ -292,7 +294,15 @@ class CorrLookup(nn.Module):
 
 # ---------------------------------------------------------------------------------- a3
 class MotionEncoder(nn.Module):
-    """raft_decoder.py:61-166 (same channel tables)."""
+    """raft_decoder.py:61-166 (same channel tables).
+
+    ``bf16`` (default False; inference only — the training forward never selects it and stays
+    fp32): the 3×3 convs the knob is wired to — corr_net's last conv, flow_net's last conv and
+    out_net's conv — take the bf16 direct 3×3 conv (``_lib.CONV_BF16_3X3``): their inputs are
+    rounded to bf16 on load and their weights when packed, products accumulate in fp32, every
+    buffer, bias and activation stay fp32.  corr_net.0 (the 1×1, fused with the lookup) and
+    flow_net.0 (7×7 on 2 channels) keep their fp32 kernels.  ``runners()`` applies it; a shape the
+    kernel does not cover raises ScflowError at the launch (no fallback)."""
     _corr_channels = {"Basic": (256, 192), "Small": 96, "Large": (256, 192)}
     _corr_kernel = {"Basic": (1, 3), "Small": 1, "Large": (1, 3)}
     _corr_padding = {"Basic": (0, 1), "Small": 0, "Large": (0, 1)}
@@ -324,6 +334,22 @@ class MotionEncoder(nn.Module):
         self.out_net = nn.Sequential(*self._make(corr_ch[-1] + lst(self._flow_channels[net_type])[-1],
                                                  self.out_channels, lst(self._out_kernel[net_type]),
                                                  lst(self._out_padding[net_type]), mk))
+        self.bf16 = False
+
+    def bf16_modules(self) -> List["ConvModule"]:
+        """The ConvModules ``bf16`` is wired to: the last conv of corr_net and of flow_net (never
+        their first: the 1×1 and the 7×7 stay fp32) and out_net's conv."""
+        mods = [net[-1] for net in (self.corr_net, self.flow_net) if len(net) > 1]
+        return mods + [self.out_net[-1]]
+
+    def runners(self) -> List["ConvRunner"]:
+        """``bf16_modules``' runners with their format set from ``bf16`` (cleared when off); called
+        before the launches of every forward."""
+        fmt = _lib.CONV_BF16_3X3 if self.bf16 else None
+        out = [ConvRunner.of(m.conv, m.act_type) for m in self.bf16_modules()]
+        for r in out:
+            r.fmt = fmt
+        return out
 
     @staticmethod
     def _make(cin, chans, kernels, pads, mk):
@@ -340,6 +366,7 @@ class MotionEncoder(nn.Module):
         cc = self.corr_net[-1].conv.out_channels
         cf = self.flow_net[-1].conv.out_channels
         co = self.out_channels[0]
+        self.runners()
         cbuf = torch.empty(M, corr.shape[1], device=dev)
         ops.nchw_into(corr.contiguous(), Chan.whole(cbuf))
         fbuf = torch.empty(M, 2, device=dev)

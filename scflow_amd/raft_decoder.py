@@ -178,6 +178,8 @@ class RAFTDecoder(_RecurrentDecoder):
                                hoist=core.ctx_map is not None)
         if core.gru_bf16:
             self._last_plan["gru_bf16"] = True
+        if core.menc_bf16:
+            self._last_plan["menc_bf16"] = True
 
         for it in range(iters):
             par = str(it % 2)

@@ -90,6 +90,12 @@ class _RecurrentDecoder(nn.Module):
         # every forward; a feature map the kernel does not cover raises ScflowError (no fallback).
         # last_plan carries gru_bf16=True only for a forward that ran it.
         self.gru_bf16 = False
+        # the motion encoder's 3×3 convs (corr_net's last, flow_net's last, out_net) on the bf16
+        # direct 3×3 kernel (MotionEncoder.bf16), under the same terms: operands rounded to bf16,
+        # fp32 accumulation and buffers, inference only, off by default, read at every forward,
+        # ScflowError on an uncovered feature map, last_plan carries menc_bf16=True only for a
+        # forward that ran it.  Independent of gru_bf16.
+        self.menc_bf16 = False
 
     def make_gru_block(self):
         return ConvGRU(self.h_channels, self.encoder.out_channels[0] + 2 + self.cxt_channels,
@@ -187,6 +193,8 @@ class RecurrentCore:
             ops.nchw_into(cxt_feat.contiguous().float(), Chan(HX, hc, xc))
         self.HX = HX
         self.gru_bf16 = dec.gru.bf16 = bool(dec.gru_bf16)
+        self.menc_bf16 = dec.encoder.bf16 = bool(dec.menc_bf16)
+        dec.encoder.runners()  # (sets or clears the 3×3 runners' format before they are bound)
         # loop-invariant context share of the GRU pre-activations (once per forward)
         self.ctx_map = dec.gru.context_map(Chan(HX, hc, xc), N, h, w) if dec.hoist_context else None
         self.hx_flow = Chan(HX, hx_c - 2, 2)
