@@ -188,7 +188,8 @@ typedef struct scflow_conv_args {
   int bk;                                /* packing format of the weights: K-stage depth 0 or 16 */
                                          /* (default) or 8, or SCFLOW_CONV_WINO — see           */
                                          /* scflow_conv_pick_bk                                 */
-  /* Winograd 3×3 only (NULL elsewhere) — the RAFT encoder's fused normalisation:              */
+  /* Winograd 3×3 (SCFLOW_CONV_WINO, _WINO4) and SCFLOW_CONV_BF16_3X3N (NULL elsewhere) — the   */
+  /* RAFT encoder's fused normalisation:                                                       */
   const float* in_scale;                 /* src0 ← relu(src0·in_scale[n][c0] + in_shift[n][c0]) */
   const float* in_shift;                 /* on load (InstanceNorm + ReLU of the producer; c1=0) */
   const float* out_scale;                /* v ← (conv + bias)·out_scale[o] + out_shift[o]       */
@@ -237,6 +238,19 @@ typedef struct scflow_conv_args {
  * stays fp32.  No workspace.  Packed size in floats (two bf16 per float):
  * 32·⌈cout/32⌉ · (c0 + c1) · 9 / 2. */
 #define SCFLOW_CONV_BF16_3X3 7
+/* scflow_conv_args.bk = SCFLOW_CONV_BF16_3X3N selects the same kernel in the RAFT encoder's form
+ * (opt-in: scflow_conv_pick_bk never returns it; SCFLOW_CONV_BF16_3X3 keeps its own domain): 3×3,
+ * pad (1,1), stride 1, width any multiple of 32, height a multiple of 4, c0 and c1 multiples of 32
+ * (c1 may be 0), any cout ≥ 1, the plain epilogue without bias map; anything else is
+ * SCFLOW_EUNSUPPORTED.  Fused, each optional: x' = relu(fmaf(x, in_scale[img][c], in_shift[img][c]))
+ * on load (one fp32 rounding, then the bf16 rounding; needs both pointers and c1 = 0; zero padding
+ * stays 0); v = conv + bias; v = v·out_scale[o] + out_shift[o]; v += res[pix·sres + o]; out =
+ * act(v).  in_scale without in_shift, out_scale without out_shift (or the reverse) and sres < cout
+ * are SCFLOW_EINVAL; a source pixel stride or sres that is not a multiple of 4 floats, or an
+ * in_scale / in_shift that is not 16-byte aligned, is SCFLOW_EALIGN.  With every fused pointer NULL
+ * a launch equals SCFLOW_CONV_BF16_3X3's bit for bit.  Packing and packed size are
+ * SCFLOW_CONV_BF16_3X3's; no workspace, no atomics, a fixed summation order. */
+#define SCFLOW_CONV_BF16_3X3N 9
 /* Two independent convolutions (neither reads what the other writes, no overlapping outputs) in
  * ONE grouped launch when a paired kernel covers the pair — the decoder tail's flow-predictor /
  * mask-predictor branches: 3×3 256→2 with 1×1 256→1, 7×7 2→128 with 3×3 1→64, two F(2×2,3×3)
@@ -269,7 +283,7 @@ long long scflow_conv_workspace_bytes(const scflow_conv_args* args);
  * nn.Conv2d's [cout][c0+c1][kh][kw]. */
 long long scflow_conv_packed_size(int cout, int c0, int c1, int kh, int kw, int stride, int w);
 /* The same for any packing format bk (0, 8, 16, SCFLOW_CONV_WINO, SCFLOW_CONV_1X1W,
- * SCFLOW_CONV_WINO4, SCFLOW_CONV_BF16 or SCFLOW_CONV_BF16_3X3). */
+ * SCFLOW_CONV_WINO4, SCFLOW_CONV_BF16, SCFLOW_CONV_BF16_3X3 or SCFLOW_CONV_BF16_3X3N). */
 long long scflow_conv_packed_size_bk(int cout, int c0, int c1, int kh, int kw, int stride, int w,
                                      int bk);
 /* bk: packing format (0 → 16, 8, SCFLOW_CONV_WINO or SCFLOW_CONV_1X1W); pass the same value in
@@ -305,6 +319,7 @@ int scflow_conv_plan_kind(const scflow_conv_args* a, const scflow_conv_args* b, 
 #define SCFLOW_PLAN_THIN_GENERIC 13     /* cout ≤ 4, any shape                                   */
 #define SCFLOW_PLAN_SEP_BF16 14         /* bf16 direct 1×5 / 5×1 (SCFLOW_CONV_BF16)              */
 #define SCFLOW_PLAN_C3_BF16 15          /* bf16 direct 3×3 (SCFLOW_CONV_BF16_3X3)                */
+#define SCFLOW_PLAN_C3_BF16N 16         /* its RAFT-encoder form (SCFLOW_CONV_BF16_3X3N)         */
 #define SCFLOW_PAIR_NONE 0
 #define SCFLOW_PAIR_THIN 1              /* THINZ (cout 2) beside THIN_CHUNKED 1×1 (cout 1)       */
 #define SCFLOW_PAIR_SMALLCIN 2          /* SMALLCIN_MFMA 7×7 2→128 beside 3×3 1→64               */

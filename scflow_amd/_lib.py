@@ -24,12 +24,14 @@ CONV_1X1W = 3  # scflow_conv_args.bk: wide 1x1 packing/kernel (SCFLOW_CONV_1X1W)
 CONV_WINO4 = 4  # scflow_conv_args.bk: Winograd F(4x4,3x3) packing/kernel (SCFLOW_CONV_WINO4)
 CONV_BF16 = 6  # scflow_conv_args.bk: opt-in bf16 direct 1x5 / 5x1 conv (SCFLOW_CONV_BF16)
 CONV_BF16_3X3 = 7  # scflow_conv_args.bk: opt-in bf16 direct 3x3 conv (SCFLOW_CONV_BF16_3X3)
+CONV_BF16_3X3N = 9  # scflow_conv_args.bk: its RAFT-encoder form, fused norms (SCFLOW_CONV_BF16_3X3N)
 # scflow_conv_plan_kind: SCFLOW_PLAN_* (one conv's kernel family) and SCFLOW_PAIR_* (grouped kernel)
 (PLAN_NONE, PLAN_MFMA, PLAN_1X1, PLAN_1X1W, PLAN_WINO, PLAN_WINO5, PLAN_WINO4, PLAN_SMALLCIN_MFMA,
  PLAN_SMALLCIN_TILED, PLAN_SMALLCIN_GENERIC, PLAN_THINZ, PLAN_THIN_FULL, PLAN_THIN_CHUNKED,
  PLAN_THIN_GENERIC) = range(14)
 PLAN_SEP_BF16 = 14
 PLAN_C3_BF16 = 15
+PLAN_C3_BF16N = 16
 PAIR_NONE, PAIR_THIN, PAIR_SMALLCIN, PAIR_WINO = range(4)
 # scflow_conv_wgrad_plan: SCFLOW_WGRAD_* (the weight gradient's kernel family)
 WGRAD_NONE, WGRAD_THIN, WGRAD_WINO, WGRAD_WINO5, WGRAD_1X1, WGRAD_GEMM = range(6)

@@ -1104,6 +1104,31 @@ bool c3_bf16_launchable(const scflow_conv_args& a) {
 long long c3_bf16_packed_size(int cout, int c0, int c1) {
   return (long long)round_up(cout, 32) * (c0 + c1) * 9 / 2;
 }
+// The RAFT encoder's form of it (SCFLOW_CONV_BF16_3X3N): the same kernel, packing and grid on maps
+// of any width that is a multiple of the 32-column block, with the producer's InstanceNorm + ReLU
+// on load (one source only), the eval-BatchNorm affine and the residual.  SCFLOW_CONV_BF16_3X3's
+// own domain above is not widened.
+bool c3n_bf16_shape(int cout, int c0, int c1, int kh, int kw, int stride, int w) {
+  return kh == 3 && kw == 3 && stride == 1 && w > 0 && w % C3OC == 0 && c0 > 0 && c1 >= 0 &&
+         c0 % SBSC == 0 && c1 % SBSC == 0 && cout > 0;
+}
+// SCFLOW_OK, or what every entry point answers before a launch: SCFLOW_EINVAL for half an affine
+// or a residual narrower than the output, SCFLOW_EUNSUPPORTED outside the domain
+int c3n_bf16_status(const scflow_conv_args& a) {
+  if ((!a.in_scale) != (!a.in_shift) || (!a.out_scale) != (!a.out_shift) ||
+      (a.res && a.sres < a.cout))
+    return SCFLOW_EINVAL;
+  if (!c3n_bf16_shape(a.cout, a.c0, a.c1, a.kh, a.kw, a.stride, a.w) || a.ph != 1 || a.pw != 1 ||
+      a.n <= 0 || a.h <= 0 || a.h % C3OR || a.epilogue != SCFLOW_EPI_PLAIN || a.bias_map ||
+      (a.in_scale && a.c1 != 0))
+    return SCFLOW_EUNSUPPORTED;
+  const int smax = a.c1 > 0 && a.s1 > a.s0 ? a.s1 : a.s0;
+  const long long span = (long long)a.n * a.h * a.w * smax * 4;
+  return a.s0 >= a.c0 && (a.c1 == 0 || a.s1 >= a.c1) && span < WINO_OOB &&
+                 c3_bf16_blocks(a) <= 0x7fffffffLL
+             ? SCFLOW_OK
+             : SCFLOW_EUNSUPPORTED;
+}
 // Always 64 output channels per workgroup (four workgroups per CU).  A 128-channel variant of the
 // kernel (170 VGPRs, two per CU) measured slower for every motion-encoder conv at both benchmark
 // shapes (profiles/menc_bf16/nbw_variants.txt: B = 16 at 32×32, corr_net.1 22 vs 54 µs, out_net 20
@@ -1316,6 +1341,10 @@ SCFLOW_API long long scflow_conv_packed_size_bk(int cout, int c0, int c1, int kh
     if (!c3_bf16_shape(cout, c0, c1, kh, kw, stride, w)) return SCFLOW_EUNSUPPORTED;
     return c3_bf16_packed_size(cout, c0, c1);
   }
+  if (bk == SCFLOW_CONV_BF16_3X3N) {
+    if (!c3n_bf16_shape(cout, c0, c1, kh, kw, stride, w)) return SCFLOW_EUNSUPPORTED;
+    return c3_bf16_packed_size(cout, c0, c1);
+  }
   if (bk != 0 && bk != 8 && bk != 16) return SCFLOW_EINVAL;
   return scflow_conv_packed_size(cout, c0, c1, kh, kw, stride, w);
 }
@@ -1344,7 +1373,7 @@ SCFLOW_API int scflow_conv_pack_weights(const float* w_oihw, float* packed, int 
         w_oihw, packed, cout, c0 + c1, (c0 + c1) / SBKC, total);
     return scflow_launch_status();
   }
-  if (bk == SCFLOW_CONV_BF16_3X3) {
+  if (bk == SCFLOW_CONV_BF16_3X3 || bk == SCFLOW_CONV_BF16_3X3N) {  // one packing for both
     const long long total = scflow_conv_packed_size_bk(cout, c0, c1, kh, kw, stride, w, bk);
     if (total < 0) return (int)total;
     c3_bf16_pack_kernel<<<pack_blocks(total), 256, 0, (hipStream_t)stream>>>(
@@ -1415,6 +1444,7 @@ SCFLOW_API long long scflow_conv_workspace_bytes(const scflow_conv_args* args) {
   if (!args) return SCFLOW_EINVAL;
   if (args->bk == SCFLOW_CONV_BF16) return sep_bf16_launchable(*args) ? 0 : SCFLOW_EUNSUPPORTED;
   if (args->bk == SCFLOW_CONV_BF16_3X3) return c3_bf16_launchable(*args) ? 0 : SCFLOW_EUNSUPPORTED;
+  if (args->bk == SCFLOW_CONV_BF16_3X3N) return c3n_bf16_status(*args);
   if (args->bk != SCFLOW_CONV_WINO4) return 0;
   if (!wino4_shape(*args) || args->n <= 0 || args->c0 <= 0) return SCFLOW_EUNSUPPORTED;
   return wino4_workspace_bytes(*args);
@@ -1496,6 +1526,17 @@ ConvPlan plan_conv(const scflow_conv_args& a) {
     p.cp0 = a.c0;
     p.nst = (a.c0 + a.c1) / SBSC;
     return is(SCFLOW_PLAN_C3_BF16, c3_bf16_blocks(a), round_up(a.cout, 64) / 64);
+  }
+  if (a.bk == SCFLOW_CONV_BF16_3X3N) {  // its encoder form (opt-in alike)
+    if (const int st = c3n_bf16_status(a)) return fail(st);
+    // (the affines are read as float4s, the residual one float per lane: its stride is held to
+    // the sources' rule all the same, so that a buffer serves as source and residual alike)
+    if (!src_aligned || !aligned16(a.weight) || (a.res && (a.sres & 3)) ||
+        (a.in_scale && (!aligned16(a.in_scale) || !aligned16(a.in_shift))))
+      return fail(SCFLOW_EALIGN);
+    p.cp0 = a.c0;
+    p.nst = (a.c0 + a.c1) / SBSC;
+    return is(SCFLOW_PLAN_C3_BF16N, c3_bf16_blocks(a), round_up(a.cout, 64) / 64);
   }
   if (a.bk == SCFLOW_CONV_1X1W) {
     if (!conv1x1w_launchable(a)) return fail(SCFLOW_EUNSUPPORTED);
@@ -1621,7 +1662,10 @@ int launch_sep_bf16(const scflow_conv_args& a, const ConvPlan& c, hipStream_t st
 }
 int launch_c3_bf16(const scflow_conv_args& a, const ConvPlan& c, hipStream_t st) {
   const C3Bf16Params p{a, c.cp0 / SBSC, c.nst, round_up(a.cout, 32) / 32};
-  return launch_k<conv3_bf16_kernel>(c, c3_bf16_lds_bytes(), st, p);
+  // the encoder form without a fused pointer is the motion encoder's launch, bit for bit
+  if (c.kind == SCFLOW_PLAN_C3_BF16N && has_fused_norm(a))
+    return launch_k<conv3_bf16_kernel<true>>(c, c3_bf16_lds_bytes(), st, p);
+  return launch_k<conv3_bf16_kernel<false>>(c, c3_bf16_lds_bytes(), st, p);
 }
 
 // the one place a plan becomes a template instantiation and a launch
@@ -1632,7 +1676,8 @@ int launch_plan(const scflow_conv_args& a, const ConvPlan& c, hipStream_t st) {
     case SCFLOW_PLAN_WINO5: return launch_wino(a, c, st);
     case SCFLOW_PLAN_WINO4: return launch_wino4(a, st);
     case SCFLOW_PLAN_SEP_BF16: return launch_sep_bf16(a, c, st);
-    case SCFLOW_PLAN_C3_BF16: return launch_c3_bf16(a, c, st);
+    case SCFLOW_PLAN_C3_BF16:
+    case SCFLOW_PLAN_C3_BF16N: return launch_c3_bf16(a, c, st);
     case SCFLOW_PLAN_1X1W: return launch_conv1x1w(a, c, st);
     case SCFLOW_PLAN_MFMA:
     case SCFLOW_PLAN_1X1: {

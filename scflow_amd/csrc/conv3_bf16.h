@@ -1,6 +1,8 @@
 // Direct 3×3 convolution on bf16 MFMA with fp32 accumulation for the motion encoder's 3×3 convs
-// (corr_net.1, flow_net.1, out_net) — the opt-in SCFLOW_CONV_BF16_3X3 format; included by conv.hip
-// (inside its anonymous namespace) after conv_sep_bf16.h, whose rounding helpers it shares.
+// (corr_net.1, flow_net.1, out_net) — the opt-in SCFLOW_CONV_BF16_3X3 format — and, with the fused
+// normalisation pieces (NORM, below), for the RAFT encoders' stride-1 3×3 convs — the opt-in
+// SCFLOW_CONV_BF16_3X3N format; included by conv.hip (inside its anonymous namespace) after
+// conv_sep_bf16.h, whose rounding helpers it shares.
 // Reference: MotionEncoder, models/decoder/raft_decoder.py:75-85 (channel tables), :152-166.
 //
 // Every buffer stays fp32.  The inputs are rounded to bf16 (round to nearest even) as the halo is
@@ -27,6 +29,16 @@
 // a ring of three register groups, two groups (12 MFMAs) ahead of their use.  Stores are masked
 // per lane to channels < cout (a lane owns one channel of the 32×32 C/D block).  No atomics, a
 // fixed summation order: bitwise reproducible.
+//
+// NORM = true is the RAFT encoder's form (SCFLOW_CONV_BF16_3X3N with a fused pointer set): the
+// producer's InstanceNorm + ReLU on load — x' = relu(fmaf(x, in_scale[img][c], in_shift[img][c])),
+// one fp32 rounding, applied before the bf16 rounding and only to pixels inside the image, so the
+// zero padding (the neighbouring sample's rows included) stays 0 and not relu(in_shift) — and in
+// the epilogue the eval-BatchNorm affine and the residual, read with the store's lane map.  A
+// thread stages the same 8 channels of every halo pixel, so its scale and shift are 16 registers
+// per stage; they are fetched when the stage's halo has been consumed from the staging registers
+// (hstore), not with the halo's loads ahead of the MFMAs, where they would be live together with
+// the whole weight ring.  NORM = false is the motion encoder's kernel, unchanged.
 
 constexpr int C3OR = 4, C3OC = 32;           // output rows × columns per workgroup
 constexpr int C3HR = C3OR + 2, C3HC = C3OC + 2;  // halo
@@ -44,6 +56,7 @@ constexpr size_t c3_bf16_lds_bytes() { return (size_t)2 * C3BUF * 16; }
 
 // (4 waves per SIMD: the grids and times of DESIGN.md §25 rest on four workgroups per CU, so a
 // build that needs more than 128 VGPRs must say so instead of halving the occupancy)
+template <bool NORM>
 __global__ __launch_bounds__(256, 4) void conv3_bf16_kernel(C3Bf16Params P) {
   extern __shared__ floatx4 smem4[];  // 2 × [C3HR·C3HC pixels][SBPITCH] 16-B slots
   const scflow_conv_args& a = P.a;
@@ -51,7 +64,7 @@ __global__ __launch_bounds__(256, 4) void conv3_bf16_kernel(C3Bf16Params P) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave & 1, wn = wave >> 1, li = lane & 31, hh = lane >> 5;
   const int W = a.w;
-  const int XB = W / C3OC;  // column blocks per image row (1 or 2)
+  const int XB = W / C3OC;  // column blocks per image row
   const int bx = blockIdx.x, by = blockIdx.y;
   const int blocks_per_img = (a.h / C3OR) * XB;
   const int img = bx / blocks_per_img;
@@ -88,7 +101,24 @@ __global__ __launch_bounds__(256, 4) void conv3_bf16_kernel(C3Bf16Params P) {
       ra[j][1] = wino_bload(hsrc, p >= 0 ? off + 16 : WINO_OOB, 0);
     }
   };
-  auto hstore = [&](int buf) {
+  // stage s's halo from the staging registers into LDS buffer buf
+  auto hstore = [&](int buf, int s) {
+    if constexpr (NORM) {
+      if (a.in_scale) {  // (c1 = 0: every stage is source 0's; workgroup-uniform)
+        const size_t c = (size_t)img * a.c0 + s * SBSC + hq * 8;
+        const floatx4 sc0 = *(const floatx4*)(a.in_scale + c), sc1 = *(const floatx4*)(a.in_scale + c + 4);
+        const floatx4 sh0 = *(const floatx4*)(a.in_shift + c), sh1 = *(const floatx4*)(a.in_shift + c + 4);
+#pragma unroll
+        for (int j = 0; j < C3NA; ++j) {
+          const bool in = hpix[j] >= 0;  // zero padding stays zero (it pads the normalised activation)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            ra[j][0][e] = in ? fmaxf(__builtin_fmaf(ra[j][0][e], sc0[e], sh0[e]), 0.f) : 0.f;
+            ra[j][1][e] = in ? fmaxf(__builtin_fmaf(ra[j][1][e], sc1[e], sh1[e]), 0.f) : 0.f;
+          }
+        }
+      }
+    }
 #pragma unroll
     for (int j = 0; j < C3NA; ++j) {
       const int idx = tid + 256 * j;
@@ -144,7 +174,7 @@ __global__ __launch_bounds__(256, 4) void conv3_bf16_kernel(C3Bf16Params P) {
   uload(u0, 0);
   uload(u1, 1);
   hload(0);
-  hstore(0);
+  hstore(0, 0);
   __syncthreads();
   for (int s = 0; s < P.nst; ++s) {
     const int buf = s & 1;
@@ -163,7 +193,7 @@ __global__ __launch_bounds__(256, 4) void conv3_bf16_kernel(C3Bf16Params P) {
     taprow(buf, 1, 1, u1);
     uload(u1, g + 7);
     taprow(buf, 1, 2, u2);
-    if (more) hstore(buf ^ 1);  // its readers finished with buf ^ 1 before the last barrier
+    if (more) hstore(buf ^ 1, s + 1);  // its readers finished with buf ^ 1 before the last barrier
     __syncthreads();
   }
 
@@ -173,6 +203,32 @@ __global__ __launch_bounds__(256, 4) void conv3_bf16_kernel(C3Bf16Params P) {
   const int col = nb * 32 + li;
   if (col >= a.cout) return;
   const float bias = a.bias ? a.bias[col] : 0.f;
+  if constexpr (NORM) {
+    // v = conv + bias; the eval-BatchNorm affine; the residual (this lane's channel of the pixels
+    // it stores, read before any of them is written: res may be the output); the activation
+    const bool aff = a.out_scale != nullptr;
+    const float osc = aff ? a.out_scale[col] : 1.f;
+    const float osh = aff ? a.out_shift[col] : 0.f;
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) {
+      const size_t row0 = (size_t)(img * a.h + oy0 + wm * 2 + rb) * W + ox0;
+      float rv[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int x = (r & 3) + 8 * (r >> 2) + 4 * hh;
+        rv[r] = a.res ? a.res[(row0 + x) * a.sres + col] : 0.f;
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int x = (r & 3) + 8 * (r >> 2) + 4 * hh;
+        float v = acc[rb][r] + bias;
+        if (aff) v = v * osc + osh;
+        if (a.res) v += rv[r];
+        a.out[(row0 + x) * a.so + col] = act_apply(v, a.act);
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int rb = 0; rb < 2; ++rb) {
     const size_t row0 = (size_t)(img * a.h + oy0 + wm * 2 + rb) * W + ox0;

@@ -19,6 +19,10 @@ Data flow (channels-last between layers; reference lines in brackets):
   ``SCFlowRefiner.extract_feat`` (scflow_refiner.py:101-104) turns the context output into
   ``tanh(h) | relu(cxt)`` in the same launch.
 
+``RAFTEncoder.bf16`` (default False, read at every ``forward_cl``; inference only) moves the
+stride-1 3×3 convs of the stages in ``BF16_STAGES`` from the fp32 kernels onto the bf16 direct conv
+(``_lib.CONV_BF16_3X3N``) with the same fused arguments; everything else stays fp32.
+
 Inference only: BatchNorm in training mode (batch statistics + running-stat update) raises.
 """
 from __future__ import annotations
@@ -150,13 +154,53 @@ def _wino_conv(conv: nn.Conv2d, x: Tensor, out: Tensor, n: int, h: int, w: int, 
                res=None if res is None else ops.Chan.whole(res.view(-1, res.shape[-1])))
 
 
+# The stages whose stride-1 3×3 convs ``RAFTEncoder.bf16`` runs on the bf16 direct conv: those whose
+# bf16 launch measured faster than the fp32 launch it replaces by more than the run-to-run spread
+# at 256² and at 512² images (tools/enc_bench.py, DESIGN.md §26's wiring table).
+BF16_STAGES: Tuple[str, ...] = ("res_layer1", "res_layer2", "res_layer3")
+
+
+def _bf16_conv(conv: nn.Conv2d, x: Tensor, out: Tensor, n: int, h: int, w: int, cin: int,
+               in_scale: Optional[Tensor] = None, in_shift: Optional[Tensor] = None,
+               out_scale: Optional[Tensor] = None, out_shift: Optional[Tensor] = None,
+               res: Optional[Tensor] = None, act: Optional[str] = None) -> None:
+    """``_wino_conv``'s launch on the bf16 direct 3×3 conv (SCFLOW_CONV_BF16_3X3N): the input is
+    rounded to bf16 after the fused IN + ReLU, the weights when packed (cached next to the Winograd
+    packing, keyed the same way); a map outside the kernel's domain raises ScflowError."""
+    wt = conv.weight
+    key = (wt.data_ptr(), wt._version, cin, w, _lib.weights_generation())
+    cache = getattr(conv, "_scflow_bf16", None)
+    if cache is None or cache[0] != key:
+        cache = (key, ops.pack_conv_weight(wt.detach().float(), cin, 0, w, 1, _lib.CONV_BF16_3X3N))
+        conv._scflow_bf16 = cache
+    cout = conv.out_channels
+    ops.conv2d(ops.Chan.whole(x.view(-1, cin)), cache[1], _bias(conv), n, h, w, cout, 3, 3, 1, 1,
+               act, out=ops.Chan.whole(out.view(-1, cout)), bk=_lib.CONV_BF16_3X3N,
+               in_scale=in_scale, in_shift=in_shift, out_scale=out_scale, out_shift=out_shift,
+               res=None if res is None else ops.Chan.whole(res.view(-1, res.shape[-1])))
+
+
+def _bf16_shaped(conv: nn.Conv2d) -> bool:
+    return (conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and
+            conv.groups == 1 and conv.dilation == (1, 1))
+
+
 def _bias(conv: nn.Conv2d) -> Optional[Tensor]:
     return None if conv.bias is None else conv.bias.detach().float().contiguous()
 
 
 @MODELS.register_module()
 class RAFTEncoder(nn.Module):
-    """models/encoder/raft_encoder.py:13-314, 'Basic' / 'Large' (BasicBlock) variants."""
+    """models/encoder/raft_encoder.py:13-314, 'Basic' / 'Large' (BasicBlock) variants.
+
+    ``bf16`` (default False; inference only — train/model.py never selects it): the stride-1 3×3
+    convs of ``BF16_STAGES`` take the bf16 direct 3×3 conv (``_lib.CONV_BF16_3X3N``): inputs are
+    rounded to bf16 on load (after the fused IN + ReLU) and weights when packed, products
+    accumulate in fp32, every buffer, bias, affine, residual and statistic stays fp32.  The stem,
+    the stride-2 convs, the 1×1 convs and ``enc_stats`` / ``enc_apply`` keep their fp32 kernels.  A
+    wired conv on a map the kernel does not cover (width not a multiple of 32, height not of 4)
+    raises ScflowError — no fallback.  ``last_bf16``: the names of the convs that ran on it in the
+    last forward (``()`` with the knob off)."""
     _arch_settings = {"Basic": (BasicBlock, (2, 2, 2)), "Large": (BasicBlock, (2, 2))}
     _stem_channels = {"Basic": 64, "Small": 32, "Large": 64}
     _base_channels = {"Basic": (64, 96, 128), "Small": (8, 16, 24), "Large": (64, 96)}
@@ -215,6 +259,8 @@ class RAFTEncoder(nn.Module):
         self.conv2 = nn.Conv2d(self.base_channels[-1], out_channels, kernel_size=1)
         if self.norm_type == "IN" and getattr(norm1, "affine", False):
             raise NotImplementedError("affine InstanceNorm is not supported by the HIP encoder")
+        self.bf16 = False
+        self.last_bf16: Tuple[str, ...] = ()
 
     @property
     def norm1(self) -> nn.Module:
@@ -260,9 +306,13 @@ class RAFTEncoder(nn.Module):
                          out_scale=bsc, out_shift=bsh, act="ReLU")
             cur = stem
         cin = c0
+        ran = []  # the convs the knob moved to bf16 in this forward
         for name in self.res_layers:
-            for blk in getattr(self, name):
-                cur, h, w, cin = self._block(blk, cur, n, h, w, cin, IN)
+            wired = bool(self.bf16) and name in BF16_STAGES
+            for i, blk in enumerate(getattr(self, name)):
+                cur, h, w, cin = self._block(blk, cur, n, h, w, cin, IN,
+                                             ran if wired else None, f"{name}.{i}")
+        self.last_bf16 = tuple(ran)
         cout = self.out_channels
         if out is None:
             out = torch.empty(n, h, w, cout, device=dev)
@@ -270,7 +320,17 @@ class RAFTEncoder(nn.Module):
                      act=act, act2=act2, act_split=act_split)
         return out
 
-    def _block(self, blk: BasicBlock, x: Tensor, n: int, h: int, w: int, cin: int, IN: bool):
+    def _block(self, blk: BasicBlock, x: Tensor, n: int, h: int, w: int, cin: int, IN: bool,
+               ran: Optional[list] = None, tag: str = ""):
+        """One BasicBlock.  ``ran`` not None: the block's stage is wired to ``bf16`` — its stride-1
+        3×3 convs run on the bf16 direct conv and their names (``tag``.conv1 / .conv2) are
+        appended to it."""
+        def bf16(conv: nn.Conv2d, name: str) -> bool:
+            if ran is None or not _bf16_shaped(conv):
+                return False
+            ran.append(f"{tag}.{name}")
+            return True
+
         planes = blk.conv1.out_channels
         st = blk.stride
         oh, ow = (h + 2 - 3) // st + 1, (w + 2 - 3) // st + 1
@@ -280,14 +340,18 @@ class RAFTEncoder(nn.Module):
         ds = blk.downsample
         if IN:
             sc1, sh1, sc2, sh2 = (torch.empty(n, planes, device=dev) for _ in range(4))
-            if st == 1 and _wino_ok(blk.conv1, h, w, cin):
+            if bf16(blk.conv1, "conv1"):
+                _bf16_conv(blk.conv1, x, y1, n, h, w, cin)
+            elif st == 1 and _wino_ok(blk.conv1, h, w, cin):
                 _wino_conv(blk.conv1, x, y1, n, h, w, cin)
             else:
                 ops.enc_conv(x, _packed(blk.conv1), _bias(blk.conv1), n, h, w, cin, planes, 3, st, 1,
                              y1)
             ops.enc_instance_norm_stats(y1, n, oh * ow, planes, sc1, sh1, eps=blk.norm1.eps)
             y2 = torch.empty_like(y1)
-            if _wino_ok(blk.conv2, oh, ow, planes):
+            if bf16(blk.conv2, "conv2"):
+                _bf16_conv(blk.conv2, y1, y2, n, oh, ow, planes, in_scale=sc1, in_shift=sh1)
+            elif _wino_ok(blk.conv2, oh, ow, planes):
                 _wino_conv(blk.conv2, y1, y2, n, oh, ow, planes, in_scale=sc1, in_shift=sh1)
             else:
                 ops.enc_conv(y1, _packed(blk.conv2), _bias(blk.conv2), n, oh, ow, planes, planes, 3,
@@ -303,7 +367,10 @@ class RAFTEncoder(nn.Module):
                 ops.enc_apply(y2, sc2, sh2, out, n, oh * ow, planes, id=x)
         else:
             b1, b2 = _bn_affine(blk.norm1), _bn_affine(blk.norm2)
-            if st == 1 and _wino_ok(blk.conv1, h, w, cin):
+            if bf16(blk.conv1, "conv1"):
+                _bf16_conv(blk.conv1, x, y1, n, h, w, cin, out_scale=b1[0], out_shift=b1[1],
+                           act="ReLU")
+            elif st == 1 and _wino_ok(blk.conv1, h, w, cin):
                 _wino_conv(blk.conv1, x, y1, n, h, w, cin, out_scale=b1[0], out_shift=b1[1],
                            act="ReLU")
             else:
@@ -315,7 +382,10 @@ class RAFTEncoder(nn.Module):
                 bd = _bn_affine(ds[1])
                 ops.enc_conv(x, _packed(ds[0]), _bias(ds[0]), n, h, w, cin, planes, 1, st, 0, res,
                              out_scale=bd[0], out_shift=bd[1])
-            if _wino_ok(blk.conv2, oh, ow, planes):
+            if bf16(blk.conv2, "conv2"):
+                _bf16_conv(blk.conv2, y1, out, n, oh, ow, planes, out_scale=b2[0], out_shift=b2[1],
+                           res=res, act="ReLU")
+            elif _wino_ok(blk.conv2, oh, ow, planes):
                 _wino_conv(blk.conv2, y1, out, n, oh, ow, planes, out_scale=b2[0], out_shift=b2[1],
                            res=res, act="ReLU")
             else:

@@ -362,7 +362,7 @@ def conv2d(src0: Chan, packed: Tensor, bias: Optional[Tensor], n: int, h: int, w
            rh: Optional[Chan] = None, hid: Optional[Chan] = None, stride: int = 1,
            bias_map: Optional[Chan] = None, bk: int = 16, **fused) -> None:
     """One scflow_conv2d launch; ``fused``: in_scale / in_shift / out_scale / out_shift / res
-    (Winograd 3×3 only, see conv2d_args)."""
+    (Winograd 3×3 and ``_lib.CONV_BF16_3X3N`` only, see conv2d_args)."""
     a = conv2d_args(src0, packed, bias, n, h, w, cout, kh, kw, ph, pw, act, out, src1, epilogue,
                     gate, rh, hid, stride, bias_map, bk, **fused)
     _launch("scflow_conv2d", src0.buf,ctypes.byref(a))
@@ -484,8 +484,9 @@ def conv2d_args(src0: Chan, packed: Tensor, bias: Optional[Tensor], n: int, h: i
                 in_shift: Optional[Tensor] = None, out_scale: Optional[Tensor] = None,
                 out_shift: Optional[Tensor] = None, res: Optional[Chan] = None) -> "_lib.ConvArgs":
     """The validated scflow_conv_args of one launch (see conv2d).  in_/out_scale/shift and res
-    (Winograd 3×3 only): relu(x·in_scale + in_shift) on load, (conv + b)·out_scale + out_shift,
-    + res before the activation."""
+    (Winograd 3×3 and the bf16 direct 3×3 conv's encoder form, ``_lib.CONV_BF16_3X3N``, only):
+    relu(x·in_scale + in_shift) on load, (conv + b)·out_scale + out_shift, + res before the
+    activation."""
     for nm, ch in (("src0", src0), ("src1", src1), ("out", out), ("gate", gate), ("rh", rh),
                    ("hid", hid), ("bias_map", bias_map)):
         if ch is not None:

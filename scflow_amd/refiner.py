@@ -74,6 +74,14 @@ class _RefinerBase(nn.Module):
         self.freeze_bn_flag = bool(freeze_bn)
         if freeze_bn:
             self.freeze_bn()
+        # opt-in bf16 direct conv for the encoders' stride-1 3×3 convs (RAFTEncoder.bf16, DESIGN.md
+        # §26): re-read at every extract_feat / fused forward, independent of the decoder's
+        # gru_bf16 / menc_bf16; inference only
+        self.enc_bf16 = False
+
+    def _set_enc_bf16(self) -> None:
+        for enc in (self.real_encoder, self.render_encoder, self.context):
+            enc.bf16 = bool(self.enc_bf16)
 
     def freeze_bn(self) -> None:
         """scflow_refiner.py:75-78, raft_refiner_flow.py:75-78: every BatchNorm2d in eval mode
@@ -93,6 +101,7 @@ class _RefinerBase(nn.Module):
                      ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
         """scflow_refiner.py:84-106, raft_refiner_flow.py:90-113 — NCHW (render_feat, real_feat,
         tanh(h), relu(cxt))."""
+        self._set_enc_bf16()
         real_feat = self.real_encoder(real_images)
         render_feat = self.render_encoder(render_images)
         n = render_images.shape[0]
@@ -107,6 +116,7 @@ class _RefinerBase(nn.Module):
         """The fused path up to the decoder call: (render_feat, real_feat, hx, h, w) with ``hx``
         the decoder's channels-last GRU buffer, tanh(h) | relu(cxt) already in place."""
         N = real.shape[0]
+        self._set_enc_bf16()
         # feature encoder(s): one launch sequence over cat[real, render] when shared
         if self.real_encoder is self.render_encoder:
             both = torch.cat([real, render], 0)
