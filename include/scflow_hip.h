@@ -38,6 +38,10 @@
  *                               reference leaves to that CPU tool after ADD.format_results   metrics/add.py:402-446
  *   scflow_scene_visibility  <- bop_toolkit's calc_gt_masks / calc_gt_info (instance masks, visib_fract,
  *                               boxes), which a ready-made BOP data set ships as files; no reference code
+ *   scflow_flow_gt           <- get_flow_from_delta_pose_and_depth + filter_flow_by_mask / _by_depth /
+ *                               _by_face_index, one launch   models/utils/pose.py:92-121, models/utils/flow.py:6-59
+ *   scflow_flow_epe          <- cal_epe and eval_epe_and_occ's occlusion term   models/utils/flow.py:64-88,
+ *                               models/refiner/raft_refiner_flow_mask.py:239-259
  *   scflow_transpose         <- layout plumbing (NCHW <-> channels-last slices), no reference equivalent
  *   scflow_ph_*              <- MultiClassPoseHead.forward                models/head/pose_head.py:201-211
  *   scflow_enc_*             <- RAFTEncoder.forward (Basic; IN / BN)      models/encoder/raft_encoder.py:286-314
@@ -1018,6 +1022,77 @@ typedef struct {
   int* stats; int* inst_id; float* depth_scene; float* depth_inst; unsigned char* mask_visib;
 } scflow_scene_args;
 int scflow_scene_visibility(const scflow_scene_args* args, void* stream);
+
+/* Flow validation: the GT flow with its validity filters, and the end-point-error
+ * statistics of a predicted flow against it (models/utils/pose.py:92-121, models/utils/flow.py:6-88,
+ * raft_refiner_flow_mask.py:239-259).
+ *
+ * scflow_flow_gt: one launch, one thread per pixel of [n][h][w], any h and w.  The flow source is
+ *   one of two: (a) the poses — depth [n][h][w] lifted with (R_ref, t_ref, K) and projected with
+ *   (R_gt, t_gt, K), a pixel with depth ≤ 0 getting invalid_num in both channels; the bits are
+ *   those of scflow_lift_points + scflow_pose_flow — or (b) flow_in [n][2][h][w] (then K, R_ref,
+ *   t_ref, R_gt, t_gt must be NULL).  A filter is selected by its non-NULL pointer; each decides
+ *   from the pixel's UNFILTERED flow (fx, fy), so the fused result is that of applying them one
+ *   after another.  bad0 = fx ≥ invalid_num ∧ fy ≥ invalid_num.  Sampling coordinates are the
+ *   reference's coords_grid, g = (x + fx)·2 / max(w − 1, 1) − 1 (rows likewise), then
+ *   torch.grid_sample's with zero padding, in fp32 without contraction:
+ *     gt_mask [n][h][w] (mask_dtype 0: bytes / bool, 1: float): bilinear, align_corners=False — on a
+ *       grid normalised for align_corners=True, the reference's quirk; invalid where the sample
+ *       < 0.9 or bad0.
+ *     depth1 [n][h][w] (the GT pose's rendered depth; depth is then depth0): both with
+ *       non-positive values read as 0; bilinear, align_corners=True; consistent = |d0 − warped| /
+ *       (d0 + 0.1) < depth_thr.  depth_combine SCFLOW_FLOW_DEPTH_OR: invalid where bad0 or not
+ *       consistent; SCFLOW_FLOW_DEPTH_REFERENCE: invalid where bad0 AND not consistent, the
+ *       reference's expression, which only rewrites pixels that are invalid already.
+ *     face_index1 / face_index2 [n][h][w] (face_dtype 0: int32, 1: int64; compared as float32):
+ *       nearest (ties to even), align_corners=True; invalid where the sample of face_index2
+ *       differs from face_index1 or bad0.
+ *   Outputs, each optional, at least one: flow [n][2][h][w], the unfiltered flow; flow_filtered
+ *   [n][2][h][w], invalid_num in both channels where a filter says invalid, else the unfiltered
+ *   flow's bits.  Out of place: no output may be flow_in or the other output.
+ *   SCFLOW_EINVAL before any launch: args NULL, n / h / w < 1, not exactly one flow source, no
+ *   output, depth1 without depth, one face map without the other, an unknown dtype or combine, an
+ *   aliased output.  SCFLOW_EUNSUPPORTED: h·w ≥ 2^30, n > 65535.
+ *
+ * scflow_flow_epe: per sample, over the pixels of flow_tgt / flow_pred [n][2][h][w]:
+ *   inside = |flow_tgt| < max_flow; valid = inside ∧ (mask NULL ∨ mask ≥ 0.5) (mask [n][h][w]
+ *   float); err = |flow_tgt − flow_pred| (fp32: sqrt(dx·dx + dy·dy), no contraction).
+ *   counts [n][4] int = the number of valid pixels, then of valid pixels with err < thresh[k];
+ *   sums [n][2] double = Σ err over valid pixels, and with occ_pred [n][h][w] Σ over ALL pixels of
+ *   |inside − occ_pred| (else 0); err_map [n][h][w] (optional) = err where valid, err·0 elsewhere.
+ *   counts and sums come together or not at all (then err_map is required).  The counts are exact;
+ *   the sums are fp64 sums of the fp32 terms in a fixed order (per workgroup, then over the
+ *   workgroups in a second launch): no floating-point atomics, the same bits in every run.  A
+ *   sample without a valid pixel has counts 0 and sums 0.  workspace: 8-byte aligned, at least
+ *   scflow_flow_epe_workspace(n, h, w) bytes (a host-side query, no GPU), needed with counts / sums.
+ *   SCFLOW_EINVAL / SCFLOW_EUNSUPPORTED as above. */
+#define SCFLOW_FLOW_DEPTH_OR 0
+#define SCFLOW_FLOW_DEPTH_REFERENCE 1
+typedef struct {
+  const float* depth;                            /* [n][h][w]: source (a), and depth0 of the depth filter */
+  const float* K; const float* R_ref; const float* t_ref; /* source (a) */
+  const float* R_gt; const float* t_gt;
+  const float* flow_in;                          /* source (b) [n][2][h][w] */
+  int n, h, w;
+  float invalid_num;
+  const void* gt_mask; int mask_dtype;           /* mask filter */
+  const float* depth1; float depth_thr; int depth_combine; /* depth filter */
+  const void* face_index1; const void* face_index2; int face_dtype; /* face-index filter */
+  float* flow; float* flow_filtered;             /* outputs */
+} scflow_flow_gt_args;
+int scflow_flow_gt(const scflow_flow_gt_args* args, void* stream);
+
+typedef struct {
+  const float* flow_tgt; const float* flow_pred; /* [n][2][h][w] */
+  const float* mask; const float* occ_pred;      /* optional [n][h][w] */
+  int n, h, w;
+  float max_flow;
+  float thresh[3];
+  int* counts; double* sums; float* err_map;     /* outputs */
+  void* workspace; long long workspace_bytes;
+} scflow_flow_epe_args;
+long long scflow_flow_epe_workspace(int n, int h, int w);
+int scflow_flow_epe(const scflow_flow_epe_args* args, void* stream);
 
 /* Batched RANSAC-PnP (replaces BaseFlowRefiner.solve_pose's per-sample host loop,
  * models/refiner/base_flow_refiner.py:99-155, over get_2d_3d_corr_by_fw_flow and

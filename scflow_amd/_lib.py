@@ -148,6 +148,34 @@ class SceneArgs(ctypes.Structure):
     ]
 
 
+class FlowGtArgs(ctypes.Structure):
+    """Mirror of ``scflow_flow_gt_args`` (include/scflow_hip.h)."""
+    _fields_ = [
+        ("depth", c_vp), ("K", c_vp), ("R_ref", c_vp), ("t_ref", c_vp), ("R_gt", c_vp), ("t_gt", c_vp),
+        ("flow_in", c_vp),
+        ("n", c_int), ("h", c_int), ("w", c_int),
+        ("invalid_num", c_float),
+        ("gt_mask", c_vp), ("mask_dtype", c_int),
+        ("depth1", c_vp), ("depth_thr", c_float), ("depth_combine", c_int),
+        ("face_index1", c_vp), ("face_index2", c_vp), ("face_dtype", c_int),
+        ("flow", c_vp), ("flow_filtered", c_vp),
+    ]
+
+
+class FlowEpeArgs(ctypes.Structure):
+    """Mirror of ``scflow_flow_epe_args`` (include/scflow_hip.h)."""
+    _fields_ = [
+        ("flow_tgt", c_vp), ("flow_pred", c_vp), ("mask", c_vp), ("occ_pred", c_vp),
+        ("n", c_int), ("h", c_int), ("w", c_int),
+        ("max_flow", c_float),
+        ("thresh", c_float * 3),
+        ("counts", c_vp), ("sums", c_vp), ("err_map", c_vp),
+        ("workspace", c_vp), ("workspace_bytes", c_ll),
+    ]
+
+
+FLOW_DEPTH_OR, FLOW_DEPTH_REFERENCE = 0, 1  # SCFLOW_FLOW_DEPTH_*: scflow_flow_gt_args.depth_combine
+
 SCFLOW_LIGHT_FIXED, SCFLOW_LIGHT_PER_IMAGE, SCFLOW_LIGHT_BATCH_ZNEAR = 0, 1, 2
 
 # name -> (restype, argtypes); every function the header declares
@@ -280,6 +308,9 @@ SIGNATURES = {
     "scflow_vsd_counts": (c_int, [c_vp] * 7 + [c_int, c_float, c_vp, c_int, c_int, c_int, c_int,
                                                c_vp]),
     "scflow_scene_visibility": (c_int, [ctypes.POINTER(SceneArgs), c_vp]),
+    "scflow_flow_gt": (c_int, [ctypes.POINTER(FlowGtArgs), c_vp]),
+    "scflow_flow_epe_workspace": (c_ll, [c_int, c_int, c_int]),
+    "scflow_flow_epe": (c_int, [ctypes.POINTER(FlowEpeArgs), c_vp]),
     "scflow_conv_wgrad_workspace": (c_int, [ctypes.POINTER(WgradArgs), ctypes.POINTER(c_ll)]),
     "scflow_conv_wgrad": (c_int, [ctypes.POINTER(WgradArgs), c_vp]),
     "scflow_conv_wgrad_batched": (c_int, [ctypes.POINTER(WgradArgs), c_int, c_vp, c_vp, c_vp, c_vp]),

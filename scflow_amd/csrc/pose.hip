@@ -30,40 +30,13 @@ __global__ __launch_bounds__(256) void lift_kernel(const float* __restrict__ dep
                                                    const float* __restrict__ R,
                                                    const float* __restrict__ t,
                                                    floatx4* __restrict__ pts, int H, int W) {
-#pragma clang fp contract(off)
   __shared__ float sh[21];  // Kinv[9], Rinv[9], t[3]
   const int n = blockIdx.y;
-  if (threadIdx.x == 0) {
-    inv3x3(K + 9 * n, sh);
-    inv3x3(R + 9 * n, sh + 9);
-    sh[18] = t[3 * n];
-    sh[19] = t[3 * n + 1];
-    sh[20] = t[3 * n + 2];
-  }
+  if (threadIdx.x == 0) lift_prologue(sh, n, K, R, t);
   __syncthreads();
   const int HW = H * W;
-  for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
-    const float d = depth[(size_t)n * HW + p];
-    floatx4 o = {0.f, 0.f, 0.f, 0.f};
-    if (d > 0.f) {
-      const float px = (float)(p % W) * d, py = (float)(p / W) * d, pz = 1.f * d;
-      float c[3];
-      for (int r = 0; r < 3; ++r) {
-        float s = sh[r * 3 + 0] * px;
-        s += sh[r * 3 + 1] * py;
-        s += sh[r * 3 + 2] * pz;
-        c[r] = s - sh[18 + r];
-      }
-      for (int r = 0; r < 3; ++r) {
-        float s = sh[9 + r * 3 + 0] * c[0];
-        s += sh[9 + r * 3 + 1] * c[1];
-        s += sh[9 + r * 3 + 2] * c[2];
-        o[r] = s;
-      }
-      o[3] = 1.f;
-    }
-    pts[(size_t)n * HW + p] = o;
-  }
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256)
+    pts[(size_t)n * HW + p] = lift_point(sh, depth[(size_t)n * HW + p], p % W, p / W);
 }
 
 // flow[n][0/1][p] from pose (R,t) in LDS; `upd` != 0: compute (R,t) from the delta first

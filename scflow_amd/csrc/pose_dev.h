@@ -90,6 +90,41 @@ __device__ void pose_update_one(const float* d6, const float* dt, const float* R
   td[2] = vz;
 }
 
+// the lift's operands of image n into LDS (Kinv[9] Rinv[9] t[3]); the caller synchronises
+__device__ __forceinline__ void lift_prologue(float* sh, int n, const float* K, const float* R,
+                                              const float* t) {
+  inv3x3(K + 9 * n, sh);
+  inv3x3(R + 9 * n, sh + 9);
+  sh[18] = t[3 * n];
+  sh[19] = t[3 * n + 1];
+  sh[20] = t[3 * n + 2];
+}
+
+// object-frame point {X, Y, Z, valid} of pixel (X, Y) with depth d under the pose in LDS
+// (lift_prologue); a non-positive depth gives {0, 0, 0, 0}
+__device__ __forceinline__ floatx4 lift_point(const float* sh, float d, int X, int Y) {
+#pragma clang fp contract(off)
+  floatx4 o = {0.f, 0.f, 0.f, 0.f};
+  if (d > 0.f) {
+    const float px = (float)X * d, py = (float)Y * d, pz = 1.f * d;
+    float c[3];
+    for (int r = 0; r < 3; ++r) {
+      float s = sh[r * 3 + 0] * px;
+      s += sh[r * 3 + 1] * py;
+      s += sh[r * 3 + 2] * pz;
+      c[r] = s - sh[18 + r];
+    }
+    for (int r = 0; r < 3; ++r) {
+      float s = sh[9 + r * 3 + 0] * c[0];
+      s += sh[9 + r * 3 + 1] * c[1];
+      s += sh[9 + r * 3 + 2] * c[2];
+      o[r] = s;
+    }
+    o[3] = 1.f;
+  }
+  return o;
+}
+
 // flow of one pixel p (point P = {X, Y, Z, valid}) under the pose in LDS (R[9] t[3] K[9])
 __device__ __forceinline__ void proj_flow(const float* sh, const floatx4 P, int X, int Y,
                                           float invalid, float& fx, float& fy) {

@@ -29,6 +29,11 @@ op                             reference                                        
                                RandomSmooth on the crop, in the same launch
 ``scflow::patch_extract_aug_   the same with RandomBackground before the stages,       no
 bg``                           color_transform.py:177-244
+``scflow::flow_gt``            get_flow_from_delta_pose_and_depth + filter_flow_by_   no
+                               mask / _by_depth / _by_face_index in one launch,
+                               pose.py:92-121, flow.py:6-59
+``scflow::flow_epe``           cal_epe's per-sample statistics and eval_epe_and_occ's  no
+                               occlusion term, flow.py:64-88
 =============================  =====================================================  =========
 
 The backward formulas are ops of their own (``scflow::corr_pyramid_backward``,
@@ -487,3 +492,54 @@ def _(frames, masks, frame_index, geom, valid, aug, backgrounds, background_size
     n = frame_index.shape[0]
     return (frames.new_empty(n, 3, size, size, dtype=torch.float32),
             frames.new_empty(n, dtype=torch.int32))
+
+
+# ------------------------------------------------------------------------------------ flow validation
+@torch.library.custom_op("scflow::flow_gt", mutates_args=(), device_types="cuda")
+def flow_gt(depth: Optional[Tensor], K: Optional[Tensor], R_ref: Optional[Tensor],
+            t_ref: Optional[Tensor], R_gt: Optional[Tensor], t_gt: Optional[Tensor],
+            flow_in: Optional[Tensor], invalid_num: float, gt_mask: Optional[Tensor],
+            depth1: Optional[Tensor], depth_thr: float, depth_combine: str,
+            face_index1: Optional[Tensor], face_index2: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """The GT flow and its validity filters in one launch (``ops.flow_gt``; replaces
+    get_flow_from_delta_pose_and_depth, pose.py:92-121, and filter_flow_by_mask / _by_depth /
+    _by_face_index, flow.py:6-59): the poses with depth [N, H, W], or ``flow_in`` [N, 2, H, W] (then
+    ``depth`` is only the depth filter's depth0) → (flow, filtered flow), both [N, 2, H, W].  Not
+    differentiable."""
+    return ops.flow_gt(depth, K, R_ref, t_ref, R_gt, t_gt, flow_in, invalid_num, gt_mask, depth1,
+                       depth_thr, depth_combine, face_index1, face_index2)
+
+
+@flow_gt.register_fake
+def _(depth, K, R_ref, t_ref, R_gt, t_gt, flow_in, invalid_num, gt_mask, depth1, depth_thr,
+      depth_combine, face_index1, face_index2):
+    if flow_in is not None:
+        n, _, h, w = flow_in.shape
+        like = flow_in
+    else:
+        n, h, w = depth.shape
+        like = depth
+    return (like.new_empty(n, 2, h, w, dtype=torch.float32),
+            like.new_empty(n, 2, h, w, dtype=torch.float32))
+
+
+@torch.library.custom_op("scflow::flow_epe", mutates_args=(), device_types="cuda")
+def flow_epe(flow_tgt: Tensor, flow_pred: Tensor, mask: Optional[Tensor], max_flow: float,
+             threshs: List[float], occ_pred: Optional[Tensor], want_map: bool, want_stats: bool
+             ) -> Tuple[Tensor, Tensor, Tensor]:
+    """End-point-error statistics per sample (``ops.flow_epe``; replaces cal_epe, flow.py:64-88, and
+    eval_epe_and_occ's occlusion term): → (counts [N, 4] int32, sums [N, 2] float64, error map
+    [N, H, W]); what is not wanted is an empty tensor.  Not differentiable."""
+    counts, sums, emap = ops.flow_epe(flow_tgt, flow_pred, mask, max_flow, threshs, occ_pred,
+                                      want_stats, want_map)
+    e = flow_tgt.new_empty(0)
+    return (e.int() if counts is None else counts, e.double() if sums is None else sums,
+            e if emap is None else emap)
+
+
+@flow_epe.register_fake
+def _(flow_tgt, flow_pred, mask, max_flow, threshs, occ_pred, want_map, want_stats):
+    n, _, h, w = flow_tgt.shape
+    return (flow_tgt.new_empty((n, 4) if want_stats else (0,), dtype=torch.int32),
+            flow_tgt.new_empty((n, 2) if want_stats else (0,), dtype=torch.float64),
+            flow_tgt.new_empty((n, h, w) if want_map else (0,), dtype=torch.float32))

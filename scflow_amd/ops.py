@@ -1781,6 +1781,143 @@ def scene_visibility(verts: Tensor, faces: Tensor, vert_offset: Tensor, face_off
     return out
 
 
+FLOW_DEPTH_COMBINE = {"or": _lib.FLOW_DEPTH_OR, "reference": _lib.FLOW_DEPTH_REFERENCE}
+
+
+def _require_all_contiguous(named) -> None:
+    """Contiguity of every given tensor, checked before anything else (device included)."""
+    for nm, x, *_ in named:
+        if isinstance(x, torch.Tensor) and not x.is_contiguous():
+            raise ValueError(f"{nm} must be contiguous")
+
+
+def _require_plane(t: Tensor, name: str, dtypes, shape: tuple) -> None:
+    """A filter's [N, H, W] input of one of ``dtypes`` (the first is the one reported)."""
+    if isinstance(t, torch.Tensor) and t.dtype not in dtypes:
+        raise TypeError(f"{name} must be one of {dtypes}, got {t.dtype}")
+    _require(t, name, dtype=t.dtype if isinstance(t, torch.Tensor) else dtypes[0])
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+
+
+def flow_gt(depth: Optional[Tensor] = None, K: Optional[Tensor] = None, R_ref: Optional[Tensor] = None,
+            t_ref: Optional[Tensor] = None, R_gt: Optional[Tensor] = None, t_gt: Optional[Tensor] = None,
+            flow_in: Optional[Tensor] = None, invalid_num: float = 400.0,
+            gt_mask: Optional[Tensor] = None, depth1: Optional[Tensor] = None, depth_thr: float = 0.2,
+            depth_combine: str = "or", face_index1: Optional[Tensor] = None,
+            face_index2: Optional[Tensor] = None, want_flow: bool = True, want_filtered: bool = True
+            ) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """scflow_flow_gt, one launch: the flow from the poses (depth [N, H, W], K, R_ref, t_ref, R_gt,
+    t_gt: the bits of ``lift_points`` + ``pose_flow``) or ``flow_in`` [N, 2, H, W], and the filters
+    selected by gt_mask (bool / uint8 / float32), depth1 (with ``depth`` as depth0) and face_index1
+    / face_index2 (int32 or int64, both the same) → (flow, filtered flow), None where not wanted.
+    Out of place.  Every argument is checked before the launch."""
+    poses = (("K", K, (3, 3)), ("R_ref", R_ref, (3, 3)), ("t_ref", t_ref, (3,)),
+             ("R_gt", R_gt, (3, 3)), ("t_gt", t_gt, (3,)))
+    _require_all_contiguous(poses + (("depth", depth), ("flow_in", flow_in), ("gt_mask", gt_mask),
+                                     ("depth1", depth1), ("face_index1", face_index1),
+                                     ("face_index2", face_index2)))
+    if flow_in is not None:
+        if any(x is not None for _, x, _ in poses):
+            raise ValueError("flow_gt takes the poses or flow_in, not both")
+        if not isinstance(flow_in, torch.Tensor) or flow_in.dim() != 4 or flow_in.shape[1] != 2:
+            raise ValueError("flow_in must be a [N, 2, H, W] tensor")
+        n, _, h, w = flow_in.shape
+        dev = flow_in
+    else:
+        if depth is None or any(x is None for _, x, _ in poses):
+            raise ValueError("flow_gt needs depth, K, R_ref, t_ref, R_gt and t_gt, or flow_in")
+        if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
+            raise ValueError("depth must be a [N, H, W] tensor")
+        n, h, w = depth.shape
+        dev = depth
+    if n < 1 or h < 1 or w < 1:
+        raise ValueError(f"flow_gt: empty input [{n}, {h}, {w}]")
+    if flow_in is not None:
+        _require(flow_in, "flow_in")
+    else:
+        for nm, x, shp in poses:
+            _require(x, nm)
+            if tuple(x.shape) != (n,) + shp:
+                raise ValueError(f"{nm} must be {(n,) + shp}, got {tuple(x.shape)}")
+    if depth_combine not in FLOW_DEPTH_COMBINE:
+        raise ValueError(f"depth_combine = {depth_combine!r}: one of {tuple(FLOW_DEPTH_COMBINE)}")
+    if not (want_flow or want_filtered):
+        raise ValueError("flow_gt: no output wanted")
+    if depth is not None:
+        _require_plane(depth, "depth", (torch.float32,), (n, h, w))
+    if gt_mask is not None:
+        _require_plane(gt_mask, "gt_mask", (torch.bool, torch.uint8, torch.float32), (n, h, w))
+    if depth1 is not None:
+        if depth is None:
+            raise ValueError("the depth filter needs depth (depth0) beside depth1")
+        _require_plane(depth1, "depth1", (torch.float32,), (n, h, w))
+    if (face_index1 is None) != (face_index2 is None):
+        raise ValueError("the face-index filter needs face_index1 and face_index2")
+    if face_index1 is not None:
+        _require_plane(face_index1, "face_index1", (torch.int32, torch.int64), (n, h, w))
+        _require_plane(face_index2, "face_index2", (face_index1.dtype,), (n, h, w))
+    flow = torch.empty(n, 2, h, w, device=dev.device) if want_flow else None
+    filt = torch.empty(n, 2, h, w, device=dev.device) if want_filtered else None
+    a = _lib.FlowGtArgs()
+    a.depth, a.flow_in = _p(depth), _p(flow_in)
+    a.K, a.R_ref, a.t_ref, a.R_gt, a.t_gt = _p(K), _p(R_ref), _p(t_ref), _p(R_gt), _p(t_gt)
+    a.n, a.h, a.w, a.invalid_num = n, h, w, float(invalid_num)
+    a.gt_mask = _p(gt_mask)
+    a.mask_dtype = 1 if gt_mask is not None and gt_mask.dtype == torch.float32 else 0
+    a.depth1, a.depth_thr, a.depth_combine = _p(depth1), float(depth_thr), FLOW_DEPTH_COMBINE[depth_combine]
+    a.face_index1, a.face_index2 = _p(face_index1), _p(face_index2)
+    a.face_dtype = 1 if face_index1 is not None and face_index1.dtype == torch.int64 else 0
+    a.flow, a.flow_filtered = _p(flow), _p(filt)
+    _launch("scflow_flow_gt", dev, ctypes.byref(a))
+    return flow, filt
+
+
+def flow_epe(flow_tgt: Tensor, flow_pred: Tensor, mask: Optional[Tensor] = None,
+             max_flow: float = 400.0, threshs: Sequence[float] = (1.0, 3.0, 5.0),
+             occ_pred: Optional[Tensor] = None, want_stats: bool = True, want_map: bool = False
+             ) -> Tuple[Optional[Tensor], Optional[Tensor], Optional[Tensor]]:
+    """scflow_flow_epe: flow_tgt / flow_pred [N, 2, H, W], mask / occ_pred [N, H, W] float32 or None
+    → (counts [N, 4] int32 = valid pixels and valid pixels below each of the three thresholds, sums
+    [N, 2] float64 = Σ error over valid pixels and Σ |inside − occ_pred| over all pixels, error map
+    [N, H, W] or None).  Two launches and no synchronisation; the sums are bitwise reproducible."""
+    _require_all_contiguous((("flow_tgt", flow_tgt), ("flow_pred", flow_pred), ("mask", mask),
+                             ("occ_pred", occ_pred)))
+    if not isinstance(flow_tgt, torch.Tensor) or not isinstance(flow_pred, torch.Tensor) or \
+            flow_tgt.dim() != 4 or flow_tgt.shape[1] != 2 or flow_pred.shape != flow_tgt.shape:
+        raise ValueError("flow_tgt and flow_pred must be tensors of the same shape [N, 2, H, W]")
+    n, _, h, w = flow_tgt.shape
+    if n < 1 or h < 1 or w < 1:
+        raise ValueError(f"flow_epe: empty input [{n}, {h}, {w}]")
+    _require(flow_tgt, "flow_tgt")
+    _require(flow_pred, "flow_pred")
+    for nm, x in (("mask", mask), ("occ_pred", occ_pred)):
+        if x is not None:
+            _require_plane(x, nm, (torch.float32,), (n, h, w))
+    threshs = tuple(float(v) for v in threshs)
+    if len(threshs) != 3:
+        raise ValueError(f"flow_epe counts under three thresholds, got {threshs}")
+    if not (want_stats or want_map):
+        raise ValueError("flow_epe: no output wanted")
+    dev = flow_tgt.device
+    counts = sums = ws = emap = None
+    if want_stats:
+        counts = torch.empty(n, 4, dtype=torch.int32, device=dev)
+        sums = torch.empty(n, 2, dtype=torch.float64, device=dev)
+        ws = torch.empty(max(int(_lib.load().scflow_flow_epe_workspace(n, h, w)), 8) // 8,
+                         dtype=torch.float64, device=dev)
+    if want_map:
+        emap = torch.empty(n, h, w, device=dev)
+    a = _lib.FlowEpeArgs()
+    a.flow_tgt, a.flow_pred, a.mask, a.occ_pred = _p(flow_tgt), _p(flow_pred), _p(mask), _p(occ_pred)
+    a.n, a.h, a.w, a.max_flow = n, h, w, float(max_flow)
+    a.thresh = (ctypes.c_float * 3)(*threshs)
+    a.counts, a.sums, a.err_map = _p(counts), _p(sums), _p(emap)
+    a.workspace, a.workspace_bytes = _p(ws), 0 if ws is None else ws.numel() * 8
+    _launch("scflow_flow_epe", flow_tgt, ctypes.byref(a))
+    return counts, sums, emap
+
+
 def group_norm_forward(x: Tensor, gamma: Tensor, beta: Tensor, groups: int, eps: float,
                        relu: bool) -> Tuple[Tensor, Tensor]:
     """GroupNorm (+ReLU) of channels-last x [n, h, w, c] (c == 4·groups) → (y, stats [n·groups, 2]

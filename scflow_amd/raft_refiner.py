@@ -20,6 +20,10 @@ with the mask decoder, ``SequenceLoss(L1Loss)`` on the ×8 occlusions) on the HI
 Functions, convex upsampling included (``scflow_convex_upsample_bwd``); ``train.step.TrainStep``
 takes these refiners.  The inference paths above stay under ``torch.no_grad()``.
 
+``val_step(batch)`` (raft_refiner_flow_mask.py:261-281) validates the flow: ``get_flow`` at
+``test_cfg['iters']``, then the end-point error, its 1 / 3 / 5 px accuracies and the occlusion error
+against the GT flow on the device (``scflow_amd/flow_eval.py``).
+
 ``solve_pose`` (base_flow_refiner.py:99-155) and ``get_pose`` turn the last ×8 flow into poses on
 the batched HIP RANSAC-PnP (``ops.pnp_ransac``: compacted 2D-3D correspondences, P3P hypotheses on
 hashed samples, one scoring kernel, Gauss-Newton on the winner's inliers) instead
@@ -113,6 +117,34 @@ class _RAFTFlowRefiner(_RefinerBase):
         vals += [res["loss_flow"], res["loss"]]
         host = torch.stack([v.detach().reshape(()) for v in vals]).tolist()  # the one sync
         return res["loss"], None, OrderedDict(zip(names, host))
+
+    def val_step(self, batch):
+        """raft_refiner_flow_mask.py:261-281 on an already formatted batch (the keys ``loss`` takes;
+        ``gt_masks`` optional): ``get_flow`` at ``test_cfg['iters']`` iterations under ``no_grad``,
+        then ``flow_eval.eval_epe_and_occ(reduction='total_mean')`` of the last ×8 flow → ``dict(
+        log_vars, num_samples)``.  With the mask decoder ``log_vars`` holds the reference's keys
+        (``epe_*``, ``epe_noc_*`` with ``gt_masks``, ``occ`` of the last occlusion).  RAFTRefinerFlow:
+        the same without ``occ``, and without ``gt_masks`` ``epe_noc_*`` repeats ``epe_*`` — the
+        evident intent of BaseFlowRefiner's ``val_step`` / ``eval_epe`` (base_flow_refiner.py:74-96),
+        which cannot run as written (``reducion=``, :89, and a call with one argument too many,
+        :80-81).  One host synchronisation, where ``log_vars`` turns into floats; The forward
+        runs in eval mode; ``decoder.iters`` and every module's training mode are left as they
+        were."""
+        from . import flow_eval
+        iters, self.decoder.iters = self.decoder.iters, self.test_iter_num
+        try:
+            with self._eval_mode():
+                out = self.get_flow(batch["render_images"], batch["real_images"])
+        finally:
+            self.decoder.iters = iters
+        flows, occs = out if isinstance(out, tuple) else (out, None)
+        with torch.no_grad():
+            metric = flow_eval.eval_epe_and_occ(
+                flows[-1], None if occs is None else occs[-1], batch["depth"], batch["gt_rotation"],
+                batch["gt_translation"], batch["internel_k"], batch["ref_rotation"],
+                batch["ref_translation"], batch.get("gt_masks"), max_flow=self.max_flow,
+                reduction="total_mean", noc_without_mask=occs is None)
+            return dict(log_vars=flow_eval.log_vars(metric), num_samples=len(flows[-1]))
 
     # ------------------------------------------------------------------ RANSAC-PnP
     def _pnp_valid(self, occlusion: Optional[Tensor], rendered_depths: Tensor) -> Optional[Tensor]:

@@ -13,6 +13,10 @@ or textured ``meshes=`` it renders UV-textured images, and ``render`` / ``refine
 pre-processing stay the reference's; the loss configuration arguments are accepted and the
 losses live in ``scflow_amd.train``.
 
+``val_step(batch)`` validates the flow of an already formatted batch on the device (end-point error
+and 1 / 3 / 5 px accuracies of the flow head's and the pose-induced flow against the GT flow,
+``scflow_amd/flow_eval.py``); the reference's SCFlowRefiner has none.
+
 ``get_pose`` runs the work MI355X-first rather than call by call:
 
 * the shared feature encoder runs ONCE on cat[real, rendered] (2B images; InstanceNorm is per
@@ -27,6 +31,7 @@ to the decoder call (``_features_into_hx``).
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Optional, Tuple, Union
 
 import torch
@@ -96,6 +101,18 @@ class _RefinerBase(nn.Module):
         if mode and self.freeze_bn_flag:
             self.freeze_bn()
         return self
+
+    @contextlib.contextmanager
+    def _eval_mode(self):
+        """Every module in eval mode inside the block (the HIP encoders run BatchNorm on its
+        running statistics only), each module's own flag put back afterwards."""
+        modes = [(m, m.training) for m in self.modules()]
+        self.eval()
+        try:
+            yield
+        finally:
+            for m, t in modes:
+                m.training = t
 
     def extract_feat(self, render_images: Tensor, real_images: Tensor
                      ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
@@ -310,6 +327,40 @@ class SCFlowRefiner(_RefinerBase):
 
     def forward(self, *args, **kwargs):
         return self.get_pose(*args, **kwargs)
+
+    def val_step(self, batch):
+        """Flow validation on an already formatted batch (the keys ``loss`` / ``TrainStep`` take,
+        ``synthetic.make_train_batch``; ``gt_masks`` optional): ``get_pose`` at
+        ``test_cfg['iters']`` iterations under ``no_grad``, then the end-point error of the last
+        flow from the flow head against the GT flow — ``epe_mean``, ``epe_1px``, ``epe_3px``,
+        ``epe_5px`` and, with ``gt_masks``, ``epe_noc_*`` (the keys of RAFTRefinerFlowMask's
+        ``val_step``, raft_refiner_flow_mask.py:239-281, ``reduction='total_mean'``) — and the same
+        for the last pose-induced flow as ``pose_epe_*`` / ``pose_epe_noc_*``.  The reference's
+        SCFlowRefiner has no ``val_step``: this is an extension.  → ``dict(log_vars, num_samples)``;
+        one ``scflow_flow_gt`` launch serves both flows, and the one host synchronisation is where
+        ``log_vars`` turns into floats.  The forward runs in eval mode; ``decoder.iters`` and every
+        module's training mode are left as they were."""
+        from . import flow_eval
+        iters, self.decoder.iters = self.decoder.iters, self.test_iter_num
+        try:
+            with self._eval_mode():
+                out = self.get_pose(batch["render_images"], batch["real_images"],
+                                    batch["ref_rotation"], batch["ref_translation"], batch["depth"],
+                                    batch["internel_k"], batch["label"])
+        finally:
+            self.decoder.iters = iters
+        with torch.no_grad():
+            masks = batch.get("gt_masks")
+            flow, noc = flow_eval.gt_flow(batch["depth"], batch["internel_k"], batch["ref_rotation"],
+                                          batch["ref_translation"], batch["gt_rotation"],
+                                          batch["gt_translation"], invalid_num=self.max_flow,
+                                          gt_mask=masks)
+            noc = noc if masks is not None else None
+            metric = flow_eval.epe_and_occ_against(flow, noc, out[1][-1], None, self.max_flow,
+                                                   "total_mean")
+            metric.update(flow_eval.epe_and_occ_against(flow, noc, out[0][-1], None, self.max_flow,
+                                                        "total_mean", prefix="pose_epe"))
+            return dict(log_vars=flow_eval.log_vars(metric), num_samples=len(out[1][-1]))
 
     # ------------------------------------------------------------------ fused path
     def _get_pose(self, render, real, R, t, depth, K, label, init_flow, head_label=None):
