@@ -1047,28 +1047,78 @@ int wino_swz(int R, int C) {
 }
 
 #include "conv_wino4.h"
+#include "conv_bf16_core.h"
 #include "conv_sep_bf16.h"
+#include "conv3_bf16.h"
 
-// The bf16 direct conv's domain (SCFLOW_CONV_BF16, conv_sep_bf16.h): F(4,5)'s shapes with both
-// sources' channels multiples of the 32-channel stage and whole 32-channel output blocks
-bool sep_bf16_shape(int cout, int c0, int c1, int kh, int kw, int stride, int w) {
-  const bool k = (kh == 1 && kw == 5) || (kh == 5 && kw == 1);
-  return k && stride == 1 && (w == 32 || w == 64) && c0 > 0 && c1 >= 0 && c0 % SBSC == 0 &&
-         c1 % SBSC == 0 && cout > 0 && cout % 32 == 0;
+// The opt-in bf16 direct formats (never scflow_conv_pick_bk's choice), one description each:
+// SCFLOW_CONV_BF16 (conv_sep_bf16.h) is 1×5 / 5×1 on F(4,5)'s shapes with whole 32-channel output
+// blocks; SCFLOW_CONV_BF16_3X3 (conv3_bf16.h) is "same" 3×3 at stride 1 on 32- or 64-wide maps of
+// whole 4-row blocks with any cout, the plain epilogue without bias map, fused normalisation or
+// residual; SCFLOW_CONV_BF16_3X3N is the RAFT encoder's form of it — the same kernel, packing and
+// grid on maps of any width that is a multiple of the 32-column block, with the producer's
+// InstanceNorm + ReLU on load (one source only), the eval-BatchNorm affine and the residual.  In
+// all three both sources' channels are multiples of the 32-channel stage.
+struct Bf16Format {
+  int bk, plan;
+  int taps;       // 5: 1×5 / 5×1, 9: 3×3
+  bool any_w;     // widths: any multiple of 32, else 32 or 64
+  bool norm;      // takes the fused normalisation pointers and the residual
+  int cout_mult;  // cout is a multiple of it
+  int cout_pad;   // the packed weights' cout padding
+};
+constexpr Bf16Format BF16_FORMATS[] = {
+    {SCFLOW_CONV_BF16, SCFLOW_PLAN_SEP_BF16, 5, false, false, 32, 64},
+    {SCFLOW_CONV_BF16_3X3, SCFLOW_PLAN_C3_BF16, 9, false, false, 1, 32},
+    {SCFLOW_CONV_BF16_3X3N, SCFLOW_PLAN_C3_BF16N, 9, true, true, 1, 32},
+};
+const Bf16Format* bf16_format(int bk) {
+  for (const Bf16Format& f : BF16_FORMATS)
+    if (f.bk == bk) return &f;
+  return nullptr;
 }
-bool sep_bf16_launchable(const scflow_conv_args& a) {
-  // (buffer-load byte offsets stay below WINO_OOB)
-  const long long span = (long long)a.n * a.h * a.w * (a.s0 > a.s1 ? a.s0 : a.s1) * 4;
-  return sep_bf16_shape(a.cout, a.c0, a.c1, a.kh, a.kw, a.stride, a.w) && wino_launchable(a) &&
-         a.s0 >= a.c0 && (a.c1 == 0 || a.s1 >= a.c1) && span < WINO_OOB;
+bool bf16_shape(const Bf16Format& f, int cout, int c0, int c1, int kh, int kw, int stride, int w) {
+  const bool k = f.taps == 5 ? (kh == 1 && kw == 5) || (kh == 5 && kw == 1) : kh == 3 && kw == 3;
+  const bool wide = f.any_w ? w > 0 && w % C3OC == 0 : w == 32 || w == 64;
+  return k && stride == 1 && wide && c0 > 0 && c1 >= 0 && c0 % SBSC == 0 && c1 % SBSC == 0 &&
+         cout > 0 && cout % f.cout_mult == 0;
 }
-// packed floats: two bf16 per float, output channels padded to 64
-long long sep_bf16_packed_size(int cout, int c0, int c1) {
-  return (long long)round_up(cout, 64) * (c0 + c1) * 5 / 2;
+// packed floats: two bf16 per float
+long long bf16_packed_size(const Bf16Format& f, int cout, int c0, int c1) {
+  return (long long)round_up(cout, f.cout_pad) * (c0 + c1) * f.taps / 2;
 }
-// 128 output channels per workgroup when that still fills both workgroup slots of every CU, else
-// 64 (measured, B = 16 at 32×32, z|r 256 → 256: 256 workgroups of 128 channels 25.2 µs, 512 of 64
-// 19.7 µs; B = 32 at 64×64: 129 vs 140 µs (1×5), 142 vs 190 µs (5×1))
+// the grid's x extent (a shape of the format's)
+long long bf16_blocks(const Bf16Format& f, const scflow_conv_args& a) {
+  return f.taps == 5 ? wino_blocks(a) : (long long)a.n * (a.h / C3OR) * (a.w / C3OC);
+}
+// Pixel strides hold their channels, buffer-load byte offsets stay below WINO_OOB and the grid's x
+// extent fits.  Source 1's stride counts only when c1 > 0: with c1 == 0 every stage is source 0's
+// (nst0 == nst) and the kernels never read s1 — before the formats shared this check,
+// SCFLOW_CONV_BF16 alone took max(s0, s1) regardless.
+bool bf16_spans_ok(const Bf16Format& f, const scflow_conv_args& a) {
+  const int smax = a.c1 > 0 && a.s1 > a.s0 ? a.s1 : a.s0;
+  const long long span = (long long)a.n * a.h * a.w * smax * 4;
+  return a.s0 >= a.c0 && (a.c1 == 0 || a.s1 >= a.c1) && span < WINO_OOB &&
+         bf16_blocks(f, a) <= 0x7fffffffLL;
+}
+// SCFLOW_OK, or what every entry point answers before a launch: SCFLOW_EINVAL for half an affine
+// or a residual narrower than the output (the form that takes them), SCFLOW_EUNSUPPORTED outside
+// the domain
+int bf16_status(const Bf16Format& f, const scflow_conv_args& a) {
+  if (f.norm && ((!a.in_scale) != (!a.in_shift) || (!a.out_scale) != (!a.out_shift) ||
+                 (a.res && a.sres < a.cout)))
+    return SCFLOW_EINVAL;
+  if (!bf16_shape(f, a.cout, a.c0, a.c1, a.kh, a.kw, a.stride, a.w)) return SCFLOW_EUNSUPPORTED;
+  const bool domain =
+      f.taps == 5 ? wino_launchable(a)  // F(4,5)'s: padding, whole blocks of rows, no fused pointer
+                  : a.ph == 1 && a.pw == 1 && a.n > 0 && a.h > 0 && a.h % C3OR == 0 &&
+                        a.epilogue == SCFLOW_EPI_PLAIN && !a.bias_map &&
+                        (f.norm ? !(a.in_scale && a.c1 != 0) : !has_fused_norm(a));
+  return domain && bf16_spans_ok(f, a) ? SCFLOW_OK : SCFLOW_EUNSUPPORTED;
+}
+// SCFLOW_CONV_BF16: 128 output channels per workgroup when that still fills both workgroup slots
+// of every CU, else 64 (measured, B = 16 at 32×32, z|r 256 → 256: 256 workgroups of 128 channels
+// 25.2 µs, 512 of 64 19.7 µs; B = 32 at 64×64: 129 vs 140 µs (1×5), 142 vs 190 µs (5×1))
 #ifndef SEP_BF16_NBW  // tuning build flag: 1 / 2 forces 64 / 128 channels where the shape allows
 #define SEP_BF16_NBW 0
 #endif
@@ -1076,64 +1126,12 @@ int sep_bf16_nbw(const scflow_conv_args& a, int cus) {
   if (SEP_BF16_NBW) return SEP_BF16_NBW == 2 && a.cout % 128 == 0 ? 2 : 1;
   return a.cout % 128 == 0 && wino_blocks(a) * (a.cout / 128) >= 2LL * cus ? 2 : 1;
 }
-
-#include "conv3_bf16.h"
-
-// The bf16 direct 3×3 conv's domain (SCFLOW_CONV_BF16_3X3, conv3_bf16.h): "same" 3×3 at stride 1
-// on 32- or 64-wide maps of whole 4-row blocks, both sources' channels multiples of the 32-channel
-// stage, any cout, the plain epilogue without bias map, fused normalisation or residual
-bool c3_bf16_shape(int cout, int c0, int c1, int kh, int kw, int stride, int w) {
-  return kh == 3 && kw == 3 && stride == 1 && (w == 32 || w == 64) && c0 > 0 && c1 >= 0 &&
-         c0 % SBSC == 0 && c1 % SBSC == 0 && cout > 0;
-}
-long long c3_bf16_blocks(const scflow_conv_args& a) {
-  return (long long)a.n * (a.h / C3OR) * (a.w / C3OC);
-}
-bool c3_bf16_launchable(const scflow_conv_args& a) {
-  if (!c3_bf16_shape(a.cout, a.c0, a.c1, a.kh, a.kw, a.stride, a.w) || a.ph != 1 || a.pw != 1 ||
-      a.n <= 0 || a.h <= 0 || a.h % C3OR || a.epilogue != SCFLOW_EPI_PLAIN || a.bias_map ||
-      has_fused_norm(a))
-    return false;
-  // (buffer-load byte offsets stay below WINO_OOB; the grid's x extent fits)
-  const int smax = a.c1 > 0 && a.s1 > a.s0 ? a.s1 : a.s0;
-  const long long span = (long long)a.n * a.h * a.w * smax * 4;
-  return a.s0 >= a.c0 && (a.c1 == 0 || a.s1 >= a.c1) && span < WINO_OOB &&
-         c3_bf16_blocks(a) <= 0x7fffffffLL;
-}
-// packed floats: two bf16 per float, output channels padded to a 32-channel block
-long long c3_bf16_packed_size(int cout, int c0, int c1) {
-  return (long long)round_up(cout, 32) * (c0 + c1) * 9 / 2;
-}
-// The RAFT encoder's form of it (SCFLOW_CONV_BF16_3X3N): the same kernel, packing and grid on maps
-// of any width that is a multiple of the 32-column block, with the producer's InstanceNorm + ReLU
-// on load (one source only), the eval-BatchNorm affine and the residual.  SCFLOW_CONV_BF16_3X3's
-// own domain above is not widened.
-bool c3n_bf16_shape(int cout, int c0, int c1, int kh, int kw, int stride, int w) {
-  return kh == 3 && kw == 3 && stride == 1 && w > 0 && w % C3OC == 0 && c0 > 0 && c1 >= 0 &&
-         c0 % SBSC == 0 && c1 % SBSC == 0 && cout > 0;
-}
-// SCFLOW_OK, or what every entry point answers before a launch: SCFLOW_EINVAL for half an affine
-// or a residual narrower than the output, SCFLOW_EUNSUPPORTED outside the domain
-int c3n_bf16_status(const scflow_conv_args& a) {
-  if ((!a.in_scale) != (!a.in_shift) || (!a.out_scale) != (!a.out_shift) ||
-      (a.res && a.sres < a.cout))
-    return SCFLOW_EINVAL;
-  if (!c3n_bf16_shape(a.cout, a.c0, a.c1, a.kh, a.kw, a.stride, a.w) || a.ph != 1 || a.pw != 1 ||
-      a.n <= 0 || a.h <= 0 || a.h % C3OR || a.epilogue != SCFLOW_EPI_PLAIN || a.bias_map ||
-      (a.in_scale && a.c1 != 0))
-    return SCFLOW_EUNSUPPORTED;
-  const int smax = a.c1 > 0 && a.s1 > a.s0 ? a.s1 : a.s0;
-  const long long span = (long long)a.n * a.h * a.w * smax * 4;
-  return a.s0 >= a.c0 && (a.c1 == 0 || a.s1 >= a.c1) && span < WINO_OOB &&
-                 c3_bf16_blocks(a) <= 0x7fffffffLL
-             ? SCFLOW_OK
-             : SCFLOW_EUNSUPPORTED;
-}
-// Always 64 output channels per workgroup (four workgroups per CU).  A 128-channel variant of the
-// kernel (170 VGPRs, two per CU) measured slower for every motion-encoder conv at both benchmark
-// shapes (profiles/menc_bf16/nbw_variants.txt: B = 16 at 32×32, corr_net.1 22 vs 54 µs, out_net 20
-// vs 50; B = 32 at 64×64, corr_net.1 131 vs 235 µs, out_net 90 vs 120) and was dropped: sep_bf16_nbw's
-// rule — 128 once that fills both workgroup slots of every CU — is not taken over.
+// The 3×3 formats: always 64 output channels per workgroup (four workgroups per CU).  A
+// 128-channel variant of the kernel (170 VGPRs, two per CU) measured slower for every
+// motion-encoder conv at both benchmark shapes (profiles/menc_bf16/nbw_variants.txt: B = 16 at
+// 32×32, corr_net.1 22 vs 54 µs, out_net 20 vs 50; B = 32 at 64×64, corr_net.1 131 vs 235 µs,
+// out_net 90 vs 120) and was dropped: sep_bf16_nbw's rule — 128 once that fills both workgroup
+// slots of every CU — is not taken over.
 
 // F(4×4,3×3) (conv_wino4.h) for the 3×3 convs it covers with at least WINO4_MIN_COUT output
 // channels; SCFLOW_CONV_WINO4 = 0 off, 1 default, 2 every covered shape (A/B).  Measured at
@@ -1333,17 +1331,9 @@ SCFLOW_API long long scflow_conv_packed_size_bk(int cout, int c0, int c1, int kh
       return SCFLOW_EUNSUPPORTED;
     return wino4_packed_size(cout, c0, c1);
   }
-  if (bk == SCFLOW_CONV_BF16) {
-    if (!sep_bf16_shape(cout, c0, c1, kh, kw, stride, w)) return SCFLOW_EUNSUPPORTED;
-    return sep_bf16_packed_size(cout, c0, c1);
-  }
-  if (bk == SCFLOW_CONV_BF16_3X3) {
-    if (!c3_bf16_shape(cout, c0, c1, kh, kw, stride, w)) return SCFLOW_EUNSUPPORTED;
-    return c3_bf16_packed_size(cout, c0, c1);
-  }
-  if (bk == SCFLOW_CONV_BF16_3X3N) {
-    if (!c3n_bf16_shape(cout, c0, c1, kh, kw, stride, w)) return SCFLOW_EUNSUPPORTED;
-    return c3_bf16_packed_size(cout, c0, c1);
+  if (const Bf16Format* f = bf16_format(bk)) {
+    if (!bf16_shape(*f, cout, c0, c1, kh, kw, stride, w)) return SCFLOW_EUNSUPPORTED;
+    return bf16_packed_size(*f, cout, c0, c1);
   }
   if (bk != 0 && bk != 8 && bk != 16) return SCFLOW_EINVAL;
   return scflow_conv_packed_size(cout, c0, c1, kh, kw, stride, w);
@@ -1366,18 +1356,11 @@ SCFLOW_API int scflow_conv_pack_weights(const float* w_oihw, float* packed, int 
                                                                    conv1x1w_kb(c0), total);
     return scflow_launch_status();
   }
-  if (bk == SCFLOW_CONV_BF16) {
+  if (const Bf16Format* f = bf16_format(bk)) {  // (the two 3×3 formats pack alike)
     const long long total = scflow_conv_packed_size_bk(cout, c0, c1, kh, kw, stride, w, bk);
     if (total < 0) return (int)total;
-    sep_bf16_pack_kernel<<<pack_blocks(total), 256, 0, (hipStream_t)stream>>>(
-        w_oihw, packed, cout, c0 + c1, (c0 + c1) / SBKC, total);
-    return scflow_launch_status();
-  }
-  if (bk == SCFLOW_CONV_BF16_3X3 || bk == SCFLOW_CONV_BF16_3X3N) {  // one packing for both
-    const long long total = scflow_conv_packed_size_bk(cout, c0, c1, kh, kw, stride, w, bk);
-    if (total < 0) return (int)total;
-    c3_bf16_pack_kernel<<<pack_blocks(total), 256, 0, (hipStream_t)stream>>>(
-        w_oihw, packed, cout, c0 + c1, (c0 + c1) / SBKC, total);
+    bf16_pack_kernel<<<pack_blocks(total), 256, 0, (hipStream_t)stream>>>(
+        w_oihw, packed, cout, c0 + c1, (c0 + c1) / SBKC, f->taps, total);
     return scflow_launch_status();
   }
   if (bk == SCFLOW_CONV_WINO4) {
@@ -1442,9 +1425,7 @@ SCFLOW_API int scflow_conv_pick_bk(const scflow_conv_args* args) {
 
 SCFLOW_API long long scflow_conv_workspace_bytes(const scflow_conv_args* args) {
   if (!args) return SCFLOW_EINVAL;
-  if (args->bk == SCFLOW_CONV_BF16) return sep_bf16_launchable(*args) ? 0 : SCFLOW_EUNSUPPORTED;
-  if (args->bk == SCFLOW_CONV_BF16_3X3) return c3_bf16_launchable(*args) ? 0 : SCFLOW_EUNSUPPORTED;
-  if (args->bk == SCFLOW_CONV_BF16_3X3N) return c3n_bf16_status(*args);
+  if (const Bf16Format* f = bf16_format(args->bk)) return bf16_status(*f, *args);
   if (args->bk != SCFLOW_CONV_WINO4) return 0;
   if (!wino4_shape(*args) || args->n <= 0 || args->c0 <= 0) return SCFLOW_EUNSUPPORTED;
   return wino4_workspace_bytes(*args);
@@ -1512,31 +1493,19 @@ ConvPlan plan_conv(const scflow_conv_args& a) {
     p.status = wino4_status(a);
     return p.status ? p : is(SCFLOW_PLAN_WINO4, 0);
   }
-  if (a.bk == SCFLOW_CONV_BF16) {  // bf16 direct 1×5 / 5×1 (opt-in: never scflow_conv_pick_bk's choice)
-    if (!sep_bf16_launchable(a)) return fail(SCFLOW_EUNSUPPORTED);
-    if (!src_aligned || !aligned16(a.weight)) return fail(SCFLOW_EALIGN);
-    p.cp0 = a.c0;
-    p.nst = (a.c0 + a.c1) / SBSC;
-    p.nbw = sep_bf16_nbw(a, device_cus());
-    return is(SCFLOW_PLAN_SEP_BF16, wino_blocks(a), round_up(a.cout, 64 * p.nbw) / (64 * p.nbw));
-  }
-  if (a.bk == SCFLOW_CONV_BF16_3X3) {  // bf16 direct 3×3 (opt-in: never scflow_conv_pick_bk's choice)
-    if (!c3_bf16_launchable(a)) return fail(SCFLOW_EUNSUPPORTED);
-    if (!src_aligned || !aligned16(a.weight)) return fail(SCFLOW_EALIGN);
-    p.cp0 = a.c0;
-    p.nst = (a.c0 + a.c1) / SBSC;
-    return is(SCFLOW_PLAN_C3_BF16, c3_bf16_blocks(a), round_up(a.cout, 64) / 64);
-  }
-  if (a.bk == SCFLOW_CONV_BF16_3X3N) {  // its encoder form (opt-in alike)
-    if (const int st = c3n_bf16_status(a)) return fail(st);
+  if (const Bf16Format* f = bf16_format(a.bk)) {  // the bf16 direct formats
+    if (const int st = bf16_status(*f, a)) return fail(st);
     // (the affines are read as float4s, the residual one float per lane: its stride is held to
-    // the sources' rule all the same, so that a buffer serves as source and residual alike)
+    // the sources' rule all the same, so that a buffer serves as source and residual alike; only
+    // SCFLOW_CONV_BF16_3X3N gets here with either)
     if (!src_aligned || !aligned16(a.weight) || (a.res && (a.sres & 3)) ||
         (a.in_scale && (!aligned16(a.in_scale) || !aligned16(a.in_shift))))
       return fail(SCFLOW_EALIGN);
     p.cp0 = a.c0;
     p.nst = (a.c0 + a.c1) / SBSC;
-    return is(SCFLOW_PLAN_C3_BF16N, c3_bf16_blocks(a), round_up(a.cout, 64) / 64);
+    if (f->taps == 9) return is(f->plan, bf16_blocks(*f, a), round_up(a.cout, 64) / 64);
+    p.nbw = sep_bf16_nbw(a, device_cus());
+    return is(f->plan, bf16_blocks(*f, a), round_up(a.cout, 64 * p.nbw) / (64 * p.nbw));
   }
   if (a.bk == SCFLOW_CONV_1X1W) {
     if (!conv1x1w_launchable(a)) return fail(SCFLOW_EUNSUPPORTED);

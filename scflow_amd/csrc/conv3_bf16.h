@@ -2,7 +2,7 @@
 // (corr_net.1, flow_net.1, out_net) — the opt-in SCFLOW_CONV_BF16_3X3 format — and, with the fused
 // normalisation pieces (NORM, below), for the RAFT encoders' stride-1 3×3 convs — the opt-in
 // SCFLOW_CONV_BF16_3X3N format; included by conv.hip (inside its anonymous namespace) after
-// conv_sep_bf16.h, whose rounding helpers it shares.
+// conv_bf16_core.h, which holds the halo stager, the packed-weight layout and the rounding.
 // Reference: MotionEncoder, models/decoder/raft_decoder.py:75-85 (channel tables), :152-166.
 //
 // Every buffer stays fp32.  The inputs are rounded to bf16 (round to nearest even) as the halo is
@@ -42,9 +42,9 @@
 
 constexpr int C3OR = 4, C3OC = 32;           // output rows × columns per workgroup
 constexpr int C3HR = C3OR + 2, C3HC = C3OC + 2;  // halo
-constexpr int C3NH = C3HR * C3HC * 4;        // 8-channel slots of one stage's halo (816)
-constexpr int C3NA = (C3NH + 255) / 256;     // slots per thread (4; the last for 48 threads)
-constexpr int C3BUF = C3HR * C3HC * SBPITCH;  // 16-B slots of one LDS halo buffer
+using C3Halo = Bf16Halo<C3HR, C3HC>;  // 816 slots of 8 channels: 4 per thread, the last for 48 threads
+constexpr int C3NA = C3Halo::NA;
+constexpr int C3BUF = C3Halo::BUF;  // 16-B slots of one LDS halo buffer
 
 struct C3Bf16Params {
   scflow_conv_args a;
@@ -52,7 +52,7 @@ struct C3Bf16Params {
   int nbt;        // 32-channel blocks of the packed weights (⌈cout / 32⌉)
 };
 
-constexpr size_t c3_bf16_lds_bytes() { return (size_t)2 * C3BUF * 16; }
+constexpr size_t c3_bf16_lds_bytes() { return C3Halo::LDS_BYTES; }
 
 // (4 waves per SIMD: the grids and times of DESIGN.md §25 rest on four workgroups per CU, so a
 // build that needs more than 128 VGPRs must say so instead of halving the occupancy)
@@ -72,35 +72,12 @@ __global__ __launch_bounds__(256, 4) void conv3_bf16_kernel(C3Bf16Params P) {
   const int oy0 = (rem / XB) * C3OR, ox0 = (rem % XB) * C3OC;
   const int npix = a.n * a.h * W;
 
-  // halo staging: slot idx = tid + 256·j is (pixel idx >> 2, channels 8·(idx & 3) .. + 7)
+  // halo staging (Bf16Halo): the next stage's loads into ra
   int hpix[C3NA];
-#pragma unroll
-  for (int j = 0; j < C3NA; ++j) {
-    const int idx = tid + 256 * j;
-    const int pix = idx >> 2;
-    const int hr = pix / C3HC, hcol = pix - hr * C3HC;
-    const int iy = oy0 - 1 + hr, ix = ox0 - 1 + hcol;
-    const bool ok = idx < C3NH && iy >= 0 && iy < a.h && ix >= 0 && ix < W;
-    hpix[j] = ok ? (img * a.h + iy) * W + ix : -1;
-  }
+  C3Halo::pixels(hpix, tid, img, a.h, W, oy0 - 1, ox0 - 1);
   const int hq = tid & 3;
   floatx4 ra[C3NA][2];
-  auto hload = [&](int s) {
-    const bool s1 = s >= P.nst0;
-    const float* src = s1 ? a.src1 : a.src0;
-    const int cs = s1 ? a.c1 : a.c0;
-    const int ss = s1 ? a.s1 : a.s0;
-    const int cc = (s1 ? s - P.nst0 : s) * SBSC;
-    const __amdgpu_buffer_rsrc_t hsrc =
-        wino_rsrc(src + cc, (unsigned)(((long long)(npix - 1) * ss + cs - cc) * 4));
-#pragma unroll
-    for (int j = 0; j < C3NA; ++j) {
-      const int p = hpix[j];
-      const int off = p >= 0 ? p * ss * 4 + hq * 32 : WINO_OOB;
-      ra[j][0] = wino_bload(hsrc, off, 0);
-      ra[j][1] = wino_bload(hsrc, p >= 0 ? off + 16 : WINO_OOB, 0);
-    }
-  };
+  auto hload = [&](int s) { C3Halo::load(ra, hpix, tid, a, P.nst0, npix, s); };
   // stage s's halo from the staging registers into LDS buffer buf
   auto hstore = [&](int buf, int s) {
     if constexpr (NORM) {
@@ -119,19 +96,13 @@ __global__ __launch_bounds__(256, 4) void conv3_bf16_kernel(C3Bf16Params P) {
         }
       }
     }
-#pragma unroll
-    for (int j = 0; j < C3NA; ++j) {
-      const int idx = tid + 256 * j;
-      if (C3NH % 256 == 0 || idx < C3NH)
-        smem4[buf * C3BUF + (idx >> 2) * SBPITCH + hq] = sep_bf16_round8(ra[j][0], ra[j][1]);
-    }
+    C3Halo::store(smem4 + buf * C3BUF, ra, tid);
   };
 
-  // weights [nb32][k-step][tap][lane][8 bf16]: lane li + 32·hh holds output channel 32·nb32 + li,
-  // input channels 16·k-step + 8·hh + 0..7.  With an odd ⌈cout / 32⌉ the last workgroup's second
-  // wave pair has no block of its own: it reads the last packed block again (the block offset is
-  // the load's scalar offset, which the buffer's range check does not cover, so it must stay
-  // inside the packed weights) and every one of its stores is masked.
+  // weights [nb32][k-step][tap][lane][8 bf16] (bf16_wblock).  With an odd ⌈cout / 32⌉ the last
+  // workgroup's second wave pair has no block of its own: it reads the last packed block again
+  // (the block offset is the load's scalar offset, which the buffer's range check does not cover,
+  // so it must stay inside the packed weights) and every one of its stores is masked.
   const int nks = P.nst * (SBSC / SBKC);
   const __amdgpu_buffer_rsrc_t wsrc = wino_rsrc(a.weight, (unsigned)((size_t)P.nbt * nks * 9 * 1024));
   const int nb = by * 2 + wn;                     // this wave's 32-channel output block
@@ -140,7 +111,7 @@ __global__ __launch_bounds__(256, 4) void conv3_bf16_kernel(C3Bf16Params P) {
   auto uload = [&](floatx4(&u)[3], int g) {
     const int gg = g < ngr ? g : ngr - 1;  // (the last stages re-load the last group)
 #pragma unroll
-    for (int tx = 0; tx < 3; ++tx) u[tx] = wino_bload(wsrc, lane * 16, ((nbl * ngr + gg) * 3 + tx) * 1024);
+    for (int tx = 0; tx < 3; ++tx) u[tx] = wino_bload(wsrc, lane * 16, bf16_wblock<3>(nbl, ngr, gg, tx));
   };
 
   // this lane's two A rows (output pixels (2·wm + rb, li) of the block) as halo slot offsets of
@@ -197,8 +168,8 @@ __global__ __launch_bounds__(256, 4) void conv3_bf16_kernel(C3Bf16Params P) {
     __syncthreads();
   }
 
-  // epilogue; C/D layout: col = lane&31, row = (r&3) + 8(r>>2) + 4(lane>>5) — the direct conv's
-  // (conv_mfma_kernel), with its arithmetic.  A lane writes its own channel only: nothing at or
+  // epilogue; C/D layout: col = lane&31, row = mfma32_row — the direct conv's (conv_mfma_kernel),
+  // with its arithmetic.  A lane writes its own channel only: nothing at or
   // past cout of the destination's pixel stride is touched.
   const int col = nb * 32 + li;
   if (col >= a.cout) return;
@@ -215,12 +186,12 @@ __global__ __launch_bounds__(256, 4) void conv3_bf16_kernel(C3Bf16Params P) {
       float rv[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int x = (r & 3) + 8 * (r >> 2) + 4 * hh;
+        const int x = mfma32_row(r, hh);
         rv[r] = a.res ? a.res[(row0 + x) * a.sres + col] : 0.f;
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int x = (r & 3) + 8 * (r >> 2) + 4 * hh;
+        const int x = mfma32_row(r, hh);
         float v = acc[rb][r] + bias;
         if (aff) v = v * osc + osh;
         if (a.res) v += rv[r];
@@ -234,32 +205,8 @@ __global__ __launch_bounds__(256, 4) void conv3_bf16_kernel(C3Bf16Params P) {
     const size_t row0 = (size_t)(img * a.h + oy0 + wm * 2 + rb) * W + ox0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int x = (r & 3) + 8 * (r >> 2) + 4 * hh;
+      const int x = mfma32_row(r, hh);
       a.out[(row0 + x) * a.so + col] = act_apply(acc[rb][r] + bias, a.act);
     }
-  }
-}
-
-// OIHW fp32 → [nb32][k-step][tap][lane][8 bf16], two bf16 per packed float (element 2i in the
-// low half): lane = li + 32·hh ↔ output channel 32·nb32 + li, input channel 16·k-step + 8·hh + j;
-// tap = 3·ky + kx.  Source 1's channels follow source 0's directly (both are multiples of 32);
-// output channels past cout in the last 32-channel block are 0.
-__global__ void c3_bf16_pack_kernel(const float* __restrict__ w, float* __restrict__ out, int cout,
-                                    int cin, int nks, long long total) {
-  for (long long idx = blockIdx.x * 256LL + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
-    long long r = idx;
-    const int e2 = (int)(r & 3); r >>= 2;
-    const int lane = (int)(r & 63); r >>= 6;
-    const int tap = (int)(r % 9); r /= 9;
-    const int ks = (int)(r % nks);
-    const int nb = (int)(r / nks);
-    const int o = nb * 32 + (lane & 31);
-    const int ci = ks * SBKC + 8 * (lane >> 5) + 2 * e2;
-    unsigned bits = 0;
-    if (o < cout) {
-      const float* g = w + ((size_t)o * cin + ci) * 9 + tap;
-      bits = sep_bf16_bits(g[0]) | (sep_bf16_bits(g[9]) << 16);
-    }
-    out[idx] = __builtin_bit_cast(float, bits);
   }
 }

@@ -1,5 +1,6 @@
 // Direct 1×5 / 5×1 convolution on bf16 MFMA with fp32 accumulation for the SeqConv GRU — the
-// opt-in SCFLOW_CONV_BF16 format; included by conv.hip (inside its anonymous namespace).
+// opt-in SCFLOW_CONV_BF16 format; included by conv.hip (inside its anonymous namespace) after
+// conv_bf16_core.h, which holds the halo stager, the packed-weight layout and the rounding.
 // Reference: ConvGRU SeqConv, models/decoder/raft_decoder.py:180-181 (kernel table), :235-253.
 //
 // Every buffer stays fp32.  The inputs are rounded to bf16 (round to nearest even) as the halo is
@@ -23,13 +24,6 @@
 // channels, 16-channel k-step, tap), streamed from L2 one k-step (5 taps) ahead of their MFMAs.
 // No atomics, a fixed summation order: bitwise reproducible.
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float floatx8 __attribute__((ext_vector_type(8)));
-
-constexpr int SBSC = 32;    // input channels per stage
-constexpr int SBKC = 16;    // input channels per MFMA k-step
-constexpr int SBPITCH = 5;  // 16-B slots per halo pixel: 4 of channels + 1 pad
-
 struct SepBf16Params {
   scflow_conv_args a;
   int nst0, nst;               // stages (32 channels) of source 0, of both sources
@@ -37,22 +31,17 @@ struct SepBf16Params {
 };
 
 template <int DIR, int W>
+using SepBf16Halo = Bf16Halo<Wino5Geom<DIR, W>::HR, Wino5Geom<DIR, W>::HC>;
+template <int DIR, int W>
 constexpr size_t sep_bf16_lds_bytes() {
-  return (size_t)2 * Wino5Geom<DIR, W>::HR * Wino5Geom<DIR, W>::HC * SBPITCH * 16;
-}
-
-// 8 fp32 → 8 bf16, round to nearest even (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ floatx4 sep_bf16_round8(floatx4 lo, floatx4 hi) {
-  const floatx8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(floatx4, __builtin_convertvector(v, bf16x8));
+  return SepBf16Halo<DIR, W>::LDS_BYTES;
 }
 
 template <int DIR, int W, int NBW, int EPI>  // DIR 0: 1×5 (along x), 1: 5×1 (along y)
 __global__ __launch_bounds__(256, 2) void conv_sep_bf16_kernel(SepBf16Params P) {
   using G = Wino5Geom<DIR, W>;
-  constexpr int NH = G::HR * G::HC * 4;  // 8-channel slots of one stage's halo
-  constexpr int NA = (NH + 255) / 256;   // slots per thread
-  extern __shared__ floatx4 smem4[];     // 2 × [HR·HC pixels][SBPITCH] 16-B slots
+  using H = SepBf16Halo<DIR, W>;
+  extern __shared__ floatx4 smem4[];  // 2 × [HR·HC pixels][SBPITCH] 16-B slots
   const scflow_conv_args& a = P.a;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -67,46 +56,14 @@ __global__ __launch_bounds__(256, 2) void conv_sep_bf16_kernel(SepBf16Params P) 
   const int npix = a.n * a.h * W;
   const int hy0 = DIR == 0 ? oy0 : oy0 - 2, hx0 = DIR == 0 ? -2 : ox0;  // halo origin
 
-  // halo staging: slot idx = tid + 256·j is (pixel idx >> 2, channels 8·(idx & 3) .. + 7)
-  int hpix[NA];
-#pragma unroll
-  for (int j = 0; j < NA; ++j) {
-    const int idx = tid + 256 * j;
-    const int pix = idx >> 2;
-    const int hr = pix / G::HC, hcol = pix - hr * G::HC;
-    const int iy = hy0 + hr, ix = hx0 + hcol;
-    const bool ok = idx < NH && iy >= 0 && iy < a.h && ix >= 0 && ix < W;
-    hpix[j] = ok ? (img * a.h + iy) * W + ix : -1;
-  }
-  const int hq = tid & 3;
-  floatx4 ra[NA][2];
-  auto hload = [&](int s) {
-    const bool s1 = s >= P.nst0;
-    const float* src = s1 ? a.src1 : a.src0;
-    const int cs = s1 ? a.c1 : a.c0;
-    const int ss = s1 ? a.s1 : a.s0;
-    const int cc = (s1 ? s - P.nst0 : s) * SBSC;
-    const __amdgpu_buffer_rsrc_t hsrc =
-        wino_rsrc(src + cc, (unsigned)(((long long)(npix - 1) * ss + cs - cc) * 4));
-#pragma unroll
-    for (int j = 0; j < NA; ++j) {
-      const int p = hpix[j];
-      const int off = p >= 0 ? p * ss * 4 + hq * 32 : WINO_OOB;
-      ra[j][0] = wino_bload(hsrc, off, 0);
-      ra[j][1] = wino_bload(hsrc, p >= 0 ? off + 16 : WINO_OOB, 0);
-    }
-  };
-  auto hstore = [&](int buf) {
-#pragma unroll
-    for (int j = 0; j < NA; ++j) {
-      const int idx = tid + 256 * j;
-      if (NH % 256 == 0 || idx < NH)
-        smem4[buf * (NH / 4 * SBPITCH) + (idx >> 2) * SBPITCH + hq] = sep_bf16_round8(ra[j][0], ra[j][1]);
-    }
-  };
+  // halo staging (Bf16Halo): the next stage's loads into ra, ra rounded into LDS buffer buf
+  int hpix[H::NA];
+  H::pixels(hpix, tid, img, a.h, W, hy0, hx0);
+  floatx4 ra[H::NA][2];
+  auto hload = [&](int s) { H::load(ra, hpix, tid, a, P.nst0, npix, s); };
+  auto hstore = [&](int buf) { H::store(smem4 + buf * H::BUF, ra, tid); };
 
-  // weights [nb32][k-step][tap][lane][8 bf16]: lane li + 32·hh holds output channel 32·nb32 + li,
-  // input channels 16·k-step + 8·hh + 0..7
+  // weights [nb32][k-step][tap][lane][8 bf16] (bf16_wblock)
   const int nks = P.nst * (SBSC / SBKC);
   const int nbt = (int)gridDim.y * 2 * NBW;  // 32-channel blocks packed
   const __amdgpu_buffer_rsrc_t wsrc = wino_rsrc(a.weight, (unsigned)((size_t)nbt * nks * 5 * 1024));
@@ -117,7 +74,7 @@ __global__ __launch_bounds__(256, 2) void conv_sep_bf16_kernel(SepBf16Params P) 
     for (int t = 0; t < 5; ++t)
 #pragma unroll
       for (int nb = 0; nb < NBW; ++nb)
-        u[t][nb] = wino_bload(wsrc, lane * 16, (((nb0 + nb) * nks + kk) * 5 + t) * 1024);
+        u[t][nb] = wino_bload(wsrc, lane * 16, bf16_wblock<5>(nb0 + nb, nks, kk, t));
   };
 
   // this lane's two A rows (output pixels) as halo slot offsets (tap 0), + its channel half
@@ -139,7 +96,7 @@ __global__ __launch_bounds__(256, 2) void conv_sep_bf16_kernel(SepBf16Params P) 
 
   // the 5 taps of k-step k (0, 1) of the stage in LDS buffer buf
   auto kstep = [&](int buf, int k, const floatx4(&u)[5][NBW]) {
-    const floatx4* hb = smem4 + buf * (NH / 4 * SBPITCH) + 2 * k;
+    const floatx4* hb = smem4 + buf * H::BUF + 2 * k;
 #pragma unroll
     for (int t = 0; t < 5; ++t) {
       bf16x8 av[2];
@@ -174,8 +131,8 @@ __global__ __launch_bounds__(256, 2) void conv_sep_bf16_kernel(SepBf16Params P) 
   }
   wino_stamp(P.stamps, 2);
 
-  // epilogue; C/D layout: col = lane&31, row = (r&3) + 8(r>>2) + 4(lane>>5) — the direct conv's
-  // (conv_mfma_kernel), with its arithmetic.  Per 32×32 block, all global reads (bias map, h, z)
+  // epilogue; C/D layout: col = lane&31, row = mfma32_row — the direct conv's (conv_mfma_kernel),
+  // with its arithmetic.  Per 32×32 block, all global reads (bias map, h, z)
   // before any store.
 #pragma unroll
   for (int nb = 0; nb < NBW; ++nb) {
@@ -187,7 +144,7 @@ __global__ __launch_bounds__(256, 2) void conv_sep_bf16_kernel(SepBf16Params P) 
       size_t pixv[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int m = wm * 64 + rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+        const int m = wm * 64 + rb * 32 + mfma32_row(r, hh);
         pixv[r] = (size_t)((img * a.h + oy0 + m / G::OCOLS) * W + ox0 + m % G::OCOLS);
       }
       float v[16];
@@ -231,34 +188,5 @@ __global__ __launch_bounds__(256, 2) void conv_sep_bf16_kernel(SepBf16Params P) 
   if (P.stamps) {
     __builtin_amdgcn_s_waitcnt(0);
     wino_stamp(P.stamps, 3);
-  }
-}
-
-// fp32 bits → bf16 bits, round to nearest even (finite weights)
-__device__ __forceinline__ unsigned sep_bf16_bits(float f) {
-  const unsigned u = __builtin_bit_cast(unsigned, f);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-
-// OIHW fp32 → [nb32][k-step][tap][lane][8 bf16], two bf16 per packed float (element 2i in the
-// low half): lane = li + 32·hh ↔ output channel 32·nb32 + li, input channel 16·k-step + 8·hh + j.
-// Source 1's channels follow source 0's directly (both are multiples of 32).
-__global__ void sep_bf16_pack_kernel(const float* __restrict__ w, float* __restrict__ out, int cout,
-                                     int cin, int nks, long long total) {
-  for (long long idx = blockIdx.x * 256LL + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
-    long long r = idx;
-    const int e2 = (int)(r & 3); r >>= 2;
-    const int lane = (int)(r & 63); r >>= 6;
-    const int tap = (int)(r % 5); r /= 5;
-    const int ks = (int)(r % nks);
-    const int nb = (int)(r / nks);
-    const int o = nb * 32 + (lane & 31);
-    const int ci = ks * SBKC + 8 * (lane >> 5) + 2 * e2;
-    unsigned bits = 0;
-    if (o < cout) {
-      const float* g = w + ((size_t)o * cin + ci) * 5 + tap;
-      bits = sep_bf16_bits(g[0]) | (sep_bf16_bits(g[5]) << 16);
-    }
-    out[idx] = __builtin_bit_cast(float, bits);
   }
 }

@@ -238,10 +238,9 @@ class ConvRunner:
             return 2.0 * pts * (m / tile) * kpad * npad
         if getattr(self, "_bk", None) == _lib.CONV_1X1W:  # K padded to 8, N to 64
             return 2.0 * m * ru(self.cout, 64) * ru(c0, 8)
-        if getattr(self, "_bk", None) == _lib.CONV_BF16:  # direct, K in 32-channel stages, N to 64
+        if getattr(self, "_bk", None) in (_lib.CONV_BF16, _lib.CONV_BF16_3X3):
+            # the bf16 direct convs: K in 32-channel stages, N to a workgroup's 64 channels
             return 2.0 * m * ru(self.cout, 64) * self.kh * self.kw * kpad
-        if getattr(self, "_bk", None) == _lib.CONV_BF16_3X3:  # the same for the bf16 direct 3×3
-            return 2.0 * m * ru(self.cout, 64) * 9 * kpad
         return 2.0 * m * npad * self.kh * self.kw * (ru(c0, 16) + ru(c1, 16))
 
 

@@ -103,6 +103,18 @@ def test_outside_the_domain_is_unsupported():
     assert _lib.load().scflow_conv_workspace_bytes(ctypes.byref(a)) == 0
 
 
+def test_source_1s_stride_counts_only_when_it_has_channels():
+    """With c1 == 0 every stage is source 0's and the kernel never reads source 1: whatever s1
+    holds — unaligned, or large enough to push the offset bound past the buffer-load range — the
+    launch plans, as it does for the 3×3 formats."""
+    for s1 in (0, 3, 1 << 30):
+        for k in ((1, 5), (5, 1)):
+            assert kind(conv(2, 32, 32, 256, 0, 128, k, s1=s1)) == (OK, _lib.PLAN_SEP_BF16)
+    # with channels it counts as before
+    assert kind(conv(2, 32, 32, 128, 128, 128, (1, 5), s1=1 << 30)) == (EUNSUPPORTED, _lib.PLAN_NONE)
+    assert kind(conv(2, 32, 32, 128, 128, 128, (1, 5), s1=64)) == (EUNSUPPORTED, _lib.PLAN_NONE)
+
+
 def test_a_pair_with_a_bf16_half_is_two_launches():
     a = conv(2, 32, 32, 128, 128, 256, (1, 5), **EPI["zr"])
     for b in (conv(2, 32, 32, 128, 128, 128, (1, 5)),                     # bf16 beside bf16

@@ -2,7 +2,7 @@
 widths 32 / 64 / 128, the encoder's direct MFMA conv at 256) against the bf16 direct conv
 (``_lib.CONV_BF16_3X3N``), and the whole ``extract_feat`` / ``get_pose`` with ``enc_bf16`` off / on.
 
-Per launch (tools/menc_launch_times.py's method): per stage (res_layer1 / 2 / 3) and form — "IN":
+Per launch (tools/bf16_launch_times.py's method; its ``--family enc`` runs this part): per stage (res_layer1 / 2 / 3) and form — "IN":
 the producer's InstanceNorm + ReLU fused on load, the shared feature encoder's conv2; "BN": the
 eval-BatchNorm affine + residual + ReLU epilogue, the context encoder's conv2 — each variant's
 launch is bound once and issued ``--launches`` times back to back between two device events, the
