@@ -12,6 +12,9 @@ import os
 
 import torch  # noqa: F401  (must be imported before the HIP library is loaded)
 
+# the generation that weight-derived forms are keyed by lives with their rule (derived.py)
+from .derived import bump_weights_generation, weights_generation  # noqa: F401
+
 LIB_PATH = os.environ.get("SCFLOW_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)),
                                                        "lib", "libscflow_hip.so")
 
@@ -370,21 +373,6 @@ SIGNATURES = {
 }
 
 _lib = None
-
-# Weight-derived caches (packed / flipped / affine forms) are keyed by (data_ptr, _version) of
-# the weights AND by this generation: an update that does not move the version counters — a
-# replayed hipGraph of the optimizer step (TrainStep(graph=True)) writes the parameters without
-# autograd seeing it — bumps the generation so every cache re-derives its forms.
-_WEIGHTS_GEN = 0
-
-
-def weights_generation() -> int:
-    return _WEIGHTS_GEN
-
-
-def bump_weights_generation() -> None:
-    global _WEIGHTS_GEN
-    _WEIGHTS_GEN += 1
 
 
 class ScflowError(RuntimeError):

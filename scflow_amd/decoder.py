@@ -36,6 +36,7 @@ import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import ScflowError
+from .derived import derived
 from .modules import ConvModule, ConvRunner, XHead, run_chain, run_chain_pair
 from .ops import Chan
 from .recurrent import RecurrentCore, _RecurrentDecoder
@@ -223,15 +224,12 @@ class SCFlowDecoder(_RecurrentDecoder):
         hargs = head_runner.args(hid, Chan.whole(HEAD), N, h, w)
         if hargs.bk != _lib.CONV_WINO4:
             return None
-        key = (fp.weight.data_ptr(), fp.weight._version, mp.weight.data_ptr(), mp.weight._version,
-               _lib.weights_generation())
-        if getattr(self, "_xpred_key", None) != key:
-            self._xpred_w = ops.xhead_pred_pack(fp.weight, mp.weight)
-            self._xpred_key = key
+        pw = derived(self, "xhead_pred", (fp.weight, mp.weight),
+                     lambda: ops.xhead_pred_pack(fp.weight, mp.weight))
         ws = ops.xhead_pred_workspace(N, h, w, fh, fh + mh, dev)
         fb = None if fp.bias is None else fp.bias.detach()
         mb = None if mp.bias is None else mp.bias.detach()
-        return hargs, self._xpred_w, ws, fb, mb, fh
+        return hargs, pw, ws, fb, mb, fh
 
     def _sync_events(self, dev, slot=0):
         """The fork / join events of a side stream (created once per device and slot, on it)."""

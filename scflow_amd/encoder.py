@@ -33,6 +33,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
+from .derived import derived
 from .registry import MODELS
 
 Tensor = torch.Tensor
@@ -104,29 +105,29 @@ class ResLayer(nn.Sequential):
         super().__init__(*layers)
 
 
+def _bn_tensors(bn: nn.BatchNorm2d) -> Tuple[Optional[Tensor], ...]:
+    """What the eval affine is derived from (running statistics included: the training
+    BatchNorm marks them as written, derived.py)."""
+    return bn.weight, bn.bias, bn.running_mean, bn.running_var
+
+
 def _bn_affine(bn: nn.BatchNorm2d) -> Tuple[Tensor, Tensor]:
-    """Eval BatchNorm as y = x·scale + shift (per channel), cached per parameter version."""
-    key = tuple((t.data_ptr(), t._version) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)
-                if t is not None) + (_lib.weights_generation(),)
-    if getattr(bn, "_scflow_key", None) != key:
+    """Eval BatchNorm as y = x·scale + shift (per channel), a derived form of ``_bn_tensors``."""
+    def make():
         with torch.no_grad():
             inv = torch.rsqrt(bn.running_var.float() + bn.eps)
             sc = inv * bn.weight.float() if bn.weight is not None else inv
             sh = -bn.running_mean.float() * sc
             if bn.bias is not None:
                 sh = sh + bn.bias.float()
-        bn._scflow_affine = (sc.contiguous(), sh.contiguous())
-        bn._scflow_key = key
-    return bn._scflow_affine
+        return sc.contiguous(), sh.contiguous()
+    return derived(bn, "affine", _bn_tensors(bn), make)
 
 
 def _packed(conv: nn.Conv2d, stem: bool = False) -> Tensor:
     w = conv.weight
-    key = (w.data_ptr(), w._version, stem, _lib.weights_generation())
-    if getattr(conv, "_scflow_enc_key", None) != key:
-        conv._scflow_enc_packed = ops.enc_stem_pack(w) if stem else ops.enc_conv_pack(w)
-        conv._scflow_enc_key = key
-    return conv._scflow_enc_packed
+    return derived(conv, ("enc", stem), (w,),
+                   lambda: ops.enc_stem_pack(w) if stem else ops.enc_conv_pack(w))
 
 
 def _wino_ok(conv: nn.Conv2d, h: int, w: int, cin: int) -> bool:
@@ -137,19 +138,20 @@ def _wino_ok(conv: nn.Conv2d, h: int, w: int, cin: int) -> bool:
             conv.groups == 1 and conv.dilation == (1, 1))
 
 
-def _wino_conv(conv: nn.Conv2d, x: Tensor, out: Tensor, n: int, h: int, w: int, cin: int,
-               in_scale: Optional[Tensor] = None, in_shift: Optional[Tensor] = None,
-               out_scale: Optional[Tensor] = None, out_shift: Optional[Tensor] = None,
-               res: Optional[Tensor] = None, act: Optional[str] = None) -> None:
+def _conv3x3(fmt: int, conv: nn.Conv2d, x: Tensor, out: Tensor, n: int, h: int, w: int, cin: int,
+             in_scale: Optional[Tensor] = None, in_shift: Optional[Tensor] = None,
+             out_scale: Optional[Tensor] = None, out_shift: Optional[Tensor] = None,
+             res: Optional[Tensor] = None, act: Optional[str] = None) -> None:
+    """A stride-1 3×3 conv with the block's normalisation fused, on scflow_conv2d in format ``fmt``:
+    ``_lib.CONV_WINO`` (fp32 F(2×2,3×3)) or ``_lib.CONV_BF16_3X3N`` (the bf16 direct conv: the
+    input is rounded to bf16 after the fused IN + ReLU, the weights when packed; a map outside the
+    kernel's domain raises ScflowError).  The packing is a derived form per format and shape."""
     wt = conv.weight
-    key = (wt.data_ptr(), wt._version, cin, w, _lib.weights_generation())
-    cache = getattr(conv, "_scflow_wino", None)
-    if cache is None or cache[0] != key:
-        cache = (key, ops.pack_conv_weight(wt.detach().float(), cin, 0, w, 1, _lib.CONV_WINO))
-        conv._scflow_wino = cache
+    pk = derived(conv, (fmt, cin, w), (wt,),
+                 lambda: ops.pack_conv_weight(wt.detach().float(), cin, 0, w, 1, fmt))
     cout = conv.out_channels
-    ops.conv2d(ops.Chan.whole(x.view(-1, cin)), cache[1], _bias(conv), n, h, w, cout, 3, 3, 1, 1,
-               act, out=ops.Chan.whole(out.view(-1, cout)), bk=_lib.CONV_WINO, in_scale=in_scale,
+    ops.conv2d(ops.Chan.whole(x.view(-1, cin)), pk, _bias(conv), n, h, w, cout, 3, 3, 1, 1,
+               act, out=ops.Chan.whole(out.view(-1, cout)), bk=fmt, in_scale=in_scale,
                in_shift=in_shift, out_scale=out_scale, out_shift=out_shift,
                res=None if res is None else ops.Chan.whole(res.view(-1, res.shape[-1])))
 
@@ -158,26 +160,6 @@ def _wino_conv(conv: nn.Conv2d, x: Tensor, out: Tensor, n: int, h: int, w: int, 
 # bf16 launch measured faster than the fp32 launch it replaces by more than the run-to-run spread
 # at 256² and at 512² images (tools/enc_bench.py, DESIGN.md §26's wiring table).
 BF16_STAGES: Tuple[str, ...] = ("res_layer1", "res_layer2", "res_layer3")
-
-
-def _bf16_conv(conv: nn.Conv2d, x: Tensor, out: Tensor, n: int, h: int, w: int, cin: int,
-               in_scale: Optional[Tensor] = None, in_shift: Optional[Tensor] = None,
-               out_scale: Optional[Tensor] = None, out_shift: Optional[Tensor] = None,
-               res: Optional[Tensor] = None, act: Optional[str] = None) -> None:
-    """``_wino_conv``'s launch on the bf16 direct 3×3 conv (SCFLOW_CONV_BF16_3X3N): the input is
-    rounded to bf16 after the fused IN + ReLU, the weights when packed (cached next to the Winograd
-    packing, keyed the same way); a map outside the kernel's domain raises ScflowError."""
-    wt = conv.weight
-    key = (wt.data_ptr(), wt._version, cin, w, _lib.weights_generation())
-    cache = getattr(conv, "_scflow_bf16", None)
-    if cache is None or cache[0] != key:
-        cache = (key, ops.pack_conv_weight(wt.detach().float(), cin, 0, w, 1, _lib.CONV_BF16_3X3N))
-        conv._scflow_bf16 = cache
-    cout = conv.out_channels
-    ops.conv2d(ops.Chan.whole(x.view(-1, cin)), cache[1], _bias(conv), n, h, w, cout, 3, 3, 1, 1,
-               act, out=ops.Chan.whole(out.view(-1, cout)), bk=_lib.CONV_BF16_3X3N,
-               in_scale=in_scale, in_shift=in_shift, out_scale=out_scale, out_shift=out_shift,
-               res=None if res is None else ops.Chan.whole(res.view(-1, res.shape[-1])))
 
 
 def _bf16_shaped(conv: nn.Conv2d) -> bool:
@@ -325,11 +307,18 @@ class RAFTEncoder(nn.Module):
         """One BasicBlock.  ``ran`` not None: the block's stage is wired to ``bf16`` — its stride-1
         3×3 convs run on the bf16 direct conv and their names (``tag``.conv1 / .conv2) are
         appended to it."""
-        def bf16(conv: nn.Conv2d, name: str) -> bool:
-            if ran is None or not _bf16_shaped(conv):
-                return False
-            ran.append(f"{tag}.{name}")
-            return True
+        def conv3(conv: nn.Conv2d, name: str, src: Tensor, dst: Tensor, sh: int, sw: int,
+                  sc: int, **fused) -> None:
+            """One of the block's 3×3 convs on the kernel its shape and the knob select: bf16
+            when wired and shaped, else Winograd when ``_wino_ok``, else ``enc_conv``."""
+            if ran is not None and _bf16_shaped(conv):
+                ran.append(f"{tag}.{name}")
+                _conv3x3(_lib.CONV_BF16_3X3N, conv, src, dst, n, sh, sw, sc, **fused)
+            elif _wino_ok(conv, sh, sw, sc):  # (stride 1 only)
+                _conv3x3(_lib.CONV_WINO, conv, src, dst, n, sh, sw, sc, **fused)
+            else:
+                ops.enc_conv(src, _packed(conv), _bias(conv), n, sh, sw, sc, conv.out_channels, 3,
+                             conv.stride[0], 1, dst, **fused)
 
         planes = blk.conv1.out_channels
         st = blk.stride
@@ -340,22 +329,10 @@ class RAFTEncoder(nn.Module):
         ds = blk.downsample
         if IN:
             sc1, sh1, sc2, sh2 = (torch.empty(n, planes, device=dev) for _ in range(4))
-            if bf16(blk.conv1, "conv1"):
-                _bf16_conv(blk.conv1, x, y1, n, h, w, cin)
-            elif st == 1 and _wino_ok(blk.conv1, h, w, cin):
-                _wino_conv(blk.conv1, x, y1, n, h, w, cin)
-            else:
-                ops.enc_conv(x, _packed(blk.conv1), _bias(blk.conv1), n, h, w, cin, planes, 3, st, 1,
-                             y1)
+            conv3(blk.conv1, "conv1", x, y1, h, w, cin)
             ops.enc_instance_norm_stats(y1, n, oh * ow, planes, sc1, sh1, eps=blk.norm1.eps)
             y2 = torch.empty_like(y1)
-            if bf16(blk.conv2, "conv2"):
-                _bf16_conv(blk.conv2, y1, y2, n, oh, ow, planes, in_scale=sc1, in_shift=sh1)
-            elif _wino_ok(blk.conv2, oh, ow, planes):
-                _wino_conv(blk.conv2, y1, y2, n, oh, ow, planes, in_scale=sc1, in_shift=sh1)
-            else:
-                ops.enc_conv(y1, _packed(blk.conv2), _bias(blk.conv2), n, oh, ow, planes, planes, 3,
-                             1, 1, y2, in_scale=sc1, in_shift=sh1)
+            conv3(blk.conv2, "conv2", y1, y2, oh, ow, planes, in_scale=sc1, in_shift=sh1)
             ops.enc_instance_norm_stats(y2, n, oh * ow, planes, sc2, sh2, eps=blk.norm2.eps)
             if ds is not None:
                 d = torch.empty_like(y1)
@@ -367,30 +344,15 @@ class RAFTEncoder(nn.Module):
                 ops.enc_apply(y2, sc2, sh2, out, n, oh * ow, planes, id=x)
         else:
             b1, b2 = _bn_affine(blk.norm1), _bn_affine(blk.norm2)
-            if bf16(blk.conv1, "conv1"):
-                _bf16_conv(blk.conv1, x, y1, n, h, w, cin, out_scale=b1[0], out_shift=b1[1],
-                           act="ReLU")
-            elif st == 1 and _wino_ok(blk.conv1, h, w, cin):
-                _wino_conv(blk.conv1, x, y1, n, h, w, cin, out_scale=b1[0], out_shift=b1[1],
-                           act="ReLU")
-            else:
-                ops.enc_conv(x, _packed(blk.conv1), _bias(blk.conv1), n, h, w, cin, planes, 3, st, 1,
-                             y1, out_scale=b1[0], out_shift=b1[1], act="ReLU")
+            conv3(blk.conv1, "conv1", x, y1, h, w, cin, out_scale=b1[0], out_shift=b1[1], act="ReLU")
             res = x
             if ds is not None:
                 res = torch.empty_like(y1)
                 bd = _bn_affine(ds[1])
                 ops.enc_conv(x, _packed(ds[0]), _bias(ds[0]), n, h, w, cin, planes, 1, st, 0, res,
                              out_scale=bd[0], out_shift=bd[1])
-            if bf16(blk.conv2, "conv2"):
-                _bf16_conv(blk.conv2, y1, out, n, oh, ow, planes, out_scale=b2[0], out_shift=b2[1],
-                           res=res, act="ReLU")
-            elif _wino_ok(blk.conv2, oh, ow, planes):
-                _wino_conv(blk.conv2, y1, out, n, oh, ow, planes, out_scale=b2[0], out_shift=b2[1],
-                           res=res, act="ReLU")
-            else:
-                ops.enc_conv(y1, _packed(blk.conv2), _bias(blk.conv2), n, oh, ow, planes, planes, 3,
-                             1, 1, out, out_scale=b2[0], out_shift=b2[1], res=res, act="ReLU")
+            conv3(blk.conv2, "conv2", y1, out, oh, ow, planes, out_scale=b2[0], out_shift=b2[1],
+                  res=res, act="ReLU")
         return out, oh, ow, planes
 
     def forward(self, x: Tensor, return_middle_result: bool = False) -> Tensor:

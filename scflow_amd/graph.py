@@ -23,13 +23,13 @@ from typing import Any, Callable, Dict
 
 import torch
 
+from .derived import stamp
+
 Tensor = torch.Tensor
 
 
 def _param_versions(module: torch.nn.Module):
-    from ._lib import weights_generation
-    return tuple((p.data_ptr(), p._version) for p in module.state_dict().values()
-                 if isinstance(p, torch.Tensor)) + (weights_generation(),)
+    return stamp(*(p for p in module.state_dict().values() if isinstance(p, torch.Tensor)))
 
 
 class GraphedForward:

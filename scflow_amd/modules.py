@@ -31,6 +31,7 @@ import torch.nn.functional as F
 
 from . import _lib, library, ops
 from ._lib import EPI_GRU_Q, EPI_GRU_ZR, EPI_PLAIN, ScflowError
+from .derived import derived
 from .ops import Chan
 from .registry import MODELS
 
@@ -99,8 +100,8 @@ class ConvModule(nn.Module):
 class ConvRunner:
     """Packs one (or several cout-concatenated) nn.Conv2d weights for scflow_conv2d and runs it.
 
-    The packed copy is cached and re-packed whenever a weight's data pointer or version
-    changes (optimizer step, load_state_dict, .to())."""
+    The packed copies are derived forms (derived.py): one per launch shape, made again whenever
+    a weight's data pointer or version changes (optimizer step, load_state_dict, .to())."""
     force_bk = 0  # 8 / 16 overrides the library's per-launch K-stage depth (tuning only)
     # per-instance packing format (e.g. ``_lib.CONV_BF16``) taken instead of the library's choice;
     # None: ``conv_pick_bk`` decides.  An unsupported shape then raises ScflowError (no fallback).
@@ -122,9 +123,7 @@ class ConvRunner:
         self.with_bias = with_bias
         self.act = act
         self.split = split
-        self._key = None
-        self._packed = None
-        self._bias = None
+        self._bk = self._bk_shape = None  # the last launch's packing format and its shape
 
     def _pick(self, n: int, h: int, w: int, c0: int, c1: int) -> int:
         """The packing format of a launch: the instance's ``fmt`` if set, the class-wide tuning
@@ -135,7 +134,7 @@ class ConvRunner:
         shape = (n, h, w, c0, c1)
         if ConvRunner.force_bk:  # tuning / A-B only
             self._bk_shape, self._bk = shape, ConvRunner.force_bk
-        if getattr(self, "_bk_shape", None) != shape:
+        if self._bk_shape != shape:
             self._bk = ops.conv_pick_bk(n, h, w, c0, c1, self.cout, self.kh, self.kw, self.ph,
                                         self.pw, self.stride)
             self._bk_shape = shape
@@ -150,25 +149,29 @@ class ConvRunner:
         return r
 
     def packed(self, c0: int, c1: int, w: int, bk: int = 16) -> Tuple[Tensor, Optional[Tensor]]:
-        key = (c0, c1, w, bk, _lib.weights_generation()) + tuple((c.weight.data_ptr(), c.weight._version,
-                                   None if c.bias is None else (c.bias.data_ptr(), c.bias._version))
-                                  for c in self.convs)
-        if key != self._key:
+        """(packed weights, bias) of one launch shape: one form per shape for the current weights
+        (derived.py), so a struct recorded for one shape stays valid while another shape runs."""
+        def make():
+            has = [c.bias is not None for c in self.convs]
+            if self.with_bias and any(has) and not all(has):
+                raise ValueError("cannot fuse convs with and without bias")
             wt = torch.cat([c.weight.detach() for c in self.convs], 0) if len(self.convs) > 1 \
                 else self.convs[0].weight.detach()
             if self.in_select is not None:
                 wt = torch.cat([wt[:, a:b] for a, b in self.in_select], 1).contiguous()
-            self._packed = ops.pack_conv_weight(wt.float(), c0, c1, w, self.stride, bk)
-            if not self.with_bias:
-                self._bias = None
-            elif all(c.bias is not None for c in self.convs):
-                self._bias = torch.cat([c.bias.detach().float() for c in self.convs]).contiguous()
-            elif any(c.bias is not None for c in self.convs):
-                raise ValueError("cannot fuse convs with and without bias")
-            else:
-                self._bias = None
-            self._key = key
-        return self._packed, self._bias
+            bias = torch.cat([c.bias.detach().float() for c in self.convs]).contiguous() \
+                if self.with_bias and all(has) else None
+            return ops.pack_conv_weight(wt.float(), c0, c1, w, self.stride, bk), bias
+        return derived(self, (c0, c1, w, bk),
+                       [c.weight for c in self.convs] + [c.bias for c in self.convs], make)
+
+    def _prepare(self, src0: Chan, src1: Optional[Chan], n: int, h: int, w: int):
+        """``run``'s and ``bind``'s prologue: the channel check, the format, the packed form."""
+        c1 = 0 if src1 is None else src1.c
+        if src0.c + c1 != self.cin:
+            raise ValueError(f"conv expects {self.cin} input channels, got {src0.c}+{c1}")
+        self._bk = self._pick(n, h, w, src0.c, c1)
+        return self.packed(src0.c, c1, w, self._bk)
 
     def args(self, src0: Chan, out: Optional[Chan], n: int, h: int, w: int,
              src1: Optional[Chan] = None, epilogue: int = EPI_PLAIN, gate: Optional[Chan] = None,
@@ -185,11 +188,7 @@ class ConvRunner:
         """``run``'s launch with its arguments fixed (weights packed now, buffers persistent):
         calling the result launches it on the current stream.  Re-bind after the weights or
         buffers change."""
-        c1 = 0 if src1 is None else src1.c
-        if src0.c + c1 != self.cin:
-            raise ValueError(f"conv expects {self.cin} input channels, got {src0.c}+{c1}")
-        self._bk = self._pick(n, h, w, src0.c, c1)
-        packed, bias = self.packed(src0.c, c1, w, self._bk)
+        packed, bias = self._prepare(src0, src1, n, h, w)
         args = ops.conv2d_args(src0, packed, bias, n, h, w, self.cout, self.kh, self.kw, self.ph,
                                self.pw, self.act, out=out, src1=src1, epilogue=epilogue, gate=gate,
                                rh=rh, hid=hid, stride=self.stride, bias_map=bias_map, bk=self._bk)
@@ -201,11 +200,7 @@ class ConvRunner:
             src1: Optional[Chan] = None, epilogue: int = EPI_PLAIN, gate: Optional[Chan] = None,
             rh: Optional[Chan] = None, hid: Optional[Chan] = None,
             bias_map: Optional[Chan] = None) -> None:
-        c1 = 0 if src1 is None else src1.c
-        if src0.c + c1 != self.cin:
-            raise ValueError(f"conv expects {self.cin} input channels, got {src0.c}+{c1}")
-        self._bk = self._pick(n, h, w, src0.c, c1)
-        packed, bias = self.packed(src0.c, c1, w, self._bk)
+        packed, bias = self._prepare(src0, src1, n, h, w)
         ops.conv2d(src0, packed, bias, n, h, w, self.cout, self.kh, self.kw, self.ph, self.pw,
                    self.act, out=out, src1=src1, epilogue=epilogue, gate=gate, rh=rh, hid=hid,
                    stride=self.stride, bias_map=bias_map, bk=self._bk)
@@ -217,12 +212,12 @@ class ConvRunner:
     @property
     def winograd(self) -> bool:
         """True once a launch picked the Winograd kernel (F(2×2,3×3) or F(4,5))."""
-        return getattr(self, "_bk", None) in (_lib.CONV_WINO, _lib.CONV_WINO4)
+        return self._bk in (_lib.CONV_WINO, _lib.CONV_WINO4)
 
     @property
     def wino4(self) -> bool:
         """True once a launch picked F(4×4,3×3) (transform launch + point-GEMM launch)."""
-        return getattr(self, "_bk", None) == _lib.CONV_WINO4
+        return self._bk == _lib.CONV_WINO4
 
     def mfma_flops(self, m: int, c0: int, c1: int = 0) -> float:
         """FLOPs the matrix cores execute for one launch over m output pixels with the inputs
@@ -231,14 +226,14 @@ class ConvRunner:
         channels padded to 32; the direct kernel does the algorithmic work on padded channels."""
         ru = lambda v, q: (v + q - 1) // q * q  # noqa: E731
         kpad, npad = ru(c0, 32) + ru(c1, 32), ru(self.cout, 32)
-        if getattr(self, "_bk", None) == _lib.CONV_WINO4:  # 36 points per 4×4 tile, K padded to 8
+        if self._bk == _lib.CONV_WINO4:  # 36 points per 4×4 tile, K padded to 8
             return 2.0 * 36 * (m / 16) * (ru(c0, 8) + ru(c1, 8)) * npad
         if self.winograd:
             pts, tile = (16, 4) if self.kh * self.kw == 9 else (8, 4)
             return 2.0 * pts * (m / tile) * kpad * npad
-        if getattr(self, "_bk", None) == _lib.CONV_1X1W:  # K padded to 8, N to 64
+        if self._bk == _lib.CONV_1X1W:  # K padded to 8, N to 64
             return 2.0 * m * ru(self.cout, 64) * ru(c0, 8)
-        if getattr(self, "_bk", None) in (_lib.CONV_BF16, _lib.CONV_BF16_3X3):
+        if self._bk in (_lib.CONV_BF16, _lib.CONV_BF16_3X3):
             # the bf16 direct convs: K in 32-channel stages, N to a workgroup's 64 channels
             return 2.0 * m * ru(self.cout, 64) * self.kh * self.kw * kpad
         return 2.0 * m * npad * self.kh * self.kw * (ru(c0, 16) + ru(c1, 16))
@@ -708,15 +703,11 @@ class MultiClassPoseHead(nn.Module):
             self.rotation_pred.bias.copy_(torch.tensor(base * self.num_class))
 
     # ------------------------------------------------------------------ HIP path
-    def _packs(self, c_last: int, hw_last: int):
-        w1 = self.fc_layers[0][0].weight
-        key = tuple((m.conv.weight.data_ptr(), m.conv.weight._version) for m in self.conv_layers) + (
-            w1.data_ptr(), w1._version, c_last, hw_last, _lib.weights_generation())
-        if getattr(self, "_pack_key", None) != key:
-            self._packed = [ops.ph_conv_pack(m.conv.weight) for m in self.conv_layers]
-            self._fc1_perm = ops.ph_fc_permute(w1, c_last, hw_last)
-            self._pack_key = key
-        return self._packed, self._fc1_perm
+    def _conv_form(self, i: int, kernel: str):
+        """conv_layers[i]'s weights packed for the kernel the layer runs on (``"enc_conv"``:
+        ``ops.enc_conv_pack``, ``"ph_conv"``: ``ops.ph_conv_pack``), made on first use."""
+        wt = self.conv_layers[i].conv.weight
+        return derived(self, (kernel, i), (wt,), lambda: getattr(ops, kernel + "_pack")(wt))
 
     def _conv_mfma(self, i: int, src0: Chan, src1: Optional[Chan], n: int, h: int, w: int,
                    scale: Optional[Tensor], shift: Optional[Tensor], keep: Optional[list] = None):
@@ -734,21 +725,15 @@ class MultiClassPoseHead(nn.Module):
         tc = min(ow, tm)
         if tc < 8 or tm % tc or ow % tc or oh % (tm // tc):
             return None
-        wt = conv.weight
-        packs = getattr(self, "_mfma_packs", None)
-        if packs is None:
-            packs = self._mfma_packs = {}
-        key = (wt.data_ptr(), wt._version, _lib.weights_generation())
-        if packs.get(i, (None,))[0] != key:
-            packs[i] = (key, ops.enc_conv_pack(wt))
         tiles = n * (oh // (tm // tc)) * (ow // tc) * ((conv.out_channels + 63) // 64)
         nst = (src0.c + c1) // 16
         ksplit = max(1, min(nst, -(-self.conv_wg_target // tiles)))
         parts = torch.empty(ksplit * n * oh * ow, conv.out_channels, device=src0.buf.device)
         if keep is not None:
             keep.append(parts)
-        ops.enc_conv(src0, packs[i][1], None, n, h, w, src0.c, conv.out_channels, 3, s, 1, parts,
-                     src1=src1, ksplit=ksplit, in_scale=scale, in_shift=shift)
+        ops.enc_conv(src0, self._conv_form(i, "enc_conv"), None, n, h, w, src0.c,
+                     conv.out_channels, 3, s, 1, parts, src1=src1, ksplit=ksplit, in_scale=scale,
+                     in_shift=shift)
         return parts, ksplit
 
     def forward_hip(self, src0: Chan, src1: Optional[Chan], n: int, h: int, w: int,
@@ -782,7 +767,9 @@ class MultiClassPoseHead(nn.Module):
         for m in self.conv_layers:
             k, st, p = m.conv.kernel_size[0], m.conv.stride[0], m.conv.padding[0]
             hl, wl = (hl + 2 * p - k) // st + 1, (wl + 2 * p - k) // st + 1
-        packs, fc1_w = self._packs(self.conv_layers[-1].conv.out_channels, hl * wl)
+        w1, c_last = self.fc_layers[0][0].weight, self.conv_layers[-1].conv.out_channels
+        fc1_w = derived(self, ("fc1", c_last, hl * wl), (w1,),
+                        lambda: ops.ph_fc_permute(w1, c_last, hl * wl))
         cur0, cur1, hh, ww = src0, src1, h, w
         scale = shift = None
         for i, m in enumerate(self.conv_layers):
@@ -799,11 +786,11 @@ class MultiClassPoseHead(nn.Module):
                 nk = k * k * -(-(cur0.c + (0 if cur1 is None else cur1.c)) // 16)
                 ks = max(1, min(nk // 16, -(-self.gather_wg_target // tiles)))
                 parts = empty(ks * n * oh * ow, cout)
-                ops.ph_conv(cur0, cur1, packs[i], None, n, hh, ww, cout, k, s, p, parts, scale, shift,
-                            ksplit=ks)
+                ops.ph_conv(cur0, cur1, self._conv_form(i, "ph_conv"), None, n, hh, ww, cout,
+                            k, s, p, parts, scale, shift, ksplit=ks)
                 split = (parts, ks)
             elif split is None:
-                ops.ph_conv(cur0, cur1, packs[i], None if conv.bias is None else conv.bias.detach(), n,
+                ops.ph_conv(cur0, cur1, self._conv_form(i, "ph_conv"), conv.bias.detach(), n,
                             hh, ww, cout, k, s, p, y, scale, shift)
             scale = empty(n, cout)
             shift = empty(n, cout)

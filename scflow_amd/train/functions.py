@@ -985,6 +985,11 @@ def batch_norm_nhwc(x: Tensor, mod, relu: bool = False, res: Optional[Tensor] = 
     y = _BatchNormNHWC.apply(x, mod.weight, mod.bias, res, mod.running_mean, mod.running_var,
                              float(mod.momentum), float(mod.eps), bool(relu or res is not None),
                              res_grad)
+    # the launch wrote the running statistics through raw pointers: mark them as written, so that
+    # the eval affine derived from them is made again (derived.py's rule for such writers)
+    for stat in (mod.running_mean, mod.running_var):
+        if stat is not None:
+            torch.autograd.graph.increment_version(stat)
     if mod.num_batches_tracked is not None:
         mod.num_batches_tracked.add_(1)
     return y

@@ -59,10 +59,10 @@ def launch_variants(n_in, n_bn, size):
                     calls = []
                     with ops.binding(calls):
                         if label == "bf16":
-                            encoder._bf16_conv(conv, x, y, n, s, s, c, **fused)
+                            encoder._conv3x3(_lib.CONV_BF16_3X3N, conv, x, y, n, s, s, c, **fused)
                             kernel = "conv3_bf16"
                         elif encoder._wino_ok(conv, s, s, c):
-                            encoder._wino_conv(conv, x, y, n, s, s, c, **fused)
+                            encoder._conv3x3(_lib.CONV_WINO, conv, x, y, n, s, s, c, **fused)
                             kernel = "F(2x2,3x3)"
                         else:
                             ops.enc_conv(x, encoder._packed(conv), encoder._bias(conv), n, s, s, c, c, 3,
