@@ -24,8 +24,9 @@
  *   scflow_pose_update_flow  <- the two calls above fused, as used at     scflow_decoder.py:231-244
  *   scflow_flow_downsample   <- 1/8·F.interpolate(flow, 1/8, bilinear, align_corners=True)  scflow_decoder.py:197-198
  *   scflow_flow_upsample     <- 8·F.interpolate(flow+Δflow, ×8) and mask ×8 (same)          scflow_decoder.py:223-228
- *   scflow_pose_step         <- one iteration's tail fused: pose update + pose flow + the ×8
+ *   scflow_pose_step_call    <- one iteration's tail fused: pose update + pose flow + the ×8
  *                               prediction + the next iteration's ↓8 flow   scflow_decoder.py:197-198, 223-244
+ *                               (scflow_pose_step / _part / _heads / _masked: its positional forms)
  *   scflow_convex_upsample   <- RAFT's convex ×8 upsampling of the flow and the occlusion (softmax over
  *                               the 3×3 neighbourhood per sub-pixel)   raft_decoder.py:381-416,
  *                               raft_decoder_mask.py:104-160
@@ -419,7 +420,8 @@ int scflow_flow_add(const float* lr, const float* delta, float* out0, int s0, fl
  * scflow_flow_upsample(lr, delta, mask, flow_up, mask_up, n, h, w, H, W, up_scale) when flow_up
  * != NULL + scflow_flow_downsample(flow, lr_next, s_next, hx_next, s_hx, n, H, W, h, w,
  * down_scale) when lr_next != NULL (the ↓8 flow is computed from the new pose directly, bit-
- * identical to downsampling `flow`).  lr_next must not alias lr. */
+ * identical to downsampling `flow`).  lr_next must not alias lr.  A positional form of
+ * scflow_pose_step_call (below): parts = 3, no heads, no masked tail; drot6 NULL is refused. */
 int scflow_pose_step(const float* drot6, const float* dt, const float* R_src, const float* t_src,
                      const float* K, const float* points, float* R_dst, float* t_dst, float* flow,
                      int n, int H, int W, float weight, int depth_transform, float invalid_num,
@@ -504,7 +506,8 @@ int scflow_ph_heads(const float* x, int m, int k, const float* Wr, const float* 
  *   hx_next).  Each part recomputes the pose update; the part with the lowest block writes
  *   R_dst / t_dst.  The decoder runs bit 1 on its critical path and bit 0 on a side stream.
  *   drot6 == NULL (parts = 1 only): R_src / t_src ARE the updated pose (the bit-1 launch's
- *   R_dst / t_dst) — no update, dt / R_dst / t_dst unused, same outputs. */
+ *   R_dst / t_dst) — no update, dt / R_dst / t_dst unused, same outputs.  A positional form of
+ *   scflow_pose_step_call: no heads, no masked tail. */
 int scflow_pose_step_part(const float* drot6, const float* dt, const float* R_src,
                           const float* t_src, const float* K, const float* points, float* R_dst,
                           float* t_dst, float* flow, int n, int H, int W, float weight,
@@ -519,7 +522,8 @@ int scflow_pose_step_part(const float* drot6, const float* dt, const float* R_sr
  *   the last FC's xsplit K-split partial sums [xsplit][n][k]; rch = 6 (ortho6d) or 4
  *   (quaternion, depth_transform's SCFLOW_POSE_QUAT_XYZW).  drot [n][rch] / dt [n][3] are
  *   OUTPUTS here (the decoder's returned deltas).  Replaces the heads launch + the pose step's
- *   delta reads of the reference's get_pose_ (models/decoder/scflow_decoder.py:230-236). */
+ *   delta reads of the reference's get_pose_ (models/decoder/scflow_decoder.py:230-236).  A
+ *   positional form of scflow_pose_step_call: x is required, no masked tail. */
 int scflow_pose_step_heads(const float* x, int xsplit, const float* xbias, int k, const float* Wr,
                            const float* br, int rch, const float* Wt, const float* bt,
                            const long long* label, int num_class, float* drot, float* dt,
@@ -539,7 +543,8 @@ int scflow_pose_step_heads(const float* x, int xsplit, const float* xbias, int k
  *   lr_next) and hx_next receive lr_next · mask_next — the flow branch's input and the motion
  *   features' flow channels of the next iteration.  mask_next NULL: hx_next and lrm_next receive
  *   lr_next, everything as the unmasked entries bit for bit.  The full-resolution outputs never
- *   depend on mask_next. */
+ *   depend on mask_next.  A positional form of scflow_pose_step_call with every field; drot NULL
+ *   is refused even for parts = 1. */
 int scflow_pose_step_masked(const float* x, int xsplit, const float* xbias, int k, const float* Wr,
                             const float* br, int rch, const float* Wt, const float* bt,
                             const long long* label, int num_class, float* drot, float* dt,
@@ -550,6 +555,33 @@ int scflow_pose_step_masked(const float* x, int xsplit, const float* xbias, int 
                             float* mask_up, float* lr_next, int s_next, float* hx_next, int s_hx,
                             const float* mask_next, float* lrm_next, int s_lrm, int h, int w,
                             float up_scale, float down_scale, int parts, void* stream);
+
+/* scflow_pose_step_call: the pose step behind one argument struct — the one launcher that the four
+ *   positional entries above fill and call.  The fields are scflow_pose_step_masked's parameters
+ *   under the same names and meanings.  A zeroed heads block (x NULL), a zeroed masked block
+ *   (mask_next / lrm_next NULL) and parts = 3 is scflow_pose_step.  It accepts the union of what
+ *   the entries accept: with x NULL what scflow_pose_step_part does (drot NULL with parts = 1 is
+ *   the given-pose form; mask_next / lrm_next as in scflow_pose_step_masked), with x != NULL what
+ *   scflow_pose_step_masked does. */
+typedef struct scflow_pose_step_args {
+  /* the fused heads (x NULL: off; drot / dt are then read, else written) */
+  const float* x; int xsplit; const float* xbias; int k;
+  const float* Wr; const float* br; int rch; const float* Wt; const float* bt;
+  const long long* label; int num_class;
+  /* the pose update and the pose flow */
+  float* drot; float* dt; const float* R_src; const float* t_src; const float* K;
+  const float* points; float* R_dst; float* t_dst; float* flow;
+  int n, H, W; float weight; int depth_transform; float invalid_num;
+  /* the ×8 outputs */
+  const float* lr; const float* delta; const float* mask; float* flow_up; float* mask_up;
+  int h, w; float up_scale, down_scale;
+  /* the next iteration's ↓8 flow */
+  float* lr_next; int s_next; float* hx_next; int s_hx;
+  /* the masked tail */
+  const float* mask_next; float* lrm_next; int s_lrm;
+  int parts;                             /* bit 0: full resolution, bit 1: the ↓8 flow */
+} scflow_pose_step_args;
+int scflow_pose_step_call(const scflow_pose_step_args* args, void* stream);
 
 /* §8(f)-1: RAFTEncoder (Basic) — feature encoder (InstanceNorm) and context encoder (BatchNorm,
  * eval statistics), models/encoder/raft_encoder.py:286-314, BasicBlock models/backbone/resnet.py:

@@ -77,6 +77,24 @@ class ConvArgs(ctypes.Structure):
     ]
 
 
+class PoseStepArgs(ctypes.Structure):
+    """Mirror of ``scflow_pose_step_args`` (include/scflow_hip.h)."""
+    _fields_ = [
+        ("x", c_vp), ("xsplit", c_int), ("xbias", c_vp), ("k", c_int),
+        ("Wr", c_vp), ("br", c_vp), ("rch", c_int), ("Wt", c_vp), ("bt", c_vp),
+        ("label", c_vp), ("num_class", c_int),
+        ("drot", c_vp), ("dt", c_vp), ("R_src", c_vp), ("t_src", c_vp), ("K", c_vp),
+        ("points", c_vp), ("R_dst", c_vp), ("t_dst", c_vp), ("flow", c_vp),
+        ("n", c_int), ("H", c_int), ("W", c_int), ("weight", c_float),
+        ("depth_transform", c_int), ("invalid_num", c_float),
+        ("lr", c_vp), ("delta", c_vp), ("mask", c_vp), ("flow_up", c_vp), ("mask_up", c_vp),
+        ("h", c_int), ("w", c_int), ("up_scale", c_float), ("down_scale", c_float),
+        ("lr_next", c_vp), ("s_next", c_int), ("hx_next", c_vp), ("s_hx", c_int),
+        ("mask_next", c_vp), ("lrm_next", c_vp), ("s_lrm", c_int),
+        ("parts", c_int),
+    ]
+
+
 class EncConvArgs(ctypes.Structure):
     """Mirror of ``scflow_enc_conv_args`` (include/scflow_hip.h)."""
     _fields_ = [
@@ -264,6 +282,7 @@ SIGNATURES = {
                                 [c_int, c_int, c_int, c_float, c_int, c_float] + [c_vp] * 6 +
                                 [c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_float,
                                  c_float, c_int, c_vp]),
+    "scflow_pose_step_call": (c_int, [ctypes.POINTER(PoseStepArgs), c_vp]),
     "scflow_sync_event_create": (c_int, [ctypes.POINTER(c_vp)]),
     "scflow_sync_event_destroy": (c_int, [c_vp]),
     "scflow_sync_event_record": (c_int, [c_vp, c_vp]),

@@ -240,6 +240,39 @@ SCFLOW_API int scflow_flow_upsample(const float* lr, const float* delta, const f
   return scflow_launch_status();
 }
 
+// The pose step's one launcher: the four positional entries below and scflow_pose_step_call fill
+// the public struct and end here.  Accepts scflow_pose_step_part's calls when the heads block is
+// off (x NULL; drot NULL with parts = 1 is the given-pose form), scflow_pose_step_masked's
+// otherwise; what only one entry refuses stays in that entry.
+static int pose_step_launch(const scflow_pose_step_args& p, hipStream_t stream) {
+  if (p.parts < 1 || p.parts > 3 || (!p.drot && (p.x || p.parts != 1))) return SCFLOW_EINVAL;
+  if (p.x && (p.xsplit < 1 || !p.xbias || p.k <= 0 || !p.Wr || !p.br || !p.Wt || !p.bt ||
+              !p.label || p.num_class <= 0 || !p.dt || p.rch != pose_rot_dim(p.depth_transform)))
+    return SCFLOW_EINVAL;
+  if ((p.mask_next || p.lrm_next) && !p.lr_next) return SCFLOW_EINVAL;
+  if (p.lrm_next && (p.s_lrm < 2 || p.lrm_next == p.lr || p.lrm_next == p.lr_next))
+    return SCFLOW_EINVAL;
+  PoseStepArgs a;
+  // (with the heads fused drot / dt are the outputs; the checks want a delta source: unread)
+  const int st = pose_step_args(&a, p, 256);
+  if (st != SCFLOW_OK) return st;
+  if (!(p.parts & 1)) a.bf = 0;
+  if (!(p.parts & 2)) a.bl = 0;
+  if (a.bf + a.bl == 0) return SCFLOW_EINVAL;  // parts = 2 needs lr_next
+  a.mnext = p.mask_next; a.o2 = p.lrm_next; a.s2 = p.s_lrm;
+  if (p.x) {
+    a.hx = p.x; a.hxs = (long long)p.n * p.k; a.hk = p.k; a.hsplit = p.xsplit; a.hxb = p.xbias;
+    a.Wr = p.Wr; a.br = p.br; a.Wt = p.Wt; a.bt = p.bt; a.hlabel = p.label; a.hrch = p.rch;
+    a.hncls = p.num_class; a.drot_out = p.drot; a.dt_out = p.dt;
+  }
+  pose_step_kernel<<<dim3(a.bf + a.bl, p.n), 256, 0, stream>>>(a);
+  return scflow_launch_status();
+}
+
+SCFLOW_API int scflow_pose_step_call(const scflow_pose_step_args* args, void* stream) {
+  return args ? pose_step_launch(*args, (hipStream_t)stream) : SCFLOW_EINVAL;
+}
+
 SCFLOW_API int scflow_pose_step(const float* drot6, const float* dt, const float* R_src,
                                 const float* t_src, const float* K, const float* points,
                                 float* R_dst, float* t_dst, float* flow, int n, int H, int W,
@@ -248,15 +281,11 @@ SCFLOW_API int scflow_pose_step(const float* drot6, const float* dt, const float
                                 float* flow_up, float* mask_up, float* lr_next, int s_next,
                                 float* hx_next, int s_hx, int h, int w, float up_scale,
                                 float down_scale, void* stream) {
-  if (!drot6) return SCFLOW_EINVAL;
-  PoseStepArgs a;
-  const int st = pose_step_args(&a, drot6, dt, R_src, t_src, K, points, R_dst, t_dst, flow, n, H, W,
-                                weight, depth_transform, invalid_num, lr, delta, mask, flow_up,
-                                mask_up, lr_next, s_next, hx_next, s_hx, h, w, up_scale, down_scale,
-                                256);
-  if (st != SCFLOW_OK) return st;
-  pose_step_kernel<<<dim3(a.bf + a.bl, n), 256, 0, (hipStream_t)stream>>>(a);
-  return scflow_launch_status();
+  if (!drot6) return SCFLOW_EINVAL;  // (only _part takes the given-pose form)
+  return scflow_pose_step_part(drot6, dt, R_src, t_src, K, points, R_dst, t_dst, flow, n, H, W,
+                               weight, depth_transform, invalid_num, lr, delta, mask, flow_up,
+                               mask_up, lr_next, s_next, hx_next, s_hx, h, w, up_scale, down_scale,
+                               3, stream);
 }
 
 SCFLOW_API int scflow_pose_step_part(const float* drot6, const float* dt, const float* R_src,
@@ -267,18 +296,17 @@ SCFLOW_API int scflow_pose_step_part(const float* drot6, const float* dt, const 
                                      float* flow_up, float* mask_up, float* lr_next, int s_next,
                                      float* hx_next, int s_hx, int h, int w, float up_scale,
                                      float down_scale, int parts, void* stream) {
-  if (parts < 1 || parts > 3 || (!drot6 && parts != 1)) return SCFLOW_EINVAL;
-  PoseStepArgs a;
-  const int st = pose_step_args(&a, drot6, dt, R_src, t_src, K, points, R_dst, t_dst, flow, n, H, W,
-                                weight, depth_transform, invalid_num, lr, delta, mask, flow_up,
-                                mask_up, lr_next, s_next, hx_next, s_hx, h, w, up_scale, down_scale,
-                                256);
-  if (st != SCFLOW_OK) return st;
-  if (!(parts & 1)) a.bf = 0;
-  if (!(parts & 2)) a.bl = 0;
-  if (a.bf + a.bl == 0) return SCFLOW_EINVAL;  // parts = 2 needs lr_next
-  pose_step_kernel<<<dim3(a.bf + a.bl, n), 256, 0, (hipStream_t)stream>>>(a);
-  return scflow_launch_status();
+  scflow_pose_step_args p{};
+  // (the struct's drot / dt are written only when the heads are fused: p.x stays NULL here)
+  p.drot = const_cast<float*>(drot6); p.dt = const_cast<float*>(dt);
+  p.R_src = R_src; p.t_src = t_src; p.K = K; p.points = points; p.R_dst = R_dst; p.t_dst = t_dst;
+  p.flow = flow; p.n = n; p.H = H; p.W = W; p.weight = weight;
+  p.depth_transform = depth_transform; p.invalid_num = invalid_num;
+  p.lr = lr; p.delta = delta; p.mask = mask; p.flow_up = flow_up; p.mask_up = mask_up;
+  p.h = h; p.w = w; p.up_scale = up_scale; p.down_scale = down_scale;
+  p.lr_next = lr_next; p.s_next = s_next; p.hx_next = hx_next; p.s_hx = s_hx;
+  p.parts = parts;
+  return pose_step_launch(p, (hipStream_t)stream);
 }
 
 SCFLOW_API int scflow_pose_step_heads(const float* x, int xsplit, const float* xbias, int k,
@@ -292,25 +320,12 @@ SCFLOW_API int scflow_pose_step_heads(const float* x, int xsplit, const float* x
                                       float* flow_up, float* mask_up, float* lr_next, int s_next,
                                       float* hx_next, int s_hx, int h, int w, float up_scale,
                                       float down_scale, int parts, void* stream) {
-  if (!x || xsplit < 1 || !xbias || k <= 0 || !Wr || !br || !Wt || !bt || !label ||
-      num_class <= 0 || !drot || !dt || rch != pose_rot_dim(depth_transform) || parts < 1 ||
-      parts > 3)
-    return SCFLOW_EINVAL;
-  PoseStepArgs a;
-  // drot / dt are the outputs here; the argument checks want a delta source: pass them (unread)
-  const int st = pose_step_args(&a, drot, dt, R_src, t_src, K, points, R_dst, t_dst, flow, n, H, W,
-                                weight, depth_transform, invalid_num, lr, delta, mask, flow_up,
-                                mask_up, lr_next, s_next, hx_next, s_hx, h, w, up_scale, down_scale,
-                                256);
-  if (st != SCFLOW_OK) return st;
-  if (!(parts & 1)) a.bf = 0;
-  if (!(parts & 2)) a.bl = 0;
-  if (a.bf + a.bl == 0) return SCFLOW_EINVAL;  // parts = 2 needs lr_next
-  a.hx = x; a.hxs = (long long)n * k; a.hk = k; a.hsplit = xsplit; a.hxb = xbias;
-  a.Wr = Wr; a.br = br; a.Wt = Wt; a.bt = bt; a.hlabel = label; a.hrch = rch; a.hncls = num_class;
-  a.drot_out = drot; a.dt_out = dt;
-  pose_step_kernel<<<dim3(a.bf + a.bl, n), 256, 0, (hipStream_t)stream>>>(a);
-  return scflow_launch_status();
+  if (!x) return SCFLOW_EINVAL;  // (the heads are this entry's point)
+  return scflow_pose_step_masked(x, xsplit, xbias, k, Wr, br, rch, Wt, bt, label, num_class, drot,
+                                 dt, R_src, t_src, K, points, R_dst, t_dst, flow, n, H, W, weight,
+                                 depth_transform, invalid_num, lr, delta, mask, flow_up, mask_up,
+                                 lr_next, s_next, hx_next, s_hx, nullptr, nullptr, 0, h, w,
+                                 up_scale, down_scale, parts, stream);
 }
 
 // The superset of the three entries above with the masked tail: x NULL → scflow_pose_step_part
@@ -330,29 +345,19 @@ SCFLOW_API int scflow_pose_step_masked(const float* x, int xsplit, const float* 
                                        float* hx_next, int s_hx, const float* mask_next,
                                        float* lrm_next, int s_lrm, int h, int w, float up_scale,
                                        float down_scale, int parts, void* stream) {
-  if (parts < 1 || parts > 3 || !drot) return SCFLOW_EINVAL;
-  if (x && (xsplit < 1 || !xbias || k <= 0 || !Wr || !br || !Wt || !bt || !label ||
-            num_class <= 0 || !dt || rch != pose_rot_dim(depth_transform)))
-    return SCFLOW_EINVAL;
-  if ((mask_next || lrm_next) && !lr_next) return SCFLOW_EINVAL;
-  if (lrm_next && (s_lrm < 2 || lrm_next == lr || lrm_next == lr_next)) return SCFLOW_EINVAL;
-  PoseStepArgs a;
-  const int st = pose_step_args(&a, drot, dt, R_src, t_src, K, points, R_dst, t_dst, flow, n, H, W,
-                                weight, depth_transform, invalid_num, lr, delta, mask, flow_up,
-                                mask_up, lr_next, s_next, hx_next, s_hx, h, w, up_scale, down_scale,
-                                256);
-  if (st != SCFLOW_OK) return st;
-  if (!(parts & 1)) a.bf = 0;
-  if (!(parts & 2)) a.bl = 0;
-  if (a.bf + a.bl == 0) return SCFLOW_EINVAL;  // parts = 2 needs lr_next
-  a.mnext = mask_next; a.o2 = lrm_next; a.s2 = s_lrm;
-  if (x) {
-    a.hx = x; a.hxs = (long long)n * k; a.hk = k; a.hsplit = xsplit; a.hxb = xbias;
-    a.Wr = Wr; a.br = br; a.Wt = Wt; a.bt = bt; a.hlabel = label; a.hrch = rch; a.hncls = num_class;
-    a.drot_out = drot; a.dt_out = dt;
-  }
-  pose_step_kernel<<<dim3(a.bf + a.bl, n), 256, 0, (hipStream_t)stream>>>(a);
-  return scflow_launch_status();
+  if (!drot) return SCFLOW_EINVAL;  // (only _part takes the given-pose form)
+  scflow_pose_step_args p{};
+  p.x = x; p.xsplit = xsplit; p.xbias = xbias; p.k = k; p.Wr = Wr; p.br = br; p.rch = rch;
+  p.Wt = Wt; p.bt = bt; p.label = label; p.num_class = num_class;
+  p.drot = drot; p.dt = dt; p.R_src = R_src; p.t_src = t_src; p.K = K; p.points = points;
+  p.R_dst = R_dst; p.t_dst = t_dst; p.flow = flow; p.n = n; p.H = H; p.W = W; p.weight = weight;
+  p.depth_transform = depth_transform; p.invalid_num = invalid_num;
+  p.lr = lr; p.delta = delta; p.mask = mask; p.flow_up = flow_up; p.mask_up = mask_up;
+  p.h = h; p.w = w; p.up_scale = up_scale; p.down_scale = down_scale;
+  p.lr_next = lr_next; p.s_next = s_next; p.hx_next = hx_next; p.s_hx = s_hx;
+  p.mask_next = mask_next; p.lrm_next = lrm_next; p.s_lrm = s_lrm;
+  p.parts = parts;
+  return pose_step_launch(p, (hipStream_t)stream);
 }
 
 SCFLOW_API int scflow_transpose(const float* in, float* out, int n, int A, int B, long long ins,

@@ -409,39 +409,33 @@ static inline int fullres_blocks() {
   return v > 0 ? v : 64;
 }
 
-static inline int pose_step_args(PoseStepArgs* a, const float* drot6, const float* dt,
-                                 const float* R_src, const float* t_src, const float* K,
-                                 const float* points, float* R_dst, float* t_dst, float* flow, int n,
-                                 int H, int W, float weight, int depth_transform, float invalid_num,
-                                 const float* lr, const float* delta, const float* mask,
-                                 float* flow_up, float* mask_up, float* lr_next, int s_next,
-                                 float* hx_next, int s_hx, int h, int w, float up_scale,
-                                 float down_scale, int nt) {
-  const bool given = !drot6;  // the full-resolution part from an updated pose (R_src, t_src)
-  if ((!given && (!dt || !R_dst || !t_dst)) || !R_src || !t_src || !K || !points || !flow ||
-      n <= 0 || H <= 0 || W <= 0 || (depth_transform & ~(SCFLOW_POSE_QUAT_XYZW | 1)) != 0)
+static inline int pose_step_args(PoseStepArgs* a, const scflow_pose_step_args& p, int nt) {
+  const bool given = !p.drot;  // the full-resolution part from an updated pose (R_src, t_src)
+  if ((!given && (!p.dt || !p.R_dst || !p.t_dst)) || !p.R_src || !p.t_src || !p.K || !p.points ||
+      !p.flow || p.n <= 0 || p.H <= 0 || p.W <= 0 || !pose_mode_ok(p.depth_transform))
     return SCFLOW_EINVAL;
-  if (given && lr_next) return SCFLOW_EINVAL;
-  if ((flow_up || lr_next) && (h <= 0 || w <= 0)) return SCFLOW_EINVAL;
-  if (flow_up && !lr) return SCFLOW_EINVAL;
-  if (lr_next && (s_next < 2 || (hx_next && s_hx < 2) || lr_next == lr)) return SCFLOW_EINVAL;
-  if (!aligned16(points)) return SCFLOW_EALIGN;
-  a->drot6 = drot6; a->dtv = dt; a->Rsrc = R_src; a->tsrc = t_src; a->K = K;
-  a->pts = (const floatx4*)points; a->Rout = R_dst; a->tout = t_dst; a->flow = flow;
-  a->H = H; a->W = W; a->weight = weight; a->depth_transform = depth_transform;
-  a->invalid = invalid_num; a->lr = lr; a->delta = delta; a->mask = mask; a->fo = flow_up;
-  a->mo = mask_up; a->o0 = lr_next; a->s0 = s_next; a->o1 = hx_next; a->s1 = s_hx; a->h = h;
-  a->w = w; a->up_scale = up_scale; a->down_scale = down_scale;
+  if (given && p.lr_next) return SCFLOW_EINVAL;
+  if ((p.flow_up || p.lr_next) && (p.h <= 0 || p.w <= 0)) return SCFLOW_EINVAL;
+  if (p.flow_up && !p.lr) return SCFLOW_EINVAL;
+  if (p.lr_next && (p.s_next < 2 || (p.hx_next && p.s_hx < 2) || p.lr_next == p.lr))
+    return SCFLOW_EINVAL;
+  if (!aligned16(p.points)) return SCFLOW_EALIGN;
+  a->drot6 = p.drot; a->dtv = p.dt; a->Rsrc = p.R_src; a->tsrc = p.t_src; a->K = p.K;
+  a->pts = (const floatx4*)p.points; a->Rout = p.R_dst; a->tout = p.t_dst; a->flow = p.flow;
+  a->H = p.H; a->W = p.W; a->weight = p.weight; a->depth_transform = p.depth_transform;
+  a->invalid = p.invalid_num; a->lr = p.lr; a->delta = p.delta; a->mask = p.mask;
+  a->fo = p.flow_up; a->mo = p.mask_up; a->o0 = p.lr_next; a->s0 = p.s_next; a->o1 = p.hx_next;
+  a->s1 = p.s_hx; a->h = p.h; a->w = p.w; a->up_scale = p.up_scale; a->down_scale = p.down_scale;
   a->given = given ? 1 : 0;
   a->hx = nullptr;
   a->mnext = nullptr; a->o2 = nullptr; a->s2 = 0;
-  const int bf = ceil_div((long long)H * W, nt);
+  const int bf = ceil_div((long long)p.H * p.W, nt);
   // from a given pose the part runs beside other work (the decoder's side stream): 4 pixels per
   // thread, a quarter of the workgroups to schedule
   const int bfmax = given ? fullres_blocks() : 256;
   a->bf = bf < bfmax ? bf : bfmax;
-  const int bl = ceil_div((long long)h * w, nt);
-  a->bl = lr_next ? (bl < 64 ? bl : 64) : 0;
+  const int bl = ceil_div((long long)p.h * p.w, nt);
+  a->bl = p.lr_next ? (bl < 64 ? bl : 64) : 0;
   return SCFLOW_OK;
 }
 

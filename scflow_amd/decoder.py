@@ -651,37 +651,37 @@ class _DecoderRun:
         for j in range(iters):
             last = j == iters - 1
             hc, pc, fc = [], [], []
-            step = (out["drot"][j], out["dt"][j], Rp, tp, self.K, self.points, out["R"][j],
-                    out["t"][j], out["flow_pose"][j], self.invalid, _at(F2s, j), _at(D2s, j),
-                    _at(MASKs, j), out["flow_pred"][j], out["mask"][j], self.h, self.w,
-                    float(self.scale))
-            nxt = dict(lr_next=None if last else Chan.whole(_at(F2s, j + 1)),
-                       hx_next=None if last else self.core.hx_flow,
-                       depth_transform=dec.depth_transform)
-            if dec.mask_flow and not last:  # the next iteration's masked ↓8 flow
+            # what every variant of the iteration's launch shares: the full-resolution part
+            full = dict(K=self.K, points=self.points, flow_out=out["flow_pose"][j],
+                        invalid_num=self.invalid, lr=_at(F2s, j), delta=_at(D2s, j),
+                        mask=_at(MASKs, j), flow_up=out["flow_pred"][j], mask_up=out["mask"][j],
+                        h=self.h, w=self.w, up_scale=float(self.scale))
+            # the pose update from this iteration's delta
+            upd = dict(drot=out["drot"][j], dt=out["dt"][j], R=Rp, t=tp, R_out=out["R"][j],
+                       t_out=out["t"][j], depth_transform=dec.depth_transform)
+            # the next iteration's ↓8 flow (under mask_flow: and its masked copy)
+            nxt = {} if last else dict(lr_next=Chan.whole(_at(F2s, j + 1)), hx_next=self.core.hx_flow)
+            if dec.mask_flow and not last:
                 nxt.update(mask_next=_at(MASKs, j), lrm_next=Chan.whole(_at(FLMs, j + 1)))
-            # the rotation / translation heads inside the pose step's launch
-            # (scflow_pose_step_heads), or as their own launch before it
+            # the rotation / translation heads inside the pose step's launch, or as their own
+            # launch before it
             ha = dec.pose_pred.heads_args(self.pose_x, self.label) if dec.fuse_heads else None
             if ha is None:
                 with ops.binding(hc, run=False):
                     dec.pose_pred.heads_hip(self.pose_x, self.label, out["drot"][j], out["dt"][j])
-            else:
-                nxt["heads"] = ha
+            heads = {} if ha is None else dict(heads=ha)
             if self.defer and not last:
-                with ops.binding(pc, run=False):
-                    ops.pose_step(*step, **nxt, parts=2)
-                with ops.binding(fc, run=False):
-                    if dec.fullres_given:
-                        ops.pose_step_given(out["R"][j], out["t"][j], *step[4:6], *step[8:])
-                    else:  # (reads the deltas the ↓8 launch wrote)
-                        fstep = step[:6] + (self.R_scr, self.t_scr) + step[8:]
-                        ops.pose_step(*fstep, parts=1,
-                                      **{k: v for k, v in nxt.items()
-                                         if k not in ("heads", "mask_next", "lrm_next")})
+                with ops.binding(pc, run=False):  # critical: only the ↓8 flow
+                    ops.pose_step(**full, **upd, **nxt, **heads, parts=2)
+                with ops.binding(fc, run=False):  # deferred: only the full-resolution part
+                    if dec.fullres_given:  # from the pose the ↓8 launch wrote
+                        ops.pose_step_given(R=out["R"][j], t=out["t"][j], **full)
+                    else:  # the update again, from the deltas the ↓8 launch wrote
+                        ops.pose_step(**full, **dict(upd, R_out=self.R_scr, t_out=self.t_scr),
+                                      lr_next=nxt["lr_next"], hx_next=nxt["hx_next"], parts=1)
             else:
                 with ops.binding(pc, run=False):
-                    ops.pose_step(*step, **nxt)
+                    ops.pose_step(**full, **upd, **nxt, **heads)
             calls.append((hc, pc, fc))
             Rp, tp = out["R"][j], out["t"][j]
         return calls

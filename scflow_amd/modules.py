@@ -22,7 +22,6 @@ and calls the kernels directly (``ConvRunner``), so no NCHW round trips happen i
 """
 from __future__ import annotations
 
-import ctypes
 from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
@@ -166,7 +165,7 @@ class ConvRunner:
                        [c.weight for c in self.convs] + [c.bias for c in self.convs], make)
 
     def _prepare(self, src0: Chan, src1: Optional[Chan], n: int, h: int, w: int):
-        """``run``'s and ``bind``'s prologue: the channel check, the format, the packed form."""
+        """``args``' prologue: the channel check, the format, the packed form."""
         c1 = 0 if src1 is None else src1.c
         if src0.c + c1 != self.cin:
             raise ValueError(f"conv expects {self.cin} input channels, got {src0.c}+{c1}")
@@ -177,33 +176,22 @@ class ConvRunner:
              src1: Optional[Chan] = None, epilogue: int = EPI_PLAIN, gate: Optional[Chan] = None,
              rh: Optional[Chan] = None, hid: Optional[Chan] = None,
              bias_map: Optional[Chan] = None):
-        """``run``'s scflow_conv_args (weights packed now; the runner keeps them) without
-        launching — for ``ops.conv2d_pair``."""
-        return self.bind(src0, out, n, h, w, src1, epilogue, gate, rh, hid, bias_map).args
-
-    def bind(self, src0: Chan, out: Optional[Chan], n: int, h: int, w: int,
-             src1: Optional[Chan] = None, epilogue: int = EPI_PLAIN, gate: Optional[Chan] = None,
-             rh: Optional[Chan] = None, hid: Optional[Chan] = None,
-             bias_map: Optional[Chan] = None) -> "ops.BoundLaunch":
-        """``run``'s launch with its arguments fixed (weights packed now, buffers persistent):
-        calling the result launches it on the current stream.  Re-bind after the weights or
-        buffers change."""
+        """The launch's scflow_conv_args, weights packed now.  The struct holds the packed weights
+        and the bias (``ops.conv2d_args``), so its holder — ``run``, a recorded ``run``
+        (``ops.binding``), ``ops.conv2d_pair``, ``ops.xhead_pred`` — keeps them alive."""
         packed, bias = self._prepare(src0, src1, n, h, w)
-        args = ops.conv2d_args(src0, packed, bias, n, h, w, self.cout, self.kh, self.kw, self.ph,
+        return ops.conv2d_args(src0, packed, bias, n, h, w, self.cout, self.kh, self.kw, self.ph,
                                self.pw, self.act, out=out, src1=src1, epilogue=epilogue, gate=gate,
                                rh=rh, hid=hid, stride=self.stride, bias_map=bias_map, bk=self._bk)
-        bl = ops.BoundLaunch(_lib.load().scflow_conv2d, args, src0.buf.device.index, "scflow_conv2d")
-        bl.keep = (packed, bias)  # the launch holds the packed weights alive
-        return bl
 
     def run(self, src0: Chan, out: Optional[Chan], n: int, h: int, w: int,
             src1: Optional[Chan] = None, epilogue: int = EPI_PLAIN, gate: Optional[Chan] = None,
             rh: Optional[Chan] = None, hid: Optional[Chan] = None,
             bias_map: Optional[Chan] = None) -> None:
-        packed, bias = self._prepare(src0, src1, n, h, w)
-        ops.conv2d(src0, packed, bias, n, h, w, self.cout, self.kh, self.kw, self.ph, self.pw,
-                   self.act, out=out, src1=src1, epilogue=epilogue, gate=gate, rh=rh, hid=hid,
-                   stride=self.stride, bias_map=bias_map, bk=self._bk)
+        """Launch ``args(...)`` on the current stream; under ``ops.binding`` the launch is
+        recorded for replay (``run=False``: only recorded)."""
+        ops.conv2d_launch(self.args(src0, out, n, h, w, src1, epilogue, gate, rh, hid, bias_map),
+                          src0.buf)
 
     def flops(self, m: int) -> float:
         """Algorithmic FLOPs of one launch over m output pixels (2·m·cout·taps·cin)."""
@@ -374,17 +362,6 @@ class MotionEncoder(nn.Module):
         return ops.chan_to_nchw(Chan.whole(out), n, h, w)
 
 
-def bind_chain(layers: Sequence[ConvModule], src: Chan, dst: Chan, n: int, h: int, w: int,
-               scratch: List[Tensor]) -> List["ops.BoundLaunch"]:
-    """run_chain's launches bound once (see ConvRunner.bind)."""
-    out_l, cur = [], src
-    for i, m in enumerate(layers):
-        out = dst if i == len(layers) - 1 else Chan.whole(scratch[i])
-        out_l.append(ConvRunner.of(m.conv, m.act_type).bind(cur, out, n, h, w))
-        cur = out
-    return out_l
-
-
 def run_chain(layers: Sequence[ConvModule], src: Chan, dst: Chan, n: int, h: int, w: int,
               scratch: Optional[List[Tensor]] = None, hooks: Optional[Sequence] = None) -> None:
     """Run a Sequential of stride-1 ConvModules channels-last; the last one writes ``dst``.
@@ -435,8 +412,8 @@ class ConvGRU(nn.Module):
     fp32): the z|r and q launches take the bf16 direct conv (``_lib.CONV_BF16``): h, r·h and the
     motion features are rounded to bf16 on load and the weights when packed, products accumulate
     in fp32, every buffer and the epilogues stay fp32.  The hoisted-context conv keeps its fp32
-    kernel (once per forward, its output is the fp32 bias map).  Read at every ``step`` /
-    ``bind_step``; a shape the kernel does not cover raises ScflowError (no fallback)."""
+    kernel (once per forward, its output is the fp32 bias map).  Read at every ``step``;
+    a shape the kernel does not cover raises ScflowError (no fallback)."""
     _kernel = {"Conv": 3, "SeqConv": ((1, 5), (5, 1))}
     _padding = {"Conv": 1, "SeqConv": ((0, 2), (2, 0))}
 
@@ -506,52 +483,14 @@ class ConvGRU(nn.Module):
             rc.run(cxt, Chan(bm, i * 3 * hc, 3 * hc), n, h, w)
         return bm
 
-    def bind_step(self, hx: Chan, z: Chan, rh: Chan, n: int, h: int, w: int,
-                  ctx_map: Optional[Tensor] = None, cxt_channels: int = 0):
-        """``step``'s launches bound once; returns step(hooks=None) replaying them."""
-        hc = self.h_channels
-        hid = Chan(hx.buf, hx.off, hc)
-        x = Chan(hx.buf, hx.off + hc, hx.c - hc)
-        launches = []
-        if ctx_map is not None:
-            mot = Chan(hx.buf, hx.off + hc + cxt_channels, hx.c - hc - cxt_channels)
-            for i, (rzr, rq, _) in enumerate(self._ctx_runners(cxt_channels)):
-                bzr = Chan(ctx_map, i * 3 * hc, 2 * hc)
-                bq = Chan(ctx_map, i * 3 * hc + 2 * hc, hc)
-                launches.append((rzr.bind(hid, None, n, h, w, src1=mot, epilogue=EPI_GRU_ZR, gate=z,
-                                          rh=rh, hid=hid, bias_map=bzr),
-                                 rq.bind(rh, None, n, h, w, src1=mot, epilogue=EPI_GRU_Q, gate=z,
-                                         hid=hid, bias_map=bq)))
-        else:
-            for rzr, rq in self.runners():
-                launches.append((rzr.bind(hx, None, n, h, w, epilogue=EPI_GRU_ZR, gate=z, rh=rh,
-                                          hid=hid),
-                                 rq.bind(rh, None, n, h, w, src1=x, epilogue=EPI_GRU_Q, gate=z,
-                                         hid=hid)))
-
-        def step(hooks=None) -> None:
-            hzr = hooks.get("gru_zr") if hooks else None
-            hq = hooks.get("gru_q") if hooks else None
-            for lzr, lq in launches:
-                if hzr:
-                    hzr(True)
-                lzr()
-                if hzr:
-                    hzr(False)
-                if hq:
-                    hq(True)
-                lq()
-                if hq:
-                    hq(False)
-        return step
-
     def step(self, hx: Chan, z: Chan, rh: Chan, n: int, h: int, w: int, hooks=None,
              ctx_map: Optional[Tensor] = None, cxt_channels: int = 0) -> None:
         """In-place GRU update of channels [0, hc) of ``hx`` (= cat[h, x] channels-last).
 
         ``ctx_map`` (from ``context_map``): the first ``cxt_channels`` of x are the loop-invariant
         context whose contribution is in the map; the convs then skip those channels.
-        ``hooks`` (optional dict name -> callable(start)) brackets the z|r and q launches."""
+        ``hooks`` (optional dict name -> callable(start)) brackets the z|r and q launches; under
+        ``ops.binding`` the brackets are recorded with the launches (``ops.host_call``)."""
         hc = self.h_channels
         hid = Chan(hx.buf, hx.off, hc)
         x = Chan(hx.buf, hx.off + hc, hx.c - hc)
@@ -563,24 +502,23 @@ class ConvGRU(nn.Module):
                       for i, (rzr, rq, _) in enumerate(self._ctx_runners(cxt_channels))]
         else:
             stages = [(rzr, rq, None, None, None) for rzr, rq in self.runners()]
+        def bracket(hk, start):  # in launch order: recorded and replayed with the launch
+            if hk:
+                ops.host_call(lambda: hk(start))
         for rzr, rq, mot, bzr, bq in stages:
-            if hzr:
-                hzr(True)
+            bracket(hzr, True)
             if mot is None:
                 rzr.run(hx, None, n, h, w, epilogue=EPI_GRU_ZR, gate=z, rh=rh, hid=hid)
             else:
                 rzr.run(hid, None, n, h, w, src1=mot, epilogue=EPI_GRU_ZR, gate=z, rh=rh, hid=hid,
                         bias_map=bzr)
-            if hzr:
-                hzr(False)
-            if hq:
-                hq(True)
+            bracket(hzr, False)
+            bracket(hq, True)
             if mot is None:
                 rq.run(rh, None, n, h, w, src1=x, epilogue=EPI_GRU_Q, gate=z, hid=hid)
             else:
                 rq.run(rh, None, n, h, w, src1=mot, epilogue=EPI_GRU_Q, gate=z, hid=hid, bias_map=bq)
-            if hq:
-                hq(False)
+            bracket(hq, False)
 
     def zr_runner(self, cxt_channels: int = 0) -> "ConvRunner":
         """The first SeqConv stage's fused z|r conv (context hoisted if cxt_channels > 0)."""

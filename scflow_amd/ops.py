@@ -34,8 +34,11 @@ def _stream(t: Tensor) -> int:
 
 
 class BoundCall:
-    """A recorded C-ABI launch: its arguments (device pointers of persistent buffers, sizes)
-    fixed, the stream taken at call time.  See ``binding``."""
+    """A recorded C-ABI launch: a function, its argument tuple (device pointers of persistent
+    buffers, sizes, ``byref`` of an argument struct), a device index and a name; the stream is
+    taken at call time.  The one way to replay a launch: see ``binding``.  It keeps alive what
+    its argument tuple refers to — a struct, and through it the tensors the struct's builder
+    attached (``conv2d_args``, ``_pose_step_call``) — and nothing else."""
     __slots__ = ("fn", "args", "dev", "name")
 
     def __init__(self, fn, args, dev: int, name: str) -> None:
@@ -363,9 +366,13 @@ def conv2d(src0: Chan, packed: Tensor, bias: Optional[Tensor], n: int, h: int, w
            bias_map: Optional[Chan] = None, bk: int = 16, **fused) -> None:
     """One scflow_conv2d launch; ``fused``: in_scale / in_shift / out_scale / out_shift / res
     (Winograd 3×3 and ``_lib.CONV_BF16_3X3N`` only, see conv2d_args)."""
-    a = conv2d_args(src0, packed, bias, n, h, w, cout, kh, kw, ph, pw, act, out, src1, epilogue,
-                    gate, rh, hid, stride, bias_map, bk, **fused)
-    _launch("scflow_conv2d", src0.buf,ctypes.byref(a))
+    conv2d_launch(conv2d_args(src0, packed, bias, n, h, w, cout, kh, kw, ph, pw, act, out, src1,
+                              epilogue, gate, rh, hid, stride, bias_map, bk, **fused), src0.buf)
+
+
+def conv2d_launch(args, dev_tensor: Tensor) -> None:
+    """scflow_conv2d on an argument struct from ``conv2d_args`` / ``ConvRunner.args``."""
+    _launch("scflow_conv2d", dev_tensor, ctypes.byref(args))
 
 
 def conv2d_pair(args_a, args_b, dev_tensor: Tensor) -> None:
@@ -419,22 +426,6 @@ def xhead_pred(hidden_args, flow_channels: int, pred_w: Tensor, ws: Tensor,
             _p(mask_out.buf) + 4 * mask_out.off, mask_out.buf.shape[1])
 
 
-class BoundLaunch:
-    """A C-ABI launch whose argument struct is built once (pointers of persistent buffers):
-    calling it costs one ctypes call on the caller's current stream.  The decoder binds every
-    convolution of its refinement loop once per forward and replays them every iteration."""
-    __slots__ = ("fn", "args", "ref", "dev", "name", "keep")
-
-    def __init__(self, fn, args, dev: int, name: str) -> None:
-        self.fn, self.args, self.dev, self.name = fn, args, dev, name
-        self.ref = ctypes.byref(args)
-
-    def __call__(self) -> None:
-        rc = self.fn(self.ref, raw_stream(self.dev))
-        if rc:
-            check(rc, self.name)
-
-
 class SyncEvent:
     """A device-scope cross-stream event (scflow_sync_event_*): ``record(stream)`` then
     ``wait(stream)`` orders the second stream after the first without the system-scope cache
@@ -486,7 +477,9 @@ def conv2d_args(src0: Chan, packed: Tensor, bias: Optional[Tensor], n: int, h: i
     """The validated scflow_conv_args of one launch (see conv2d).  in_/out_scale/shift and res
     (Winograd 3×3 and the bf16 direct 3×3 conv's encoder form, ``_lib.CONV_BF16_3X3N``, only):
     relu(x·in_scale + in_shift) on load, (conv + b)·out_scale + out_shift, + res before the
-    activation."""
+    activation.  The struct holds the packed weights and the bias it points at (``_keep``, and
+    the workspace in ``_ws``), so whoever holds the struct — a recorded call, ``conv2d_pair``,
+    ``xhead_pred`` — keeps them alive."""
     for nm, ch in (("src0", src0), ("src1", src1), ("out", out), ("gate", gate), ("rh", rh),
                    ("hid", hid), ("bias_map", bias_map)):
         if ch is not None:
@@ -500,6 +493,7 @@ def conv2d_args(src0: Chan, packed: Tensor, bias: Optional[Tensor], n: int, h: i
         a.src1, a.c1, a.s1 = src1.ptr, src1.c, src1.stride
     a.weight = packed.data_ptr()
     a.bias = None if bias is None else bias.data_ptr()
+    a._keep = (packed, bias)
     if out is not None:
         a.out, a.so = out.ptr, out.stride
     a.n, a.h, a.w = n, h, w
@@ -602,28 +596,23 @@ def pose_step(drot: Tensor, dt: Tensor, R: Tensor, t: Tensor, K: Tensor, points:
               lrm_next: Optional[Chan] = None) -> None:
     """One launch: ``pose_update_flow`` + ``flow_upsample(lr, delta, mask → flow_up, mask_up)``
     + (if ``lr_next``) the next iteration's ``flow_downsample`` of the new pose flow into
-    ``lr_next`` / ``hx_next``, computed from the pose directly (scflow_pose_step).  ``parts``
-    (scflow_pose_step_part): 1 = only the full-resolution outputs, 2 = only the ↓8 flow.
+    ``lr_next`` / ``hx_next``, computed from the pose directly (scflow_pose_step_call).
+    ``parts``: 1 = only the full-resolution outputs, 2 = only the ↓8 flow.
     ``heads`` (``MultiClassPoseHead.heads_args``): the pose head's rotation / translation heads
-    in the same launch (scflow_pose_step_heads) — ``drot`` / ``dt`` are then written, not read.
-    ``mask_next`` ([n·h·w], the mask just predicted) / ``lrm_next`` (scflow_pose_step_masked, the
-    reference's ``mask_flow``): ``lr_next`` still receives the unmasked ↓8 flow, ``lrm_next`` and
+    in the same launch — ``drot`` / ``dt`` are then written, not read.
+    ``mask_next`` ([n·h·w], the mask just predicted) / ``lrm_next`` (the reference's
+    ``mask_flow``): ``lr_next`` still receives the unmasked ↓8 flow, ``lrm_next`` and
     ``hx_next`` receive ``lr_next · mask_next``."""
     for nm, x in (("drot", drot), ("dt", dt), ("R", R), ("t", t), ("K", K), ("points", points),
                   ("R_out", R_out), ("t_out", t_out), ("flow_out", flow_out), ("lr", lr),
                   ("flow_up", flow_up)):
         _require(x, nm)
-    n, H, W, _ = points.shape
+    n = points.shape[0]
     if lr_next is not None and lr_next.buf.data_ptr() == lr.data_ptr():
         raise ValueError("pose_step: lr_next must not alias lr")
-    args = (_p(drot), _p(dt), _p(R), _p(t), _p(K), _p(points), _p(R_out), _p(t_out), _p(flow_out), n,
-            H, W, float(weight), pose_mode(drot, depth_transform), float(invalid_num), _p(lr),
-            _p(delta), _p(mask), _p(flow_up), _p(mask_up),
-            None if lr_next is None else lr_next.ptr, 0 if lr_next is None else lr_next.stride,
-            None if hx_next is None else hx_next.ptr, 0 if hx_next is None else hx_next.stride,
-            h, w, float(up_scale), 1.0 / float(up_scale))
+    mode = pose_mode(drot, depth_transform)
     if heads is not None:
-        x, xsplit, xbias, k, Wr, br, rch, Wt, bt, label, num_class = heads
+        label, x = heads[9], heads[0]
         if label.dtype != torch.int64 or label.device != x.device:
             raise TypeError("label must be an int64 tensor on the same device")
     if mask_next is not None or lrm_next is not None:
@@ -634,19 +623,44 @@ def pose_step(drot: Tensor, dt: Tensor, R: Tensor, t: Tensor, K: Tensor, points:
         if lrm_next is not None and lrm_next.buf.data_ptr() in (lr.data_ptr(),
                                                                 lr_next.buf.data_ptr()):
             raise ValueError("pose_step: lrm_next must alias neither lr nor lr_next")
-        hd = ((None, 0, None, 0, None, None, 0, None, None, None, 0) if heads is None else
-              (_p(x), int(xsplit), _p(xbias), int(k), _p(Wr), _p(br), int(rch), _p(Wt), _p(bt),
-               _p(label), int(num_class)))
-        _launch("scflow_pose_step_masked", drot, *hd, *args[:24], _p(mask_next),
-                None if lrm_next is None else lrm_next.ptr,
-                0 if lrm_next is None else lrm_next.stride, *args[24:], int(parts))
-    elif heads is not None:
-        _launch("scflow_pose_step_heads", drot, _p(x), int(xsplit), _p(xbias), int(k), _p(Wr), _p(br),
-                int(rch), _p(Wt), _p(bt), _p(label), int(num_class), *args, int(parts))
-    elif parts == 3:
-        _launch("scflow_pose_step", drot, *args)
-    else:
-        _launch("scflow_pose_step_part", drot, *args, int(parts))
+    _pose_step_call(drot=drot, dt=dt, R=R, t=t, K=K, points=points, R_out=R_out, t_out=t_out,
+                    flow_out=flow_out, invalid_num=invalid_num, lr=lr, delta=delta, mask=mask,
+                    flow_up=flow_up, mask_up=mask_up, h=h, w=w, up_scale=up_scale, lr_next=lr_next,
+                    hx_next=hx_next, weight=weight, mode=mode,
+                    parts=parts, heads=heads, mask_next=mask_next, lrm_next=lrm_next)
+
+
+def _pose_step_call(*, R, t, K, points, flow_out, invalid_num, lr, delta, mask, flow_up, mask_up, h,
+                    w, up_scale, drot=None, dt=None, R_out=None, t_out=None, lr_next=None,
+                    hx_next=None, weight=10.0, mode=0, parts=1, heads=None, mask_next=None,
+                    lrm_next=None) -> None:
+    """Fill scflow_pose_step_args by field name (unset: NULL / 0) and launch
+    scflow_pose_step_call.  ``drot`` None is the given-pose form (R, t are the updated pose).
+    The struct holds the tensors it points at (``_keep``): a recorded call keeps them alive."""
+    a = _lib.PoseStepArgs()
+    keep = [drot, dt, R, t, K, points, R_out, t_out, flow_out, lr, delta, mask, flow_up, mask_up,
+            mask_next]
+    if heads is not None:
+        x, xsplit, xbias, k, Wr, br, rch, Wt, bt, label, num_class = heads
+        a.x, a.xsplit, a.xbias, a.k = _p(x), int(xsplit), _p(xbias), int(k)
+        a.Wr, a.br, a.rch, a.Wt, a.bt = _p(Wr), _p(br), int(rch), _p(Wt), _p(bt)
+        a.label, a.num_class = _p(label), int(num_class)
+        keep += [x, xbias, Wr, br, Wt, bt, label]
+    a.drot, a.dt, a.R_src, a.t_src, a.K, a.points = _p(drot), _p(dt), _p(R), _p(t), _p(K), _p(points)
+    a.R_dst, a.t_dst, a.flow = _p(R_out), _p(t_out), _p(flow_out)
+    a.n, a.H, a.W = points.shape[:3]
+    a.weight, a.depth_transform, a.invalid_num = float(weight), int(mode), float(invalid_num)
+    a.lr, a.delta, a.mask, a.flow_up, a.mask_up = _p(lr), _p(delta), _p(mask), _p(flow_up), _p(mask_up)
+    a.h, a.w, a.up_scale, a.down_scale = h, w, float(up_scale), 1.0 / float(up_scale)
+    for ch, ptr, stride in ((lr_next, "lr_next", "s_next"), (hx_next, "hx_next", "s_hx"),
+                            (lrm_next, "lrm_next", "s_lrm")):
+        if ch is not None:
+            setattr(a, ptr, ch.ptr)
+            setattr(a, stride, ch.stride)
+            keep.append(ch.buf)
+    a.mask_next, a.parts = _p(mask_next), int(parts)
+    a._keep = keep
+    _launch("scflow_pose_step_call", R, ctypes.byref(a))
 
 
 def pose_step_given(R: Tensor, t: Tensor, K: Tensor, points: Tensor, flow_out: Tensor,
@@ -654,16 +668,14 @@ def pose_step_given(R: Tensor, t: Tensor, K: Tensor, points: Tensor, flow_out: T
                     flow_up: Tensor, mask_up: Optional[Tensor], h: int, w: int,
                     up_scale: float) -> None:
     """``pose_step``'s full-resolution part (parts = 1) from an already updated pose R, t (the ↓8
-    part's R_out / t_out): pose flow, ×8 flow prediction and mask, no pose update
-    (scflow_pose_step_part with drot6 = NULL)."""
+    part's R_out / t_out): pose flow, ×8 flow prediction and mask, no pose update (the same
+    struct with drot = NULL)."""
     for nm, x in (("R", R), ("t", t), ("K", K), ("points", points), ("flow_out", flow_out),
                   ("lr", lr), ("flow_up", flow_up)):
         _require(x, nm)
-    n, H, W, _ = points.shape
-    _launch("scflow_pose_step_part", R, None, None, _p(R), _p(t), _p(K), _p(points), None, None,
-            _p(flow_out), n, H, W, 10.0, 0, float(invalid_num), _p(lr), _p(delta), _p(mask),
-            _p(flow_up), _p(mask_up), None, 0, None, 0, h, w, float(up_scale),
-            1.0 / float(up_scale), 1)
+    _pose_step_call(R=R, t=t, K=K, points=points, flow_out=flow_out, invalid_num=invalid_num, lr=lr,
+                    delta=delta, mask=mask, flow_up=flow_up, mask_up=mask_up, h=h, w=w,
+                    up_scale=up_scale)
 
 
 # ------------------------------------------------------------------------------- RANSAC-PnP

@@ -211,8 +211,6 @@ class RecurrentCore:
         self.s_corr = self.scratch(enc.corr_net)
         self.s_flow = self.scratch(enc.flow_net)
         self.s_out = self.scratch(enc.out_net)
-        self._gru_step = dec.gru.bind_step(Chan.whole(HX), Chan.whole(self.Z), Chan.whole(self.RH),
-                                           N, h, w, ctx_map=self.ctx_map, cxt_channels=xc)
 
     def scratch(self, mods):
         """The buffers between a Sequential's ConvModules (every output but the last)."""
@@ -257,10 +255,16 @@ class RecurrentCore:
         self.segment("out", self._out)
 
     def gru(self, hooks=None) -> None:
-        """The GRU step, in place on HX's hidden channels (``hooks``: ConvGRU.bind_step's)."""
-        self._gru_step(hooks)
+        """The GRU step, in place on HX's hidden channels (``hooks``: ConvGRU.step's, read on
+        the recording pass)."""
+        self.segment("gru", self._gru, hooks)
 
     # ------------------------------------------------------------------ the recorded launches
+    def _gru(self, hooks):
+        dec = self.dec
+        dec.gru.step(Chan.whole(self.HX), Chan.whole(self.Z), Chan.whole(self.RH), self.N, self.h,
+                     self.w, hooks=hooks, ctx_map=self.ctx_map, cxt_channels=dec.cxt_channels)
+
     def _flow_branch(self, flow_in):
         run_chain(self.dec.encoder.flow_net, Chan.whole(flow_in), Chan(self.MF, self.cc, self.cf),
                   self.N, self.h, self.w, self.s_flow, hooks=self.hooks_for(None, "flow_net1"))

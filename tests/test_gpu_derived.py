@@ -2,6 +2,8 @@
 keeps one — the encoders' packings and eval-BatchNorm affine, the pose head's per-layer packings
 and FC1 permutation, ``ConvRunner``'s form per launch shape.  fp32 throughout; a module whose
 weights moved must compute exactly what a freshly built module with those weights computes."""
+import ctypes
+
 import pytest
 import torch
 
@@ -122,7 +124,7 @@ def test_a_recorded_launch_outlives_another_launch_shape():
     x32, x64 = (torch.randn(n * h * w, 32, generator=g).cuda() for w in (32, 64))
     y32, y64 = torch.zeros(n * h * 32, 32, device="cuda"), torch.zeros(n * h * 64, 32, device="cuda")
     a32 = r.args(ops.Chan.whole(x32), ops.Chan.whole(y32), n, h, 32)
-    launch = ops.BoundLaunch(_lib.load().scflow_conv2d, a32, 0, "scflow_conv2d")
+    launch = ops.BoundCall(_lib.load().scflow_conv2d, (ctypes.byref(a32),), 0, "scflow_conv2d")
     form32 = r.packed(32, 0, 32, a32.bk)[0]
     assert a32.weight == form32.data_ptr()
     launch()
@@ -134,3 +136,81 @@ def test_a_recorded_launch_outlives_another_launch_shape():
     launch()
     torch.cuda.synchronize()
     assert torch.equal(y32, first)
+
+
+def test_a_conv_struct_holds_what_it_points_at():
+    """``conv2d_args`` attaches the packed weights and the bias to the struct: with every other
+    reference dropped, and buffers of their sizes allocated and overwritten in between, the
+    struct still launches the conv it was built for."""
+    import gc
+    from scflow_amd import ops
+    conv = torch.nn.Conv2d(32, 32, 3, padding=1)
+    synthetic.fill_module_(conv, 4)
+    weight, bias0 = conv.weight.detach().cuda(), conv.bias.detach().cuda()
+    n, h, w = 1, 8, 32
+    x = torch.randn(n * h * w, 32, generator=torch.Generator().manual_seed(2)).cuda()
+    bk = ops.conv_pick_bk(n, h, w, 32, 0, 32, 3, 3, 1, 1)
+
+    def build(y):
+        packed, bias = ops.pack_conv_weight(weight, 32, 0, w, 1, bk), bias0.clone()
+        return ops.conv2d_args(ops.Chan.whole(x), packed, bias, n, h, w, 32, 3, 3, 1, 1, "ReLU",
+                               out=ops.Chan.whole(y), bk=bk), packed.numel(), bias.numel()
+
+    y, y_fresh = torch.zeros(n * h * w, 32, device="cuda"), torch.zeros(n * h * w, 32, device="cuda")
+    a, n_packed, n_bias = build(y)
+    torch.cuda.synchronize()
+    gc.collect()
+    # what the allocator would hand out again had the struct not held its inputs
+    junk = [torch.full((size,), 1e30, device="cuda") for size in (n_packed, n_bias) * 3]
+    torch.cuda.synchronize()
+    ops.conv2d_launch(a, x)
+    ops.conv2d_launch(build(y_fresh)[0], x)
+    torch.cuda.synchronize()
+    assert y.abs().max() > 0 and torch.isfinite(y).all()
+    assert torch.equal(y, y_fresh)
+    del junk
+
+
+@pytest.mark.parametrize("hoist", [False, True])
+def test_a_recorded_gru_step_replays_the_eager_one(hoist):
+    """``ConvGRU.step`` recorded once under ``ops.binding`` and replayed twice against three eager
+    steps from the same state (1 × 32 × 32, the narrowest map these kernels take; with and without
+    the hoisted context): the same hidden state bit for bit after each, and the ``gru_zr`` /
+    ``gru_q`` hooks called start / stop around each launch on every pass."""
+    from scflow_amd import ops
+    from scflow_amd.modules import ConvGRU
+    n, h, w, hc, cxt = 1, 32, 32, 128, 128
+    M = n * h * w
+    gru = ConvGRU(hc, 2 * hc, "SeqConv")  # x = context | motion
+    synthetic.fill_module_(gru, 3)
+    gru = gru.cuda()
+    hx0 = torch.randn(M, 3 * hc, generator=torch.Generator().manual_seed(6)).cuda()
+    hx0[:, :hc].tanh_()
+    want = [("gru_zr", True), ("gru_zr", False), ("gru_q", True), ("gru_q", False)] * 2  # two stages
+
+    def state():
+        hx = hx0.clone()
+        log = []
+        hooks = {name: (lambda start, name=name: log.append((name, start))) for name in ("gru_zr", "gru_q")}
+        cm = gru.context_map(ops.Chan(hx, hc, cxt), n, h, w) if hoist else None
+        args = (ops.Chan.whole(hx), ops.Chan.whole(torch.zeros(M, hc, device="cuda")),
+                ops.Chan.whole(torch.zeros(M, hc, device="cuda")), n, h, w)
+        return hx, log, lambda: gru.step(*args, hooks=hooks, ctx_map=cm, cxt_channels=cxt)
+
+    hx_e, log_e, eager = state()
+    hx_r, log_r, step = state()
+    calls = []
+    for i in range(3):
+        eager()
+        if i == 0:
+            with ops.binding(calls):  # records and runs
+                step()
+        else:
+            for c in calls:
+                c()
+        torch.cuda.synchronize()
+        assert torch.equal(hx_r, hx_e), i
+        assert log_e == want * (i + 1) and log_r == log_e, i
+    assert not torch.equal(hx_e[:, :hc], hx0[:, :hc]) and torch.equal(hx_e[:, hc:], hx0[:, hc:])
+    # in the record each launch stands between its start and its stop
+    assert [isinstance(c, ops.BoundCall) for c in calls] == [False, True, False] * 4

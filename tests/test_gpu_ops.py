@@ -665,6 +665,103 @@ def test_pose_step_matches_separate_launches(ops, S, s, nxt):
         assert torch.equal(a, b), nm
 
 
+# case → (the positional export called raw, what the call sets)
+POSE_ENTRY_CASES = {
+    "plain": ("scflow_pose_step", dict()),
+    "parts1": ("scflow_pose_step_part", dict(parts=1)),
+    "parts2": ("scflow_pose_step_part", dict(parts=2)),
+    "given": ("scflow_pose_step_part", dict(parts=1, given=True)),
+    "heads": ("scflow_pose_step_heads", dict(heads=True)),
+    "masked": ("scflow_pose_step_masked", dict(masked=True)),
+    "masked_heads": ("scflow_pose_step_masked", dict(masked=True, heads=True)),
+}
+
+
+@pytest.mark.parametrize("case", list(POSE_ENTRY_CASES))
+def test_pose_step_entries_give_the_same_bits(ops, case):
+    """The four positional exports, called raw through ctypes, against ``ops.pose_step`` /
+    ``ops.pose_step_given``, which go through scflow_pose_step_call: one launcher behind all five,
+    so every output buffer (written or not) holds the same bits."""
+    from scflow_amd import _lib, synthetic
+    from tests.test_pose_step_host import ORDERS
+    entry, opt = POSE_ENTRY_CASES[case]
+    parts, given = opt.get("parts", 3), opt.get("given", False)
+    heads, masked = opt.get("heads", False), opt.get("masked", False)
+    n, S, s, k, ncls, split, rch = 3, 128, 16, 256, 21, 4, 6
+    M = n * s * s
+    sc = synthetic.make_scene(n, S, seed=5)
+    R0, t0, K, depth = (t(sc[key]).cuda() for key in ("ref_rotation", "ref_translation",
+                                                      "internel_k", "depth"))
+    g = torch.Generator().manual_seed(8)
+    drot_in = (torch.tensor([[1.0, 0, 0, 0, 1.0, 0]]).repeat(n, 1) +
+               0.03 * torch.randn(n, 6, generator=g)).cuda()
+    dt_in = (0.05 * torch.randn(n, 3, generator=g)).cuda()
+    pts = ops.lift_points(depth, K, R0, t0)
+    lr = torch.randn(M, 2, generator=g).cuda()
+    delta = torch.randn(M, 2, generator=g).cuda()
+    mask = torch.rand(M, 1, generator=g).cuda()
+    mnext = torch.rand(M, generator=g).cuda()
+    x = (0.1 * torch.randn(split, n, k, generator=g)).cuda()
+    xb = (0.05 * torch.randn(k, generator=g)).cuda()
+    Wr = (0.01 * torch.randn(rch * ncls, k, generator=g)).cuda()
+    br = torch.tensor([1.0, 0, 0, 0, 1.0, 0] * ncls).cuda()
+    Wt = (0.01 * torch.randn(3 * ncls, k, generator=g)).cuda()
+    bt = (0.01 * torch.randn(3 * ncls, generator=g)).cuda()
+    label = torch.tensor([7, 3, 12], dtype=torch.int64).cuda()
+    R1, t1 = ops.pose_update(drot_in, dt_in, R0, t0)  # the given-pose form's updated pose
+
+    def outputs():
+        def f(*shape):
+            return torch.full(shape, 5.0, device="cuda")
+        return dict(R=f(n, 3, 3), t=f(n, 3), flow=f(n, 2, S, S), up=f(n, 2, S, S), mup=f(n, 1, S, S),
+                    nx=f(M, 2), hx=f(M, 6), lrm=f(M, 4), drot=f(n, rch) if heads else drot_in,
+                    dt=f(n, 3) if heads else dt_in)
+    a, b = outputs(), outputs()
+
+    # raw: the positional export, its arguments taken by name in the header's order
+    c = {f: 0 for f, _ in _lib.PoseStepArgs._fields_}
+    c.update(K=K.data_ptr(), points=pts.data_ptr(), flow=a["flow"].data_ptr(), n=n, H=S, W=S,
+             weight=10.0, invalid_num=400.0, lr=lr.data_ptr(), delta=delta.data_ptr(),
+             mask=mask.data_ptr(), flow_up=a["up"].data_ptr(), mask_up=a["mup"].data_ptr(), h=s, w=s,
+             up_scale=8.0, down_scale=0.125, parts=parts)
+    if given:
+        c.update(R_src=R1.data_ptr(), t_src=t1.data_ptr())
+    else:
+        c.update(drot=a["drot"].data_ptr(), dt=a["dt"].data_ptr(), R_src=R0.data_ptr(),
+                 t_src=t0.data_ptr(), R_dst=a["R"].data_ptr(), t_dst=a["t"].data_ptr(),
+                 lr_next=a["nx"].data_ptr(), s_next=2, hx_next=a["hx"].data_ptr() + 4 * 4, s_hx=6)
+    if heads:
+        c.update(x=x.data_ptr(), xsplit=split, xbias=xb.data_ptr(), k=k, Wr=Wr.data_ptr(),
+                 br=br.data_ptr(), rch=rch, Wt=Wt.data_ptr(), bt=bt.data_ptr(), label=label.data_ptr(),
+                 num_class=ncls)
+    if masked:
+        c.update(mask_next=mnext.data_ptr(), lrm_next=a["lrm"].data_ptr() + 4 * 1, s_lrm=4)
+    rc = getattr(_lib.load(), entry)(*[c[f] for f in ORDERS[entry]],
+                                     torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, rc
+
+    # the wrappers: the struct entry
+    if given:
+        ops.pose_step_given(R1, t1, K, pts, b["flow"], 400.0, lr, delta, mask, b["up"], b["mup"], s, s,
+                            8.0)
+    else:
+        kw = dict(heads=(x, split, xb, k, Wr, br, rch, Wt, bt, label, ncls)) if heads else {}
+        if masked:
+            kw.update(mask_next=mnext, lrm_next=ops.Chan(b["lrm"], 1, 2))
+        ops.pose_step(b["drot"], b["dt"], R0, t0, K, pts, b["R"], b["t"], b["flow"], 400.0, lr, delta,
+                      mask, b["up"], b["mup"], s, s, 8.0, lr_next=ops.Chan.whole(b["nx"]),
+                      hx_next=ops.Chan(b["hx"], 4, 2), parts=parts, **kw)
+    torch.cuda.synchronize()
+    for key in a:
+        assert torch.equal(a[key], b[key]), key
+    # what the case's parts write was written, the rest was left alone
+    assert ((a["flow"] == 5).all().item(), (a["up"] == 5).all().item()) == (not parts & 1,) * 2
+    assert (a["nx"] == 5).all().item() == (not parts & 2)
+    assert (a["lrm"][:, 1:3] == 5).all().item() == (not masked)
+    if heads:
+        assert not (a["drot"] == 5).any() and not (a["dt"] == 5).any()
+
+
 @pytest.mark.parametrize("blocks", [1, 7])
 def test_pose_step_given_fullres_blocks(ops, blocks, monkeypatch):
     """The deferred full-resolution part with SCFLOW_FULLRES_BLOCKS workgroups per image (1: one

@@ -9,7 +9,7 @@ against the bf16 one, by family:
   enc   the RAFT encoders' stride-1 3×3 convs with their fused normalisation, fp32 against
         ``_lib.CONV_BF16_3X3N``: the per-launch part of tools/enc_bench.py
 
-One method for all: each variant's launch is bound once and issued ``--launches`` times back to
+One method for all: each variant's launch is recorded once and issued ``--launches`` times back to
 back between two device events, the variants alternating within a round, ``--rounds`` rounds,
 median [min, max] of the per-launch time.  Every variant is listed twice (``rep`` 0 and 1:
 identical runs of the same process, whose difference is the run-to-run spread the wiring rules of
@@ -39,7 +39,7 @@ MENC_CONVS = [("corr_net.1", (256, 0), 192, "ReLU", 0, 256),     # → MF[:, :19
 
 
 def menc_variants(n, h, w):
-    """[(label, plan kind, bound launch, keep-alive, times)]: per conv, fp32 and bf16, each twice."""
+    """[(label, plan kind, recorded launch, keep-alive, times)]: per conv, fp32 and bf16, each twice."""
     from scflow_amd import _lib, ops
     from scflow_amd.modules import ConvRunner
     M = n * h * w
@@ -58,13 +58,13 @@ def menc_variants(n, h, w):
                 r.fmt = fmt
                 s0 = ops.Chan(src, 0, c0)
                 s1 = ops.Chan(src, c0, c1) if c1 else None
-                bl = r.bind(s0, ops.Chan(out, off, cout), n, h, w, src1=s1)
-                variants.append((f"{name} {label} rep={rep}", plan_name(bl), bl, (r, src, out), []))
+                kind, bl = record(r, s0, ops.Chan(out, off, cout), n, h, w, src1=s1)
+                variants.append((f"{name} {label} rep={rep}", kind, bl, (r, src, out), []))
     return variants
 
 
 def gru_variants(n, h, w):
-    """The same list for the GRU's four launches as ``ConvGRU.bind_step`` binds them with the
+    """The same list for the GRU's four launches as ``ConvGRU.step`` issues them with the
     context hoisted: z|r (epilogue writes z and r·h) and q (epilogue updates h), 1×5 then 5×1."""
     from scflow_amd import _lib, ops
     from scflow_amd.modules import ConvGRU, ConvRunner
@@ -90,19 +90,23 @@ def gru_variants(n, h, w):
                 rzr = ConvRunner([cz, cr], "Sigmoid", in_select=keep, with_bias=False)
                 rq = ConvRunner([cq], "Tanh", in_select=keep, with_bias=False)
                 rzr.fmt = rq.fmt = fmt
-                bzr = rzr.bind(hid, None, n, h, w, src1=mot, epilogue=_lib.EPI_GRU_ZR, gate=ops.Chan.whole(z),
-                               rh=ops.Chan.whole(rh), hid=hid, bias_map=ops.Chan(bmap, i * 3 * hc, 2 * hc))
-                bq = rq.bind(ops.Chan.whole(rh), None, n, h, w, src1=mot, epilogue=_lib.EPI_GRU_Q,
-                             gate=ops.Chan.whole(z), hid=hid, bias_map=ops.Chan(bmap, i * 3 * hc + 2 * hc, hc))
-                for name, bl in (("zr", bzr), ("q ", bq)):
-                    variants.append((f"{name} {k} {label} rep={rep}", plan_name(bl), bl, (hx, z, rh, bmap), []))
+                bzr = record(rzr, hid, None, n, h, w, src1=mot, epilogue=_lib.EPI_GRU_ZR, gate=ops.Chan.whole(z),
+                             rh=ops.Chan.whole(rh), hid=hid, bias_map=ops.Chan(bmap, i * 3 * hc, 2 * hc))
+                bq = record(rq, ops.Chan.whole(rh), None, n, h, w, src1=mot, epilogue=_lib.EPI_GRU_Q,
+                            gate=ops.Chan.whole(z), hid=hid, bias_map=ops.Chan(bmap, i * 3 * hc + 2 * hc, hc))
+                for name, (kind, bl) in (("zr", bzr), ("q ", bq)):
+                    variants.append((f"{name} {k} {label} rep={rep}", kind, bl, (hx, z, rh, bmap), []))
     return variants
 
 
-def plan_name(bl):
+def record(r, *args, **kw):
+    """(plan kind's name, the launch ``r.run(...)`` recorded for replay: ``ops.binding``)."""
     from scflow_amd import _lib, ops
     names = {v: k for k, v in vars(_lib).items() if k.startswith("PLAN_")}
-    return names.get(ops.conv_plan_kind(bl.args), "?")
+    calls = []
+    with ops.binding(calls, run=False):
+        r.run(*args, **kw)
+    return names.get(ops.conv_plan_kind(r.args(*args, **kw)), "?"), calls[0]
 
 
 def by_shape(a, make):
