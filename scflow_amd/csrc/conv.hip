@@ -1187,9 +1187,17 @@ int launch_k(const ConvPlan& c, size_t lds, hipStream_t st, const Args&... args)
 // The Winograd and wide 1×1 plans' instantiations (launch_plan's cases for them).  They stand
 // ahead of conv_pair.h and xhead_pred.h because device code is emitted in the order of first use
 // and the library's code object is kept byte-identical across host-side changes.
+// The input affine is a property of the instantiation (conv_wino.h): a conv that brings in_scale
+// runs the form that carries it, which is the kernel as it was.  So does every 128-wide map —
+// only the encoders' first stage has them — where the form without it measured slower (64 → 64
+// channels at B = 32: 211 µs against 223).
 template <int W, int NBW>
 int launch_wino_k(const ConvPlan& c, const WinoParams& p, hipStream_t st) {
-  return launch_k<conv_wino_kernel<W, NBW>>(c, wino_lds_bytes<W, NBW>(), st, p);
+  if constexpr (W != 128) {
+    if (!p.a.in_scale)
+      return launch_k<conv_wino_kernel<W, NBW, false>>(c, wino_lds_bytes<W, NBW>(), st, p);
+  }
+  return launch_k<conv_wino_kernel<W, NBW, true>>(c, wino_lds_bytes<W, NBW>(), st, p);
 }
 template <int EPI, int DIR, int W>
 int launch_wino5_k(const ConvPlan& c, const Wino5Params& p, hipStream_t st) {

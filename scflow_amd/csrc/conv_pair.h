@@ -40,9 +40,9 @@ __global__ __launch_bounds__(256, 2) void wino_pair_kernel(WinoParams pa, WinoPa
                                                            int gya, int gxb, int gyb) {
   const int L = blockIdx.x, na = gxa * gya;
   if (L < na)
-    conv_wino_body<W, NA>(pa, L % gxa, L / gxa, gxa, gya, L);
+    conv_wino_body<W, NA, false>(pa, L % gxa, L / gxa, gxa, gya, L);
   else
-    conv_wino_body<W, NB>(pb, (L - na) % gxb, (L - na) / gxb, gxb, gyb, L);
+    conv_wino_body<W, NB, false>(pb, (L - na) % gxb, (L - na) / gxb, gxb, gyb, L);
 }
 
 // The grouped kernel that covers (a, b) in this order, or SCFLOW_PAIR_NONE: decided on the two
@@ -58,9 +58,10 @@ int pair_kind(const scflow_conv_args& a, const ConvPlan& pa, const scflow_conv_a
   if (pa.kind == SCFLOW_PLAN_SMALLCIN_MFMA && pb.kind == SCFLOW_PLAN_SMALLCIN_MFMA && a.c0 == 2 &&
       a.kh == 7 && pa.nbw == 2 && b.c0 == 1 && pb.npad == 64 && a.h == b.h && a.w == b.w)
     return SCFLOW_PAIR_SMALLCIN;
-  // F(2×2,3×3) of one width, 32 or 64 output channels per workgroup
+  // F(2×2,3×3) of one width, 32 or 64 output channels per workgroup, neither with the input
+  // affine (the pair runs the bodies without it; the encoders' convs go out one by one)
   if (pa.kind == SCFLOW_PLAN_WINO && pb.kind == SCFLOW_PLAN_WINO && a.w == b.w && a.w != 128 &&
-      pa.nbw <= 2 && pb.nbw <= 2)
+      pa.nbw <= 2 && pb.nbw <= 2 && !a.in_scale && !b.in_scale)
     return SCFLOW_PAIR_WINO;
   return SCFLOW_PAIR_NONE;
 }

@@ -64,8 +64,9 @@ __device__ __forceinline__ floatx4 sub4(floatx4 a, floatx4 b) {
   return floatx4{lo[0], lo[1], hi[0], hi[1]};
 }
 #else
-// scalar forms (v_fma_f32 / v_add_f32 issue beside MFMAs without the packed-op penalty);
-// build with -fno-slp-vectorize so they stay scalar
+// scalar forms; build with -fno-slp-vectorize so they stay scalar.  Beside fp32 MFMAs at two
+// waves per SIMD one packed op costs a little less than the two scalar ops it stands for
+// (tools/micro/mfma_mix.hip), and neither form of the transforms moves a launch
 __device__ __forceinline__ floatx4 fma_s4(floatx4 b, float s, floatx4 a) {
   return floatx4{__builtin_fmaf(b[0], s, a[0]), __builtin_fmaf(b[1], s, a[1]),
                  __builtin_fmaf(b[2], s, a[2]), __builtin_fmaf(b[3], s, a[3])};
@@ -98,6 +99,16 @@ __device__ __forceinline__ void wino_prio(int s, int nst) {
   else
     __builtin_amdgcn_s_setprio(0);
 #endif
+}
+
+// The next stage after t whose halo offsets differ from its predecessor's, or nst: source 0's
+// last stage when it is short of sc channels, source 1's first stage, the last stage when short.
+__device__ __forceinline__ int wino_next_change(int t, int nst0, int nst, int c0, int c1, int sc) {
+  int b = nst;
+  if (c0 % sc && nst0 - 1 > t) b = nst0 - 1;
+  if (nst0 < nst && nst0 > t && nst0 < b) b = nst0;
+  if ((nst0 < nst ? c1 : c0) % sc && nst - 1 > t && nst - 1 < b) b = nst - 1;
+  return b;
 }
 
 #ifndef WINO_SCHED_BARRIER
@@ -182,7 +193,11 @@ constexpr size_t wino_lds_bytes() {
 // was built in round 4 and measured in round 5: ±2 % alone, the decoder 2 % slower; removed.)
 // body: logical block (lbx, lby) of an lgx × lgy grid, stamps at slot sid (conv_pair.h
 // launches two bodies in one grid)
-template <int W, int NBW>
+// AFF: the form with the encoders' normalisation on load, relu(x·in_scale + in_shift) per (image,
+// channel), applied when a.in_scale is set.  The launcher picks it for a conv that brings
+// in_scale and for every 128-wide map (launch_wino_k), so the loops of the decoder's convs
+// carry none of it.
+template <int W, int NBW, bool AFF>
 __device__ __forceinline__ void conv_wino_body(const WinoParams& P, int lbx, int lby, int lgx,
                                                int lgy, int sid) {
   using G = WinoGeom<W>;
@@ -222,29 +237,43 @@ __device__ __forceinline__ void conv_wino_body(const WinoParams& P, int lbx, int
   const int npix = a.n * a.h * W;
 
   // halo staging: four quarters of NA float4 per thread; slot (part, j) is the (pixel, channel
-  // quad) pair (idx >> 3, idx & 7), idx = tid + 256·(4j + part).  Per slot: the input pixel
-  // (-1 = zero padding) and the LDS float4 index, both stage-invariant.
+  // quad) pair (idx >> 3, idx & 7), idx = tid + 256·(4j + part).  Per slot the LDS float4 index
+  // hlds and hoff, which holds
+  // - HOFF (the form without the affine): the byte offset of the slot's 16 B from the stage's first
+  //   channel in the current source, WINO_OOB for a lane that reads zero.  It changes at most three
+  //   times per launch (hfix), the main loop is cut at those stages (below) and its loads use the
+  //   offsets as they are;
+  // - otherwise (AFF, the kernel as it was: no register to spare at 64 channels per workgroup):
+  //   the input pixel, -1 for zero padding, turned into an offset at every load.
+  constexpr bool HOFF = !AFF;
   bool inloop = false;  // tuning experiments (WX_NO_*): prologue loads still happen
-  int hpix[4][NA], hlds[4][NA];
+  int hoff[4][NA], hlds[4][NA];
+  auto hoffsets = [&](int ss4, bool with_lds) {  // ss4: the source's pixel stride in bytes
 #pragma unroll
-  for (int part = 0; part < 4; ++part)
+    for (int part = 0; part < 4; ++part)
 #pragma unroll
-    for (int j = 0; j < NA; ++j) {
-      const int idx = tid + NT * (4 * j + part);
-      const int pix = idx >> 3;
-      const int hr = pix / G::HC, hcol = pix - hr * G::HC;
-      const int iy = oy0 - 1 + hr, ix = ox0 - 1 + hcol;
-      const bool ok = idx < G::NH4 && iy >= 0 && iy < a.h && ix >= 0 && ix < W;
-      hpix[part][j] = ok ? (img * a.h + iy) * W + ix : -1;
-      hlds[part][j] = idx < G::NH4 ? G::addr(hr, hcol) + (idx & 7) : -1;
-    }
+      for (int j = 0; j < NA; ++j) {
+        const int idx = tid + NT * (4 * j + part);
+        const int pix = idx >> 3;
+        const int hr = pix / G::HC, hcol = pix - hr * G::HC;
+        const int iy = oy0 - 1 + hr, ix = ox0 - 1 + hcol;
+        const bool ok = idx < G::NH4 && iy >= 0 && iy < a.h && ix >= 0 && ix < W;
+        const int p = (img * a.h + iy) * W + ix;
+        hoff[part][j] = HOFF ? (ok ? p * ss4 + (idx & 7) * 16 : WINO_OOB) : (ok ? p : -1);
+        if (with_lds) hlds[part][j] = idx < G::NH4 ? G::addr(hr, hcol) + (idx & 7) : -1;
+      }
+  };
+  hoffsets((nst0 ? a.s0 : a.s1) * 4, true);  // the first source's
   const int hq4 = 4 * (tid & 7);  // channel of this thread's quad within the stage (idx & 7 = tid & 7)
   floatx4 ra[2][NA];  // quarter part in slot part & 1
-  // stage s's source, as a buffer starting at its first channel
+  // stage s's source, as a buffer starting at its first channel (scalar work only)
   __amdgpu_buffer_rsrc_t hsrc;
-  int hss4 = 0, hlim = 0;  // pixel stride in bytes, channels of the stage present in the source
-  floatx4 isc = {1.f, 1.f, 1.f, 1.f}, ish = {0.f, 0.f, 0.f, 0.f};  // input affine (encoder IN)
-  const bool in_aff = a.in_scale != nullptr;
+  int hss4 = 0, hlim = 0;  // pixel stride in bytes, channels of the source from the stage on
+  floatx4 isc = {1.f, 1.f, 1.f, 1.f}, ish = {0.f, 0.f, 0.f, 0.f};  // input affine (AFF: encoder IN)
+  // AFF is the kernel as it was before the affine became a template parameter, run-time flag
+  // included: its 64-channel instantiations sit at the 256-VGPR limit, and this form is the one
+  // known not to add scratch there
+  const bool in_aff = AFF && a.in_scale != nullptr;
   auto hsource = [&](int s) {
     const bool s1 = s >= nst0;
     const float* src = s1 ? a.src1 : a.src0;
@@ -259,6 +288,21 @@ __device__ __forceinline__ void conv_wino_body(const WinoParams& P, int lbx, int
       ish = *(const floatx4*)(a.in_shift + (size_t)img * a.c0 + cc + hq4);
     }
   };
+  // HOFF: the offsets for loading stage t, given those of stage t − 1.  Source 1's first stage
+  // brings its pixel stride; a source's last stage may hold fewer than WSC channels, and the lanes
+  // of the missing ones read zero from then on (what follows is source 1's hoffsets, or the end).
+  auto hfix = [&](int t) {
+    const bool s1 = t >= nst0;
+    if (t == nst0 && t > 0) hoffsets(a.s1 * 4, false);
+    const int lim = s1 ? a.c1 - (t - nst0) * WSC : a.c0 - t * WSC;
+    if (lim < WSC) {
+      const bool gone = hq4 >= lim;
+#pragma unroll
+      for (int part = 0; part < 4; ++part)
+#pragma unroll
+        for (int j = 0; j < NA; ++j) hoff[part][j] = gone ? WINO_OOB : hoff[part][j];
+    }
+  };
   auto hload = [&](int part) {
 #ifdef WX_NO_HALO
     if (inloop) return;
@@ -266,9 +310,9 @@ __device__ __forceinline__ void conv_wino_body(const WinoParams& P, int lbx, int
     const bool chan_ok = hq4 < hlim;
 #pragma unroll
     for (int j = 0; j < NA; ++j) {
-      const int p = hpix[part][j];
-      const bool ok = p >= 0 && chan_ok;
-      floatx4 v = wino_bload(hsrc, ok ? p * hss4 + hq4 * 4 : WINO_OOB, 0);
+      const int p = hoff[part][j];
+      const bool ok = HOFF ? p != WINO_OOB : p >= 0 && chan_ok;
+      floatx4 v = wino_bload(hsrc, HOFF ? p : (ok ? p * hss4 + hq4 * 4 : WINO_OOB), 0);
       if (in_aff && ok) {  // zero padding stays zero (it pads the normalised activation)
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e] * isc[e] + ish[e], 0.f);
@@ -388,6 +432,7 @@ __device__ __forceinline__ void conv_wino_body(const WinoParams& P, int lbx, int
   for (int d = 0; d < UAH; ++d)
 #pragma unroll
     for (int j = 0; j < 4; ++j) uload1(u[d][j], d, j);
+  if constexpr (HOFF) hfix(0);
   hsource(0);
 #pragma unroll
   for (int part = 0; part < 4; ++part) {
@@ -402,29 +447,41 @@ __device__ __forceinline__ void conv_wino_body(const WinoParams& P, int lbx, int
   floatx4 vA[4], vB[4];
   vcompute(0, 0, vA);
   inloop = true;
-  for (int s = 0; s < nst; ++s) {
-    const int buf = s & 1;
-    hsource(s + 1 < nst ? s + 1 : s);  // the last stage re-stages itself (no branches)
-    // sub-step t = 4s + k − 1 in slot t % UAH reloads its points for t + UAH
-    const int t0 = s * WNSUB;
-    hload(0);
-    substep_next(vA, t0 + UAH, 0, buf, 1, vB);
-    hstore(buf ^ 1, 0);
-    hload(1);
-    substep_next(vB, t0 + 1 + UAH, 1 % UAH, buf, 2, vA);
-    hstore(buf ^ 1, 1);
-    hload(2);
-    substep_next(vA, t0 + 2 + UAH, 2 % UAH, buf, 3, vB);
-    hstore(buf ^ 1, 2);
-    hload(3);
-    substep(vB, t0 + 3 + UAH, 3 % UAH);
-    hstore(buf ^ 1, 3);
+  // The stage loop.  HOFF: cut where the offsets change — iteration s loads stage t = s + 1 (the
+  // last one itself), so the inner loop runs up to the iteration that loads the next such stage
+  // and hfix stands outside it; otherwise one pass of the outer loop.
+  for (int s = 0; s < nst;) {
+    int send = nst;
+    if constexpr (HOFF) {
+      const int t = s + 1 < nst ? s + 1 : s;
+      hfix(t);
+      const int b = wino_next_change(t, nst0, nst, a.c0, a.c1, WSC);
+      if (b < nst) send = b - 1;
+    }
+    for (; s < send; ++s) {
+      const int buf = s & 1;
+      hsource(s + 1 < nst ? s + 1 : s);  // the last stage re-stages itself (no branches)
+      // sub-step t = 4s + k − 1 in slot t % UAH reloads its points for t + UAH
+      const int t0 = s * WNSUB;
+      hload(0);
+      substep_next(vA, t0 + UAH, 0, buf, 1, vB);
+      hstore(buf ^ 1, 0);
+      hload(1);
+      substep_next(vB, t0 + 1 + UAH, 1 % UAH, buf, 2, vA);
+      hstore(buf ^ 1, 1);
+      hload(2);
+      substep_next(vA, t0 + 2 + UAH, 2 % UAH, buf, 3, vB);
+      hstore(buf ^ 1, 2);
+      hload(3);
+      substep(vB, t0 + 3 + UAH, 3 % UAH);
+      hstore(buf ^ 1, 3);
 #ifndef WX_NO_SYNC
-    __syncthreads();
+      __syncthreads();
 #endif
 #ifndef WX_NO_V
-    vcompute(buf ^ 1, 0, vA);
+      vcompute(buf ^ 1, 0, vA);
 #endif
+    }
   }
 
 #ifdef WX_NO_EPI
@@ -570,9 +627,9 @@ __device__ __forceinline__ void conv_wino_body(const WinoParams& P, int lbx, int
   }
 }
 
-template <int W, int NBW>
+template <int W, int NBW, bool AFF>
 __global__ __launch_bounds__(256, NBW >= 3 ? 1 : 2) void conv_wino_kernel(WinoParams P) {
-  conv_wino_body<W, NBW>(P, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y,
+  conv_wino_body<W, NBW, AFF>(P, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y,
                          blockIdx.y * gridDim.x + blockIdx.x);
 }
 

@@ -109,41 +109,51 @@ __global__ __launch_bounds__(256, 2) void conv_wino5_kernel(Wino5Params P) {
   const int hy0 = DIR == 0 ? oy0 : oy0 - 2, hx0 = DIR == 0 ? -2 : ox0;
 
   // halo staging in two halves of NA float4 per thread: slot (part, j) is the (pixel, channel
-  // quad) pair (idx >> 3, idx & 7), idx = tid + 256·(2j + part)
-  int hpix[2][NA], hlds[2][NA];
-#pragma unroll
-  for (int part = 0; part < 2; ++part)
-#pragma unroll
-    for (int j = 0; j < NA; ++j) {
-      const int idx = tid + NTH * (2 * j + part);
-      const int pix = idx >> 3;
-      const int hr = pix / G::HC, hcol = pix - hr * G::HC;
-      const int iy = hy0 + hr, ix = hx0 + hcol;
-      const bool ok = idx < G::NH4 && iy >= 0 && iy < a.h && ix >= 0 && ix < W;
-      hpix[part][j] = ok ? (img * a.h + iy) * W + ix : -1;
-      hlds[part][j] = idx < G::NH4 ? G::addr(hr, hcol) + (idx & 7) : -1;
-    }
+  // quad) pair (idx >> 3, idx & 7), idx = tid + 256·(2j + part).  Per slot the LDS float4 index and
+  // the byte offset in the current source, WINO_OOB for a lane that reads zero (conv_wino.h: it
+  // changes at most three times per launch and the main loop is cut there).
+  int hoff[2][NA], hlds[2][NA];
   const int hq4 = 4 * (tid & 7);
+  auto hoffsets = [&](int ss4, bool with_lds) {  // ss4: the source's pixel stride in bytes
+#pragma unroll
+    for (int part = 0; part < 2; ++part)
+#pragma unroll
+      for (int j = 0; j < NA; ++j) {
+        const int idx = tid + NTH * (2 * j + part);
+        const int pix = idx >> 3;
+        const int hr = pix / G::HC, hcol = pix - hr * G::HC;
+        const int iy = hy0 + hr, ix = hx0 + hcol;
+        const bool ok = idx < G::NH4 && iy >= 0 && iy < a.h && ix >= 0 && ix < W;
+        const int p = (img * a.h + iy) * W + ix;
+        hoff[part][j] = ok ? p * ss4 + hq4 * 4 : WINO_OOB;
+        if (with_lds) hlds[part][j] = idx < G::NH4 ? G::addr(hr, hcol) + (idx & 7) : -1;
+      }
+  };
   floatx4 ra[NA];
   __amdgpu_buffer_rsrc_t hsrc;
-  int hss4 = 0, hlim = 0;
-  auto hsource = [&](int s) {
+  auto hsource = [&](int s) {  // stage s's source as a buffer from its first channel (scalar work)
     const bool s1 = s >= nst0;
     const float* src = s1 ? a.src1 : a.src0;
     const int cs = s1 ? a.c1 : a.c0;
     const int ss = s1 ? a.s1 : a.s0;
     const int cc = (s1 ? s - nst0 : s) * W5SC;
     hsrc = wino_rsrc(src + cc, (unsigned)(((long long)(npix - 1) * ss + cs - cc) * 4));
-    hss4 = ss * 4;
-    hlim = cs - cc;
+  };
+  auto hfix = [&](int t) {  // the offsets for loading stage t, given stage t − 1's (conv_wino.h)
+    const bool s1 = t >= nst0;
+    if (t == nst0 && t > 0) hoffsets(a.s1 * 4, false);
+    const int lim = s1 ? a.c1 - (t - nst0) * W5SC : a.c0 - t * W5SC;
+    if (lim < W5SC) {
+      const bool gone = hq4 >= lim;
+#pragma unroll
+      for (int part = 0; part < 2; ++part)
+#pragma unroll
+        for (int j = 0; j < NA; ++j) hoff[part][j] = gone ? WINO_OOB : hoff[part][j];
+    }
   };
   auto hload = [&](int part) {
-    const bool chan_ok = hq4 < hlim;
 #pragma unroll
-    for (int j = 0; j < NA; ++j) {
-      const int p = hpix[part][j];
-      ra[j] = wino_bload(hsrc, (p >= 0 && chan_ok) ? p * hss4 + hq4 * 4 : WINO_OOB, 0);
-    }
+    for (int j = 0; j < NA; ++j) ra[j] = wino_bload(hsrc, hoff[part][j], 0);
   };
   auto hstore = [&](int buf, int part) {
 #pragma unroll
@@ -230,6 +240,8 @@ __global__ __launch_bounds__(256, 2) void conv_wino5_kernel(Wino5Params P) {
     floatx4 d[8];
     uload1(0, 0);
     uload1(0, 1);
+    hoffsets((nst0 ? a.s0 : a.s1) * 4, true);
+    hfix(0);
     hsource(0);
     hload(0);
     hstore(0, 0);
@@ -243,28 +255,35 @@ __global__ __launch_bounds__(256, 2) void conv_wino5_kernel(Wino5Params P) {
     vmath(d, vA[0], w3);
     vload(0, 0, 1, d, w3);
     vmath(d, vA[1], w3);
-    for (int s = 0; s < nst; ++s) {
-      wino_prio(s, nst);
-      const int buf = s & 1;
-      const int t0 = s * W5NSUB;
-      hsource(s + 1 < nst ? s + 1 : s);  // the last stage re-stages itself (no branches)
-      hload(0);
-      vload(buf, 1, 0, d, w3);
-      half(vA, 0, t0 + 1);
-      vmath(d, vB[0], w3);
-      vload(buf, 1, 1, d, w3);
-      half(vA, 1, t0 + 1);
-      vmath(d, vB[1], w3);
-      hstore(buf ^ 1, 0);
-      hload(1);
-      half(vB, 0, t0 + 2);
-      half(vB, 1, t0 + 2);
-      hstore(buf ^ 1, 1);
-      __syncthreads();
-      vload(buf ^ 1, 0, 0, d, w3);
-      vmath(d, vA[0], w3);
-      vload(buf ^ 1, 0, 1, d, w3);
-      vmath(d, vA[1], w3);
+    // the stage loop, cut where the offsets change: hfix outside the inner loop (conv_wino.h)
+    for (int s = 0; s < nst;) {
+      const int t = s + 1 < nst ? s + 1 : s;
+      hfix(t);
+      const int b = wino_next_change(t, nst0, nst, a.c0, a.c1, W5SC);
+      const int send = b < nst ? b - 1 : nst;
+      for (; s < send; ++s) {
+        wino_prio(s, nst);
+        const int buf = s & 1;
+        const int t0 = s * W5NSUB;
+        hsource(s + 1 < nst ? s + 1 : s);  // the last stage re-stages itself (no branches)
+        hload(0);
+        vload(buf, 1, 0, d, w3);
+        half(vA, 0, t0 + 1);
+        vmath(d, vB[0], w3);
+        vload(buf, 1, 1, d, w3);
+        half(vA, 1, t0 + 1);
+        vmath(d, vB[1], w3);
+        hstore(buf ^ 1, 0);
+        hload(1);
+        half(vB, 0, t0 + 2);
+        half(vB, 1, t0 + 2);
+        hstore(buf ^ 1, 1);
+        __syncthreads();
+        vload(buf ^ 1, 0, 0, d, w3);
+        vmath(d, vA[0], w3);
+        vload(buf ^ 1, 0, 1, d, w3);
+        vmath(d, vA[1], w3);
+      }
     }
   };
   if (wave == 3)
